@@ -141,6 +141,47 @@ def loss_fn(out):
                            for k in ("sem_cls_logits", "center_normalized", "size_normalized")])
 
 
+def step_outputs(out):
+    """name -> tensor of what the model's forward hands its caller: every floating tensor of the box predictions of the final
+    stage (`outputs_*`) and of the auxiliary ones (`aux<i>_*`), and the sampled seed points"""
+    stages = [("outputs", out["outputs"])] + [(f"aux{i}", o) for i, o in enumerate(out["aux_outputs"])]
+    kept = {f"{s}_{k}": v.detach() for s, o in stages for k, v in o.items()
+            if not k.startswith("_") and torch.is_tensor(v) and v.is_floating_point()}
+    if torch.is_tensor(out.get("seed_xyz")):
+        kept["seed_xyz"] = out["seed_xyz"].detach()
+    return kept
+
+
+DUMP_SAMPLE = 1 << 20  # entries kept of a larger array: a fixed, seeded sample
+DUMP_LIMIT = 64 << 20  # bytes, all files together
+
+
+def dump_outputs(dirname, trainer, model):
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy per array (float32; the loss float64):
+    the loss, the predictions of every stage (step_outputs), and a fixed, seeded sample of the gradient w.r.t. the backbone
+    features and of the model state (parameters, running statistics) the step's update left.  The inputs depend on the arguments
+    only, so two builds run with the same arguments can be compared array by array."""
+    def sample(flat, seed):
+        if flat.numel() <= DUMP_SAMPLE:
+            return flat
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+        return flat[torch.from_numpy(idx).to(flat.device)]
+
+    arrays = {"loss": np.array([float(trainer.loss.item())], np.float64)}
+    arrays.update({k: v.float().cpu().numpy() for k, v in trainer.last_outputs.items()})
+    grads = [g.reshape(-1).float() for g in trainer.last_feature_grads if g is not None]
+    if grads:
+        arrays["backbone_features_grad"] = sample(torch.cat(grads), 1).cpu().numpy()
+    state = [v.detach().reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()]
+    arrays["model_state"] = sample(torch.cat(state), 2).cpu().numpy()
+    total = sum(x.nbytes for x in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT} allowed"
+    os.makedirs(dirname, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), x)
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {total / 2**20:.1f} MB in {dirname}", file=sys.stderr)
+
+
 def fps_fork_layer(t1, t_fps, nlayers):
     """LATEST decoder layer of the forward in front of which the next scene's sampling branch may be forked, or -1 (the step's start),
     from the measured step (t1 ms, sampling forked at the start) and the sampling alone (t_fps ms).  The one-workgroup kernel holds a
@@ -330,6 +371,8 @@ class Trainer:
         from vdetr_amd.runtime import ts_mark  # (no-ops unless VDETR_TS_PROBE=1: tools/probes/step_timeline.py)
         ts_mark("step start")
         out = self.model(self.inputs)
+        if self.keep_outputs:  # (captured: the same tensors are rewritten by every replay)
+            self.last_outputs = step_outputs(out)
         if self.fps_prefetch and not self.fps_depth2:
             if hook is not None:
                 hook.remove()
@@ -351,6 +394,8 @@ class Trainer:
         if self.fps_prefetch and not self.fps_depth2:
             main.wait_stream(self.side)
             self.cur_inds.copy_(next_inds)
+        if self.keep_outputs:
+            self.last_feature_grads = [f.grad for f in self.inputs["backbone_features"]]
         ts_mark("gradients packed, sampling joined")
 
     def _update(self):
@@ -372,6 +417,7 @@ class Trainer:
 
     quiesce_collectives = quiesce_collectives  # (module-level: BackboneTrainer takes it too)
     _capture_stream = None  # one per process: a second Trainer on the same model meets the first one's AccumulateGrad nodes
+    keep_outputs = False  # --dump-outputs: hold the step's predictions and feature gradients (last_outputs, last_feature_grads)
 
     def capture(self):
         if Trainer._capture_stream is None:
@@ -557,12 +603,16 @@ class BackboneTrainer:
             torch.cuda.current_stream().wait_event(ev)
             self.inputs["geometry"] = geo
             self.inds.copy_(inds)
+            inds.record_stream(torch.cuda.current_stream())  # (see below)
         if self._worker is not None:  # thread mode: what the loader thread prepared during the previous step
             self._worker.join()
             self._worker = None
             torch.cuda.current_stream().wait_stream(self.side)
             self.inputs["geometry"], inds = self._next
             self.inds.copy_(inds)
+            # the indices were allocated on the loader stream: without this, dropping them lets the allocator hand their block to
+            # the next scene's geometry on that stream while the copy above is still queued here (the gather then reads garbage rows)
+            inds.record_stream(torch.cuda.current_stream())
         import threading
         mode = os.environ.get("VDETR_BENCH_GEOMETRY", "thread")  # A/B switch: thread | inline | static (first scene's geometry reused)
         marks = getattr(self, "marks", None)  # (tools/backbone_step_probe.py --timeline: events between the phases of the step)
@@ -992,7 +1042,11 @@ def main():
                     "the N>1 code path with several ranks on one GPU)")
     ap.add_argument("--launch-check", action="store_true", help="start the ranks, form the process group, all-reduce one "
                     "number, print a JSON line and leave: the launcher path without a GPU (tests/test_dist_gloo.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(rank 0; float32 / float64, at most 64 MB: dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # `python bench.py --gpus N` with nobody else having started the ranks: start them here, one process per GPU, as the
@@ -1162,6 +1216,7 @@ def main():
         return tr1
 
     crit_holder = [None, None]
+    Trainer.keep_outputs = bool(a.dump_outputs)
     trainer = make_trainer(a.loss == "criterion")
     graph_ok = False
     def all_ranks(ok):
@@ -1238,6 +1293,13 @@ def main():
     # slower than the steady state (20 timed steps after 0 / 3 / 5 / 30 warm-up steps: 8.19 / 8.15 / 8.10 / 8.06 ms), whatever W
     # the caller asks for.  Real training steps on every rank; recorded in config.settle_steps.
     settle = int(os.environ.get("VDETR_BENCH_SETTLE", "25")) if graph_ok else 0
+    # The dropout masks of the steps below do not depend on how many steps the capture and the measured choice of the sampling
+    # look-ahead ran before them: every run starts them from the same generator offset (written in place: captured steps read it).
+    from vdetr_amd import attention as _A
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        for st in _A._master.values():
+            st[1] = 0
     for _ in range(settle):
         trainer.step()
     for _ in range(a.warmup):
@@ -1258,6 +1320,11 @@ def main():
         dt = float(tt.item())
     loss = float(trainer.loss.item())
     assert np.isfinite(loss), "non-finite loss"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, trainer, model)
+    # the secondary measurements below run as without --dump-outputs
+    Trainer.keep_outputs = False
+    trainer.last_outputs = trainer.last_feature_grads = None
 
     npts, bs, npre, nq, nl, _, desc = CONFIGS[a.config]
     result = {
@@ -1293,11 +1360,16 @@ def main():
     if a.config == "c2":  # decoder fwd+bwd = 216 GFLOP per scene at the full configuration
         result["end_to_end"] = {"gflop_per_scene": 216.0, "achieved_tflops": 216.0e-3 * result["value"],
                                 "note": "algorithmic decoder flops (SURVEY 8d) x scenes/s, all GPUs"}
+    failed_legs = []
+
     def leg(name, fn):
-        """The headline line must be printed whatever happens in a secondary measurement."""
+        """The headline line must be printed whatever happens in a secondary measurement.  What a failed leg built stays alive
+        (its exception holds the leg's frames) and the process leaves without the interpreter's teardown: a graph whose capture
+        failed cannot be destroyed (see relaunch)."""
         try:
             fn()
         except Exception as exc:  # noqa: BLE001
+            failed_legs.append(exc)
             result[name] = {"error": f"{type(exc).__name__}: {exc}"}
             print(f"[bench] {name} leg failed: {type(exc).__name__}: {exc}", file=sys.stderr)
 
@@ -1534,6 +1606,15 @@ def main():
             sys.stdout.flush()
             sys.stderr.flush()
             os._exit(rc)
+    if failed_legs:
+        try:
+            from vdetr_amd.runtime import finish_gemm_tuning
+            finish_gemm_tuning()
+        except Exception as exc:  # noqa: BLE001
+            print(f"[bench] GEMM-tuning results not published: {type(exc).__name__}: {exc}", file=sys.stderr)
+        sys.stdout.flush()
+        sys.stderr.flush()
+        os._exit(0)
 
 
 if __name__ == "__main__":

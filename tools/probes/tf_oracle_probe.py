@@ -1,5 +1,6 @@
 import sys, os, time, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle.attention_oracle import fused_attention_reference
 from vdetr_amd import attention as A
 dev = "cuda"
