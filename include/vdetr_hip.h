@@ -835,6 +835,31 @@ int vdetr_set_loss_f32(const vdetr_setloss_desc* d, vdetr_stream_t stream);
 /* the same for n descriptors (HOST array: all stages of a step + the seed-point loss) in one launch per 12 descriptors */
 int vdetr_set_loss_batch_f32(const vdetr_setloss_desc* descs, int n, vdetr_stream_t stream);
 
+/* Box-overlap term of the matcher cost and of loss_giou (criterion.py --iou_type, main.py:110).  VDETR_IOU_GIOU is the GIoU
+ * of the 8 corners, as the entry points above compute it.  VDETR_IOU_DIOU / _IOU are the rotated 3-D DIoU / IoU of the boxes
+ * (x, y, z, w, h, l, alpha) = (center_unnormalized, size_unnormalized, angle_continuous) against (gt_box_centers,
+ * gt_box_sizes, gt_box_angles) (criterion.py:25-64, 620-633: diff_diou_rotated_3d / mmcv diff_iou_rotated_3d); slots
+ * >= nactual[b] are 0.  In these two modes `corners` / `rotated` of the descriptors are not read, and the set loss
+ * differentiates the box parameters instead of the corners. */
+#define VDETR_IOU_GIOU 0
+#define VDETR_IOU_DIOU 1
+#define VDETR_IOU_IOU 2
+typedef struct vdetr_iou_ext {
+  int32_t iou_kind;        /* VDETR_IOU_* */
+  int32_t reserved;
+  const float *center, *size; /* [B,P,3] center_unnormalized, size_unnormalized (DIOU / IOU) */
+  const float* angle;      /* [B,P] angle_continuous (DIOU / IOU) */
+  float *d_center, *d_size; /* [B,P,3] set loss, DIOU / IOU: d total / d center, size; written in full (0 where unmatched) */
+  float* d_angle;          /* [B,P] the same for the angle */
+} vdetr_iou_ext;
+/* vdetr_match_cost_batch_f32 / vdetr_set_loss_batch_f32 with one extension per descriptor (HOST arrays of n each).
+ * Every descriptor with box terms must carry the same iou_kind; the extension of a classification-only set-loss descriptor
+ * (center_reg == NULL: the seed-point loss) is not read.  In DIOU / IOU mode the set loss needs neither `corners` nor
+ * `d_corners`; a non-NULL d_corners is written with zeros.  Status 1 with vdetr_last_error: exts == NULL, an unknown
+ * iou_kind, mixed kinds, or a NULL box-parameter / gradient pointer that the kind needs. */
+int vdetr_match_cost_ext_batch_f32(const vdetr_match_desc* descs, const vdetr_iou_ext* exts, int n, vdetr_stream_t stream);
+int vdetr_set_loss_ext_batch_f32(const vdetr_setloss_desc* descs, const vdetr_iou_ext* exts, int n, vdetr_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Greedy 3-D NMS of a scene's predictions (reference utils/nms.py:78-162 nms_3d_faster /
  * nms_3d_faster_samecls as called from utils/ap_calculator.py:165-220 on the min / max extents of the 8 box corners).

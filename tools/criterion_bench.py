@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the device criterion alone (C2 shapes, outputs of the randomly initialised model) and reports the solver's
-row-scan counts:  python tools/criterion_bench.py [--boxes 24]"""
+row-scan counts:  python tools/criterion_bench.py [--boxes 24] [--iou-type giou|diou|iou]"""
 import argparse
 import os
 import sys
@@ -16,13 +16,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--boxes", type=int, default=24)
     ap.add_argument("--config", default="c2")
+    ap.add_argument("--iou-type", default="giou", choices=("giou", "diou", "iou"))
     a = ap.parse_args()
     from vdetr_amd.criterion import Matcher, build_criterion, default_criterion_args
     dev = torch.device("cuda", 0)
     model = bench.build_model(a.config, dev)
     inputs = bench.make_inputs(a.config, dev, 0)
     targets = bench.make_targets(a.config, dev, 0, boxes_per_scene=a.boxes)
-    crit = build_criterion(default_criterion_args(), model.dataset_config)
+    crit = build_criterion(default_criterion_args(iou_type=a.iou_type), model.dataset_config)
     out = model(inputs)
     prep = crit.prepare_targets(targets)
 
@@ -40,7 +41,8 @@ def main():
         run()
     e1.record()
     torch.cuda.synchronize()
-    print(f"criterion fwd+bwd (eager launches, decoder backward included): {e0.elapsed_time(e1) / 10:.3f} ms")
+    print(f"criterion fwd+bwd, iou_type {a.iou_type} (eager launches, decoder backward included): "
+          f"{e0.elapsed_time(e1) / 10:.3f} ms")
     # solver alone + scan counts
     stages = [(out["outputs"], True, -1)] + [((o, False, 0) if k == 0 else (o, True, -1)) for k, o in enumerate(out["aux_outputs"])]
     problems = []

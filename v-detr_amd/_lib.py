@@ -256,6 +256,17 @@ class SetLossDesc(ctypes.Structure):
                 [(n, c_void_p) for n in _LOSS_PTR])
 
 
+VDETR_IOU_GIOU, VDETR_IOU_DIOU, VDETR_IOU_IOU = 0, 1, 2
+IOU_KINDS = {"giou": VDETR_IOU_GIOU, "diou": VDETR_IOU_DIOU, "iou": VDETR_IOU_IOU}
+
+
+class IouExt(ctypes.Structure):
+    """Mirror of ``vdetr_iou_ext``."""
+
+    _fields_ = [("iou_kind", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [
+        (n, c_void_p) for n in ("center", "size", "angle", "d_center", "d_size", "d_angle")]
+
+
 class SpBnDesc(ctypes.Structure):
     """Mirror of ``vdetr_spbn_desc``."""
 
@@ -350,6 +361,8 @@ _SIGNATURES = {
     "vdetr_point_labels_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vdetr_set_loss_f32": (c_int, [ctypes.POINTER(SetLossDesc), c_void_p]),
     "vdetr_set_loss_batch_f32": (c_int, [ctypes.POINTER(SetLossDesc), c_int, c_void_p]),
+    "vdetr_match_cost_ext_batch_f32": (c_int, [ctypes.POINTER(MatchDesc), ctypes.POINTER(IouExt), c_int, c_void_p]),
+    "vdetr_set_loss_ext_batch_f32": (c_int, [ctypes.POINTER(SetLossDesc), ctypes.POINTER(IouExt), c_int, c_void_p]),
     "vdetr_sp_kernel_map_i32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vdetr_sp_inverse_map_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_sp_gather_cols_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -16,11 +16,13 @@ No host synchronisation anywhere (the reference has >= 30 per step: ``.item()``,
 integers), so the whole training step including the criterion can be captured in one hipGraph.  ``nactual_gt`` and
 ``num_boxes`` stay device tensors.
 
-Scope: ``cls_loss`` "focalloss_<alpha>" (default) or "celoss" (3DETR's weighted cross entropy), ``iou_type="giou"``; the
-mmcv-based diou / iou variants raise.  Rotated ground
-truth (any ``gt_box_angles`` > 0, criterion.py:616) switches the GIoU's footprint overlap to the polygon clip of
-box_util.py:566-589 through a device flag -- the reference decides that with ``.item()``.  There is no CPU path: CPU
-tensors raise.
+Scope: ``cls_loss`` "focalloss_<alpha>" (default) or "celoss" (3DETR's weighted cross entropy); ``iou_type`` "giou"
+(default), "diou" or "iou".  With "giou", rotated ground truth (any ``gt_box_angles`` > 0, criterion.py:616) switches the
+GIoU's footprint overlap to the polygon clip of box_util.py:566-589 through a device flag -- the reference decides that
+with ``.item()``.  "diou" / "iou" are the rotated 3-D DIoU / IoU of (center_unnormalized, size_unnormalized,
+angle_continuous) against the ground truth's (centre, size, angle) (criterion.py:25-64, 620-633; mmcv's
+diff_iou_rotated_3d), computed in the same two kernels (csrc/rot_iou.h); their gradient goes to those three outputs
+instead of ``box_corners``, which then receives none.  There is no CPU path: CPU tensors raise.
 """
 import ctypes
 
@@ -31,6 +33,9 @@ import torch.nn as nn
 from . import _lib as L
 
 _DIFF = ("sem_cls_logits", "center_reg", "size_reg", "box_corners", "angle_logits", "angle_residual_normalized")
+# iou_type "diou" / "iou": the box-overlap term differentiates the decoded box parameters instead of the corners
+_DIFF_ROT = ("sem_cls_logits", "center_reg", "size_reg", "angle_logits", "angle_residual_normalized", "center_unnormalized",
+             "size_unnormalized", "angle_continuous")
 LOSS_NAMES = ("loss_sem_cls", "loss_angle_cls", "loss_angle_reg", "loss_center", "loss_size", "loss_giou", "loss_cardinality")
 
 
@@ -83,6 +88,13 @@ class PreparedTargets:
         return self.gt, self.G, self.nactual, self.num_boxes[0:1]
 
 
+def iou_kind(iou_type):
+    """--iou_type (main.py:110) -> VDETR_IOU_*"""
+    if iou_type not in L.IOU_KINDS:
+        raise ValueError(f"iou_type must be one of {sorted(L.IOU_KINDS)}, not {iou_type!r}")
+    return L.IOU_KINDS[iou_type]
+
+
 class Matcher(nn.Module):
     """criterion.py:100-228.  ``forward`` matches ONE stage (API parity); SetCriterion batches all stages in one solve."""
 
@@ -93,19 +105,28 @@ class Matcher(nn.Module):
         self.cost_center, self.cost_size = cost_center, cost_size
         self.matcher_anglecls_cost = args.matcher_anglecls_cost
         self.matcher_anglereg_cost = args.matcher_anglereg_cost
+        self.iou_kind = iou_kind(getattr(args, "iou_type", "giou"))
 
     def cost(self, o, records, G, nactual, label_override=-1, want_giou=False, rotated=None):
         """Launches the pairwise kernel of one stage.  Returns (cost_t [B,G,P], giou_t or None).  ``rotated``: device scalar
         (PreparedTargets.rotated) selecting the polygon-clip footprint overlap, None = axis-aligned."""
         d, keep = self._cost_desc(o, records, G, nactual, label_override, want_giou, rotated)
-        L.check(L.lib().vdetr_match_cost_f32(ctypes.byref(d), L.stream_ptr()), "match_cost")
+        if self.iou_kind == L.VDETR_IOU_GIOU:
+            L.check(L.lib().vdetr_match_cost_f32(ctypes.byref(d), L.stream_ptr()), "match_cost")
+        else:
+            L.check(L.lib().vdetr_match_cost_ext_batch_f32(ctypes.byref(d), ctypes.byref(keep["ext"]), 1, L.stream_ptr()),
+                    "match_cost")
         return keep["cost_t"], keep["giou_t"]
 
     def cost_batch(self, items, rotated=None):
         """items: [(stage outputs, records, G, nactual, label_override)] -> [cost_t]; ONE launch for all stages."""
         built = [self._cost_desc(*it, rotated=rotated) for it in items]
         arr = (L.MatchDesc * len(built))(*[d for d, _ in built])
-        L.check(L.lib().vdetr_match_cost_batch_f32(arr, len(built), L.stream_ptr()), "match_cost")
+        if self.iou_kind == L.VDETR_IOU_GIOU:
+            L.check(L.lib().vdetr_match_cost_batch_f32(arr, len(built), L.stream_ptr()), "match_cost")
+        else:
+            exts = (L.IouExt * len(built))(*[keep["ext"] for _, keep in built])
+            L.check(L.lib().vdetr_match_cost_ext_batch_f32(arr, exts, len(built), L.stream_ptr()), "match_cost")
         return [keep["cost_t"] for _, keep in built]
 
     def _cost_desc(self, o, records, G, nactual, label_override=-1, want_giou=False, rotated=None):
@@ -119,10 +140,16 @@ class Matcher(nn.Module):
         d.w_cls, d.w_objectness, d.w_center, d.w_giou = self.cost_class, self.cost_objectness, self.cost_center, self.cost_giou
         d.w_size, d.w_angle_cls, d.w_angle_reg = self.cost_size, self.matcher_anglecls_cost, self.matcher_anglereg_cost
         keep = {"cls": cls, "gt": records, "nactual": nactual, "rotated": rotated}
+        rot = self.iou_kind != L.VDETR_IOU_GIOU
         for dst, src in (("objectness", "objectness_prob"), ("center_reg", "center_reg"), ("size_reg", "size_reg"),
                          ("pre_center", "pre_box_center_unnormalized"), ("pre_size", "pre_box_size_unnormalized"),
                          ("corners", "box_corners"), ("angle_logits", "angle_logits"),
-                         ("angle_res_norm", "angle_residual_normalized")):
+                         ("angle_res_norm", "angle_residual_normalized")) + (
+                            (("box_center", "center_unnormalized"), ("box_size", "size_unnormalized"),
+                             ("box_angle", "angle_continuous")) if rot else ()):
+            if rot and dst == "corners" and src not in o:
+                keep[dst] = None  # the rotated DIoU / IoU do not read the corners
+                continue
             t = o[src].detach()
             L.require_gpu(t, src)
             L.require_float(t, src)
@@ -130,7 +157,11 @@ class Matcher(nn.Module):
         keep["cost_t"] = cls.new_empty((B, G, P))
         keep["giou_t"] = cls.new_empty((B, G, P)) if want_giou else None
         for k, t in keep.items():
-            setattr(d, k, t.data_ptr() if t is not None else None)
+            if not k.startswith("box_"):
+                setattr(d, k, t.data_ptr() if t is not None else None)
+        if rot:
+            keep["ext"] = L.IouExt(iou_kind=self.iou_kind, center=keep["box_center"].data_ptr(),
+                                   size=keep["box_size"].data_ptr(), angle=keep["box_angle"].data_ptr())
         return d, keep
 
     @staticmethod
@@ -202,13 +233,15 @@ class _CriterionFn(torch.autograd.Function):
         problems = [(c, mt[2], prep.repeat if rep else 0) for c, mt, (_, rep, _) in zip(costs, metas, stages)]
         matches = m.solve(problems)
         lib, st = L.lib(), L.stream_ptr()
-        keep, loss_descs = [], []
+        keep, loss_descs, exts = [], [], []
+        names = crit.diff_names
+        nd = len(names)
         for si, ((o, repeated, override), (records, G, nactual, nb, _), (inds, mask)) in enumerate(zip(stages, metas, matches)):
-            ins = [t.detach().contiguous() for t in diff[si * 6:si * 6 + 6]]
-            g = grads[si * 6:si * 6 + 6]
-            B, P, C = ins[0].shape
+            ins = dict(zip(names, (t.detach().contiguous() for t in diff[si * nd:si * nd + nd])))
+            g = dict(zip(names, grads[si * nd:si * nd + nd]))
+            B, P, C = ins["sem_cls_logits"].shape
             d = L.SetLossDesc()
-            d.B, d.P, d.G, d.C, d.A, d.label_override = B, P, G, C, ins[4].shape[-1], override
+            d.B, d.P, d.G, d.C, d.A, d.label_override = B, P, G, C, ins["angle_logits"].shape[-1], override
             d.focal_alpha = crit.focal_alpha
             d.cls_kind = L.VDETR_CLS_SIGMOID if crit.focal else L.VDETR_CLS_SOFTMAX
             d.w_no_object = crit.no_object_weight
@@ -217,18 +250,25 @@ class _CriterionFn(torch.autograd.Function):
             d.w_center, d.w_size, d.w_giou = w["loss_center_weight"], w["loss_size_weight"], w["loss_giou_weight"]
             pre_c = o["pre_box_center_unnormalized"].detach().contiguous()
             pre_s = o["pre_box_size_unnormalized"].detach().contiguous()
-            d.cls_logits, d.center_reg, d.size_reg, d.corners = (ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(),
-                                                                 ins[3].data_ptr())
-            d.angle_logits, d.angle_res_norm = ins[4].data_ptr(), ins[5].data_ptr()
+            d.cls_logits, d.center_reg, d.size_reg = (ins["sem_cls_logits"].data_ptr(), ins["center_reg"].data_ptr(),
+                                                      ins["size_reg"].data_ptr())
+            d.corners = ins["box_corners"].data_ptr() if "box_corners" in ins else None
+            d.angle_logits, d.angle_res_norm = ins["angle_logits"].data_ptr(), ins["angle_residual_normalized"].data_ptr()
             d.pre_center, d.pre_size = pre_c.data_ptr(), pre_s.data_ptr()
             d.gt, d.nactual, d.inds, d.mask, d.labels = records.data_ptr(), nactual.data_ptr(), inds.data_ptr(), mask.data_ptr(), None
             d.num_boxes = nb.data_ptr()
             d.rotated = prep.rotated.data_ptr()
             d.losses = losses[si].data_ptr()
             d.card_ws = losses[si].data_ptr() + 32
-            (d.d_cls_logits, d.d_center_reg, d.d_size_reg, d.d_corners, d.d_angle_logits,
-             d.d_angle_res_norm) = (t.data_ptr() for t in g)
+            (d.d_cls_logits, d.d_center_reg, d.d_size_reg, d.d_angle_logits, d.d_angle_res_norm) = (
+                g[k].data_ptr() for k in ("sem_cls_logits", "center_reg", "size_reg", "angle_logits", "angle_residual_normalized"))
+            d.d_corners = g["box_corners"].data_ptr() if "box_corners" in g else None
+            e = L.IouExt(iou_kind=crit.iou_kind)
+            if crit.iou_kind != L.VDETR_IOU_GIOU:
+                e.center, e.size, e.angle = (ins[k].data_ptr() for k in ("center_unnormalized", "size_unnormalized", "angle_continuous"))
+                e.d_center, e.d_size, e.d_angle = (g[k].data_ptr() for k in ("center_unnormalized", "size_unnormalized", "angle_continuous"))
             loss_descs.append(d)
+            exts.append(e)
             keep.append((ins, pre_c, pre_s))
         point_labels = None
         if point is not None:
@@ -252,10 +292,14 @@ class _CriterionFn(torch.autograd.Function):
             d.losses, d.d_cls_logits = losses[ns].data_ptr(), grads[-1].data_ptr()
             d.card_ws = losses[ns].data_ptr() + 32
             loss_descs.append(d)
+            exts.append(L.IouExt(iou_kind=crit.iou_kind))  # classification only: not read
             keep.append((seed_xyz, logits, inside))
         # every stage's losses + gradients and the seed-point loss: ONE launch
         arr = (L.SetLossDesc * len(loss_descs))(*loss_descs)
-        L.check(lib.vdetr_set_loss_batch_f32(arr, len(loss_descs), st), "set_loss")
+        if crit.iou_kind == L.VDETR_IOU_GIOU:
+            L.check(lib.vdetr_set_loss_batch_f32(arr, len(loss_descs), st), "set_loss")
+        else:
+            L.check(lib.vdetr_set_loss_ext_batch_f32(arr, (L.IouExt * len(exts))(*exts), len(loss_descs), st), "set_loss")
         total = losses[:, 7].sum()
         ctx.flat, ctx.grads = flat, grads
         ctx.mark_non_differentiable(losses)
@@ -282,8 +326,9 @@ class SetCriterion(nn.Module):
         self.args, self.dataset_config, self.matcher = args, dataset_config, matcher
         self.loss_weight_dict = dict(loss_weight_dict)
         self.is_bilable, self.repeat_num, self.iou_type = args.is_bilable, args.repeat_num, args.iou_type
-        if self.iou_type != "giou":
-            raise NotImplementedError("iou_type 'diou' / 'iou' need mmcv's rotated-IoU ops (criterion.py:21-22); only 'giou'")
+        self.iou_kind = iou_kind(self.iou_type)
+        # the differentiable inputs of every stage, in this order
+        self.diff_names = _DIFF if self.iou_kind == L.VDETR_IOU_GIOU else _DIFF_ROT
         # class loss: "focalloss_<alpha>" (the default, main.py:127) or the weighted cross entropy of 3DETR ("celoss": the
         # logits then carry a trailing "no object" class weighted by loss_no_object_weight, criterion.py:240-246)
         self.focal = args.cls_loss.split("_")[0] == "focalloss"
@@ -306,7 +351,7 @@ class SetCriterion(nn.Module):
         stages = [(outputs["outputs"], True, -1)]
         for k, o in enumerate(aux):
             stages.append((o, False, 0) if (k == 0 and self.is_bilable) else (o, True, -1))
-        diff = [o[k] for o, _, _ in stages for k in _DIFF]
+        diff = [o[k] for o, _, _ in stages for k in self.diff_names]
         point = None
         if "enc_outputs" in outputs:
             assert "point_cls_logits" in outputs["enc_outputs"]
@@ -344,7 +389,8 @@ def build_criterion(args, dataset_config):
 
 
 def default_criterion_args(**overrides):
-    """The criterion-related defaults of the reference's argument parser (main.py:86-137)."""
+    """The criterion-related defaults of the reference's argument parser (main.py:86-137); ``iou_type`` "giou" (the
+    reference's default) or "diou" / "iou"."""
     from argparse import Namespace
     a = dict(cls_loss="focalloss_0.25", is_bilable=True, repeat_num=5, iou_type="giou", point_cls_loss_weight=0.05,
              matcher_giou_cost=2.0, matcher_cls_cost=3.0, matcher_center_cost=1.0, matcher_objectness_cost=0.0,

@@ -3,13 +3,15 @@
 // The reference builds three [B,P,G] matrices with ~60 torch launches per stage, copies the cost to the host, runs
 // scipy's Hungarian solver there (9 x per step, each behind a device->host sync), copies the assignment back and
 // gathers the matched losses from the matrices.  Here, per stage:
-//   match_cost_kernel   one launch: GIoU + centre + size + class terms -> cost, stored box-major so the solver reads rows
+//   match_cost_kernel   one launch: GIoU (or the rotated DIoU / IoU of rot_iou.h) + centre + size + class terms -> cost,
+//                       stored box-major so the solver reads rows
 //   lsa_kernel          ONE launch for all stages: a workgroup per (stage, scene) runs the same shortest-augmenting-path
 //                       algorithm as scipy in fp64, columns spread over the lanes, state in registers / LDS
 //   set_loss_kernel     one launch: matched losses AND their gradients (the pairwise matrices are never needed again)
 // Everything is latency-bound integer/fp32 work of a few hundred KB; the design goals are launch count, no host round
 // trip (the whole step stays capturable in a hipGraph) and bit-identical assignments.
 #include "wave.h"
+#include "rot_iou.h"
 
 #include <stdlib.h>
 
@@ -254,11 +256,30 @@ struct MatchBatch {
 struct LossBatch {
   vdetr_setloss_desc d[kCritBatch];
 };
+// the kernels' argument per box-overlap kind (VDETR_IOU_*): the DIoU / IoU instantiations also carry the extensions
+template <int KIND>
+struct MatchLaunch : MatchBatch {
+  vdetr_iou_ext e[kCritBatch];
+};
+template <>
+struct MatchLaunch<VDETR_IOU_GIOU> : MatchBatch {};
+template <int KIND>
+struct LossLaunch : LossBatch {
+  vdetr_iou_ext e[kCritBatch];
+};
+template <>
+struct LossLaunch<VDETR_IOU_GIOU> : LossBatch {};
+
+struct GtRot {  // the ground truth's angle and its sine / cosine (rotated DIoU / IoU)
+  float angle, s, c;
+};
 
 // All stages of a step in ONE launch: blockIdx.z enumerates (stage, scene); the grid is sized for the largest stage and
 // the workgroups outside a smaller stage's extent leave at once.
-__global__ __launch_bounds__(256) void match_cost_kernel(MatchBatch batch) {
+template <int KIND>
+__global__ __launch_bounds__(256) void match_cost_kernel(MatchLaunch<KIND> batch) {
   __shared__ GtDerived sh[kMatchBoxes];
+  __shared__ GtRot shr[KIND == VDETR_IOU_GIOU ? 1 : kMatchBoxes];
   int z = blockIdx.z, stage = 0;
   while (z >= batch.d[stage].B) z -= batch.d[stage++].B;
   const vdetr_match_desc d = batch.d[stage];
@@ -276,15 +297,30 @@ __global__ __launch_bounds__(256) void match_cost_kernel(MatchBatch batch) {
     s.label = d.label_override >= 0 ? d.label_override : (int)r[VDETR_GT_LABEL];
     s.alabel = (int)r[VDETR_GT_ANGLE_CLS];
     s.ares_norm = r[VDETR_GT_ANGLE_RES] / (3.14159265358979323846f / (float)d.A);
+    if constexpr (KIND != VDETR_IOU_GIOU) {
+      shr[threadIdx.x].angle = r[VDETR_GT_ANGLE];
+      sincosf(r[VDETR_GT_ANGLE], &shr[threadIdx.x].s, &shr[threadIdx.x].c);
+    }
   }
   __syncthreads();
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= d.P) return;
   const size_t row = (size_t)b * d.P + p;
-  const BoxGeo pg = box_geo(d.corners + row * 24);
-  const bool rot = d.rotated != nullptr && d.rotated[0] != 0.f;
+  BoxGeo pg;
+  bool rot = false;
   float pfx[4], pfz[4];
-  footprint(d.corners + row * 24, pfx, pfz);
+  float pbox[7], psin = 0.f, pcos = 1.f;  // rotated DIoU / IoU: (centre, size, angle) of the prediction
+  if constexpr (KIND == VDETR_IOU_GIOU) {
+    pg = box_geo(d.corners + row * 24);
+    rot = d.rotated != nullptr && d.rotated[0] != 0.f;
+    footprint(d.corners + row * 24, pfx, pfz);
+  } else {
+    const vdetr_iou_ext& e = batch.e[stage];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) pbox[a] = e.center[row * 3 + a], pbox[3 + a] = e.size[row * 3 + a];
+    pbox[6] = e.angle[row];
+    sincosf(pbox[6], &psin, &pcos);
+  }
   float creg[3], sreg[3], pc[3], ps[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -301,14 +337,20 @@ __global__ __launch_bounds__(256) void match_cost_kernel(MatchBatch batch) {
 #pragma unroll 4
   for (int gi = 0; gi < ng; ++gi) {
     const GtDerived& s = sh[gi];
-    float area = aligned_overlap(pg, s.geo);
-    if (rot && area != 0.f && g0 + gi < nact) {  // box_util.py:571-589
-      float gfx[4], gfz[4];
+    float giou;
+    if constexpr (KIND == VDETR_IOU_GIOU) {
+      float area = aligned_overlap(pg, s.geo);
+      if (rot && area != 0.f && g0 + gi < nact) {  // box_util.py:571-589
+        float gfx[4], gfz[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) gfx[i] = s.fx[i], gfz[i] = s.fz[i];
-      area = 0.5f * clip_area2<0>(pfx, pfz, gfx, gfz, nullptr);
+        for (int i = 0; i < 4; ++i) gfx[i] = s.fx[i], gfz[i] = s.fz[i];
+        area = 0.5f * clip_area2<0>(pfx, pfz, gfx, gfz, nullptr);
+      }
+      giou = giou_pair(pg, s.geo, area);
+    } else {  // gious *= mask (criterion.py:630-633): the cost sees the masked value too
+      const float gbox[7] = {s.center[0], s.center[1], s.center[2], s.size[0], s.size[1], s.size[2], shr[gi].angle};
+      giou = g0 + gi < nact ? rot_iou_pair<float>(pbox, psin, pcos, gbox, shr[gi].s, shr[gi].c, KIND == VDETR_IOU_DIOU) : 0.f;
     }
-    const float giou = giou_pair(pg, s.geo, area);
     float center = 0.f, size = 0.f;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -726,7 +768,8 @@ constexpr int kLossRows = 256;  // rows (proposals / seed points) per workgroup
 
 // Phase A, one thread per row: the row's label, the box terms of its matched pair with their gradients, the arg-max for
 // the cardinality count.  Phase B, all threads over the chunk's rows x C logits (coalesced): focal loss + gradient.
-__global__ __launch_bounds__(kLossRows) void set_loss_kernel(LossBatch batch) {
+template <int KIND>
+__global__ __launch_bounds__(kLossRows) void set_loss_kernel(LossLaunch<KIND> batch) {
   __shared__ float red[kLossRows / 64][8];
   __shared__ int lab[kLossRows];
   int z = blockIdx.y, stage = 0;
@@ -789,9 +832,10 @@ __global__ __launch_bounds__(kLossRows) void set_loss_kernel(LossBatch batch) {
     }
     if (boxes) {
       float d_creg[3] = {0.f, 0.f, 0.f}, d_sreg[3] = {0.f, 0.f, 0.f};
-      float dc[24];
+      float dc[KIND == VDETR_IOU_GIOU ? 24 : 1];
+      float dbox[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // DIoU / IoU: d total / d (centre, size, angle)
 #pragma unroll
-      for (int k = 0; k < 24; ++k) dc[k] = 0.f;
+      for (int k = 0; k < (KIND == VDETR_IOU_GIOU ? 24 : 1); ++k) dc[k] = 0.f;
       int alabel = 0;
       float g_areg = 0.f;
       const bool active = matched && gate;
@@ -807,13 +851,35 @@ __global__ __launch_bounds__(kLossRows) void set_loss_kernel(LossBatch batch) {
           acc[4] += fabsf(es);
           d_sreg[a] = sgn(es) * (d.w_size * inv_nb);
         }
-        float c[24];
+        if constexpr (KIND == VDETR_IOU_GIOU) {
+          float c[24];
 #pragma unroll
-        for (int k = 0; k < 24; ++k) c[k] = d.corners[row * 24 + k];
-        const BoxGeo pg = box_geo(c), gg = box_geo(r + VDETR_GT_CORNERS);
-        const bool rot = d.rotated != nullptr && d.rotated[0] != 0.f;
-        const float giou = gi < (int)d.nactual[b] ? giou_grad(c, pg, gg, d.w_giou * inv_nb, dc, rot, r + VDETR_GT_CORNERS) : 0.f;
-        acc[5] = 1.f - giou;
+          for (int k = 0; k < 24; ++k) c[k] = d.corners[row * 24 + k];
+          const BoxGeo pg = box_geo(c), gg = box_geo(r + VDETR_GT_CORNERS);
+          const bool rot = d.rotated != nullptr && d.rotated[0] != 0.f;
+          const float giou = gi < (int)d.nactual[b] ? giou_grad(c, pg, gg, d.w_giou * inv_nb, dc, rot, r + VDETR_GT_CORNERS) : 0.f;
+          acc[5] = 1.f - giou;
+        } else {  // forward-mode tangents of the pair's DIoU / IoU w.r.t. the prediction's 7 parameters
+          const vdetr_iou_ext& e = batch.e[stage];
+          Dual<7> pb[7];
+#pragma unroll
+          for (int i = 0; i < 7; ++i) {
+            pb[i] = cst<Dual<7>>(i < 3 ? e.center[row * 3 + i] : (i < 6 ? e.size[row * 3 + i - 3] : e.angle[row]));
+            pb[i].t[i] = 1.f;
+          }
+          Dual<7> ps, pc;
+          rot_sincos(pb[6], ps, pc);
+          float gbox[7], gs, gc;
+#pragma unroll
+          for (int a = 0; a < 3; ++a) gbox[a] = r[VDETR_GT_CENTER + a], gbox[3 + a] = r[VDETR_GT_SIZE + a];
+          gbox[6] = r[VDETR_GT_ANGLE];
+          sincosf(gbox[6], &gs, &gc);
+          const Dual<7> q = gi < (int)d.nactual[b] ? rot_iou_pair(pb, ps, pc, gbox, gs, gc, KIND == VDETR_IOU_DIOU) : cst<Dual<7>>(0.f);
+          acc[5] = 1.f - q.v;
+          const float sc = -(d.w_giou * inv_nb);  // d (w_giou (1 - q) / num_boxes) / d q
+#pragma unroll
+          for (int i = 0; i < 7; ++i) dbox[i] = sc * q.t[i];
+        }
         alabel = (int)r[VDETR_GT_ANGLE_CLS];
         const float e = d.angle_res_norm[row * d.A + alabel] - r[VDETR_GT_ANGLE_RES] / (3.14159265358979323846f / (float)d.A);
         acc[2] = huber1(e);
@@ -835,8 +901,17 @@ __global__ __launch_bounds__(kLossRows) void set_loss_kernel(LossBatch batch) {
       for (int a = 0; a < d.A; ++a) d.d_angle_res_norm[row * d.A + a] = (active && a == alabel) ? g_areg : 0.f;
 #pragma unroll
       for (int a = 0; a < 3; ++a) d.d_center_reg[row * 3 + a] = d_creg[a], d.d_size_reg[row * 3 + a] = d_sreg[a];
+      if constexpr (KIND == VDETR_IOU_GIOU) {
 #pragma unroll
-      for (int k = 0; k < 24; ++k) d.d_corners[row * 24 + k] = dc[k];
+        for (int k = 0; k < 24; ++k) d.d_corners[row * 24 + k] = dc[k];
+      } else {
+        const vdetr_iou_ext& e = batch.e[stage];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) e.d_center[row * 3 + a] = dbox[a], e.d_size[row * 3 + a] = dbox[3 + a];
+        e.d_angle[row] = dbox[6];
+        if (d.d_corners != nullptr)
+          for (int k = 0; k < 24; ++k) d.d_corners[row * 24 + k] = 0.f;
+      }
     }
   }
   __syncthreads();
@@ -916,18 +991,39 @@ static int check_match_desc(const vdetr_match_desc* d) {
   return VDETR_OK;
 }
 
-extern "C" int vdetr_match_cost_batch_f32(const vdetr_match_desc* descs, int n, vdetr_stream_t stream) {
-  VDETR_REQUIRE(descs != nullptr && n >= 1, "match_cost: null descriptors");
+// the extensions of a batch: every descriptor with box terms carries the same known kind and the pointers it needs
+static int check_iou_exts(const vdetr_iou_ext* exts, int n, const char* op, bool loss, const vdetr_setloss_desc* ldescs,
+                          int* kind_out) {
+  VDETR_REQUIRE(exts != nullptr, "%s: null extensions", op);
+  int kind = -1;
+  for (int k = 0; k < n; ++k) {
+    if (loss && ldescs[k].center_reg == nullptr) continue;  // classification only: no box term
+    const vdetr_iou_ext& e = exts[k];
+    VDETR_REQUIRE(e.iou_kind >= VDETR_IOU_GIOU && e.iou_kind <= VDETR_IOU_IOU, "%s: unknown iou_kind %d", op, e.iou_kind);
+    VDETR_REQUIRE(kind < 0 || e.iou_kind == kind, "%s: mixed iou kinds %d and %d in one batch", op, kind, e.iou_kind);
+    kind = e.iou_kind;
+    if (kind != VDETR_IOU_GIOU) {
+      VDETR_REQUIRE(e.center && e.size && e.angle, "%s: iou_kind %d needs center, size and angle", op, kind);
+      if (loss) VDETR_REQUIRE(e.d_center && e.d_size && e.d_angle, "%s: iou_kind %d needs d_center, d_size and d_angle", op, kind);
+    }
+  }
+  *kind_out = kind < 0 ? VDETR_IOU_GIOU : kind;
+  return VDETR_OK;
+}
+
+template <int KIND>
+static int match_cost_launch(const vdetr_match_desc* descs, const vdetr_iou_ext* exts, int n, vdetr_stream_t stream) {
   for (int s0 = 0; s0 < n; s0 += kCritBatch) {
     const int cnt = n - s0 < kCritBatch ? n - s0 : kCritBatch;
-    MatchBatch batch{};
+    MatchLaunch<KIND> batch{};
     int maxp = 1, maxg = 1, zs = 0;
     for (int k = 0; k < kCritBatch; ++k) {
       if (k >= cnt) {
         batch.d[k].B = 1 << 30;  // terminates the (stage, scene) search
         continue;
       }
-      if (int e = check_match_desc(descs + s0 + k)) return e;
+      if constexpr (KIND != VDETR_IOU_GIOU) batch.e[k] = exts[s0 + k];
+      else if (int e = check_match_desc(descs + s0 + k)) return e;
       batch.d[k] = descs[s0 + k];
       maxp = batch.d[k].P > maxp ? batch.d[k].P : maxp;
       maxg = batch.d[k].G > maxg ? batch.d[k].G : maxg;
@@ -935,10 +1031,32 @@ extern "C" int vdetr_match_cost_batch_f32(const vdetr_match_desc* descs, int n, 
     }
     VDETR_REQUIRE(zs <= 65535, "match_cost: %d (stage, scene) pairs > 65535", zs);
     const dim3 grid(ceil_div(maxp, 256), ceil_div(maxg, kMatchBoxes), zs);
-    hipLaunchKernelGGL(match_cost_kernel, grid, dim3(256), 0, (hipStream_t)stream, batch);
+    hipLaunchKernelGGL(match_cost_kernel<KIND>, grid, dim3(256), 0, (hipStream_t)stream, batch);
     if (int e = check_launch("match_cost")) return e;
   }
   return VDETR_OK;
+}
+
+extern "C" int vdetr_match_cost_batch_f32(const vdetr_match_desc* descs, int n, vdetr_stream_t stream) {
+  VDETR_REQUIRE(descs != nullptr && n >= 1, "match_cost: null descriptors");
+  return match_cost_launch<VDETR_IOU_GIOU>(descs, nullptr, n, stream);
+}
+
+extern "C" int vdetr_match_cost_ext_batch_f32(const vdetr_match_desc* descs, const vdetr_iou_ext* exts, int n,
+                                              vdetr_stream_t stream) {
+  VDETR_REQUIRE(descs != nullptr && n >= 1, "match_cost: null descriptors");
+  int kind;
+  if (int e = check_iou_exts(exts, n, "match_cost", false, nullptr, &kind)) return e;
+  for (int k = 0; k < n; ++k) {  // corners (GIoU only) may be NULL in the rotated modes
+    vdetr_match_desc c = descs[k];
+    if (kind != VDETR_IOU_GIOU && c.corners == nullptr) c.corners = c.cls;
+    if (int e = check_match_desc(&c)) return e;
+  }
+  switch (kind) {
+    case VDETR_IOU_DIOU: return match_cost_launch<VDETR_IOU_DIOU>(descs, exts, n, stream);
+    case VDETR_IOU_IOU: return match_cost_launch<VDETR_IOU_IOU>(descs, exts, n, stream);
+    default: return match_cost_launch<VDETR_IOU_GIOU>(descs, exts, n, stream);
+  }
 }
 
 extern "C" int vdetr_match_cost_f32(const vdetr_match_desc* d, vdetr_stream_t stream) {
@@ -1005,42 +1123,61 @@ extern "C" int vdetr_point_labels_f32(const float* seed_xyz, const float* gt, co
   return check_launch("point_labels");
 }
 
-static int check_loss_desc(const vdetr_setloss_desc* d) {
+static int check_loss_desc(const vdetr_setloss_desc* d, int kind = VDETR_IOU_GIOU) {
   VDETR_REQUIRE(d->B >= 1 && d->P >= 1 && d->C >= 1, "set_loss: bad sizes");
   VDETR_REQUIRE(d->cls_logits && d->d_cls_logits && d->nactual && d->num_boxes && d->losses, "set_loss: null pointer");
   VDETR_REQUIRE((d->inds != nullptr && d->mask != nullptr && d->gt != nullptr) || d->labels != nullptr,
                 "set_loss: need (inds, mask, gt) or labels");
   if (d->center_reg != nullptr) {
-    VDETR_REQUIRE(d->size_reg && d->pre_center && d->pre_size && d->corners && d->angle_logits && d->angle_res_norm && d->gt &&
-                      d->inds && d->mask && d->d_center_reg && d->d_size_reg && d->d_corners && d->d_angle_logits &&
-                      d->d_angle_res_norm && d->A >= 1 && d->G >= 1,
+    const bool giou = kind == VDETR_IOU_GIOU;  // the rotated DIoU / IoU read no corners and may write none
+    VDETR_REQUIRE(d->size_reg && d->pre_center && d->pre_size && (d->corners || !giou) && d->angle_logits && d->angle_res_norm &&
+                      d->gt && d->inds && d->mask && d->d_center_reg && d->d_size_reg && (d->d_corners || !giou) &&
+                      d->d_angle_logits && d->d_angle_res_norm && d->A >= 1 && d->G >= 1,
                   "set_loss: box terms need all box pointers");
   }
   VDETR_REQUIRE(d->card_ws != nullptr, "set_loss: card_ws (B zero-initialised uint64) is required");
   return VDETR_OK;
 }
 
-extern "C" int vdetr_set_loss_batch_f32(const vdetr_setloss_desc* descs, int n, vdetr_stream_t stream) {
-  VDETR_REQUIRE(descs != nullptr && n >= 1, "set_loss: null descriptors");
+template <int KIND>
+static int set_loss_launch(const vdetr_setloss_desc* descs, const vdetr_iou_ext* exts, int n, vdetr_stream_t stream) {
   for (int s0 = 0; s0 < n; s0 += kCritBatch) {
     const int cnt = n - s0 < kCritBatch ? n - s0 : kCritBatch;
-    LossBatch batch{};
+    LossLaunch<KIND> batch{};
     int maxp = 1, ys = 0;
     for (int k = 0; k < kCritBatch; ++k) {
       if (k >= cnt) {
         batch.d[k].B = 1 << 30;
         continue;
       }
-      if (int e = check_loss_desc(descs + s0 + k)) return e;
+      if (int e = check_loss_desc(descs + s0 + k, KIND)) return e;
+      if constexpr (KIND != VDETR_IOU_GIOU) batch.e[k] = exts[s0 + k];
       batch.d[k] = descs[s0 + k];
       maxp = batch.d[k].P > maxp ? batch.d[k].P : maxp;
       ys += batch.d[k].B;
     }
     VDETR_REQUIRE(ys <= 65535, "set_loss: %d (stage, scene) pairs > 65535", ys);
-    hipLaunchKernelGGL(set_loss_kernel, dim3(ceil_div(maxp, kLossRows), ys), dim3(kLossRows), 0, (hipStream_t)stream, batch);
+    hipLaunchKernelGGL(set_loss_kernel<KIND>, dim3(ceil_div(maxp, kLossRows), ys), dim3(kLossRows), 0, (hipStream_t)stream, batch);
     if (int e = check_launch("set_loss")) return e;
   }
   return VDETR_OK;
+}
+
+extern "C" int vdetr_set_loss_batch_f32(const vdetr_setloss_desc* descs, int n, vdetr_stream_t stream) {
+  VDETR_REQUIRE(descs != nullptr && n >= 1, "set_loss: null descriptors");
+  return set_loss_launch<VDETR_IOU_GIOU>(descs, nullptr, n, stream);
+}
+
+extern "C" int vdetr_set_loss_ext_batch_f32(const vdetr_setloss_desc* descs, const vdetr_iou_ext* exts, int n,
+                                            vdetr_stream_t stream) {
+  VDETR_REQUIRE(descs != nullptr && n >= 1, "set_loss: null descriptors");
+  int kind;
+  if (int e = check_iou_exts(exts, n, "set_loss", true, descs, &kind)) return e;
+  switch (kind) {
+    case VDETR_IOU_DIOU: return set_loss_launch<VDETR_IOU_DIOU>(descs, exts, n, stream);
+    case VDETR_IOU_IOU: return set_loss_launch<VDETR_IOU_IOU>(descs, exts, n, stream);
+    default: return set_loss_launch<VDETR_IOU_GIOU>(descs, exts, n, stream);
+  }
 }
 
 extern "C" int vdetr_set_loss_f32(const vdetr_setloss_desc* d, vdetr_stream_t stream) {
