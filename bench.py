@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Benchmark of the V-DETR hot path on MI355X:  python bench.py --gpus N --steps K --warmup W
+"""Benchmark of the V-DETR hot path on MI355X:  python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one TRAINING step of the post-backbone path on one synthetic scene per GPU:
   FPS + gather (40k voxels -> 4096 tokens) -> projection -> decoder (FFN stage, top-1024 proposals, 8 x [self-attn,
@@ -7,7 +7,9 @@ A "step" is one TRAINING step of the post-backbone path on one synthetic scene p
   gradient clipping + AdamW.
 Workload = BASELINE.json configs[1] ("ScanNet 40k-point scene, full V-DETR config, bs=1, 1xMI355X"); N>1 is
 configs[2] (one scene per GPU, weak scaling).  Inputs are resident in HBM before the timed region.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs,
+the line.  --full adds the secondary measurements after the timed steps (secondary_legs): the `roofline` micro-benchmark, the
+`with_backbone`, `criterion` and `arith.exact_f32` steps and the `cpu_baseline`.
 """
 import argparse
 import json
@@ -1007,13 +1009,7 @@ def launch_check(a):
     return 0
 
 
-def main():
-    # a run that is still going after VDETR_BENCH_WATCHDOG seconds (default 900) prints every thread's Python stack to stderr: where a
-    # hung run hangs (round 6 saw two `--config c5` runs out of ~25 sit forever without a line of output)
-    import faulthandler
-    wd = float(os.environ.get("VDETR_BENCH_WATCHDOG", "900"))
-    if wd > 0:
-        faulthandler.dump_traceback_later(wd, repeat=False, file=sys.stderr)
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -1023,6 +1019,8 @@ def main():
                     "(auto: bf16 for c4, as BASELINE names it, f32 otherwise); softmax, RPE table and accumulators are f32 either way")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of captured hipGraphs")
     ap.add_argument("--sync-bn", action="store_true", help="batch statistics over all ranks, as the reference's SyncBatchNorm conversion (main.py:512-514)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the secondary measurements (secondary_legs): "
+                    "roofline micro-benchmark, with_backbone, exact-f32 and criterion steps, CPU baseline; a plain run does only the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--quick-cpu-baseline", action="store_true", help="time 1 and 2 RPE layers on the CPU and scale to the full count, instead of the whole decoder once (~30 s)")
     ap.add_argument("--loss", default="synthetic", choices=["synthetic", "criterion"],
@@ -1044,9 +1042,40 @@ def main():
                     "number, print a JSON line and leave: the launcher path without a GPU (tests/test_dist_gloo.py)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy "
                     "(rank 0; float32 / float64, at most 64 MB: dump_outputs)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    return a
+
+
+def secondary_legs(a, world, dtype):
+    """What rank 0 measures after the timed steps besides the headline, in this order: none in a plain run; with --full every leg
+    the configuration has, less those its --no-* switches turn off.  (The GPU legs first: the CPU baseline leaves 32 OpenMP workers
+    behind that take turns with the launch threads — with_backbone measured 44.7 ms per step after it, 30.3 before.)"""
+    if not a.full:
+        return []
+    legs = []
+    if not a.no_roofline:
+        legs.append("roofline")
+    if world == 1 and a.config == "c2" and not a.no_backbone_leg:
+        legs.append("with_backbone")
+    if world == 1 and dtype == "f32" and a.loss == "synthetic" and not a.no_exact_leg:
+        legs.append("exact_f32_error")  # (writes result["arith"]["exact_f32"]; this key only appears with an error)
+    if world == 1 and a.loss == "synthetic" and not a.no_criterion_leg:
+        legs.append("criterion")  # (times the criterion's CPU oracle as well: after the backbone leg for the same reason)
+    if world == 1 and not a.no_cpu_baseline:
+        legs.append("cpu_baseline")
+    return legs
+
+
+def main():
+    # a run that is still going after VDETR_BENCH_WATCHDOG seconds (default 900) prints every thread's Python stack to stderr: where a
+    # hung run hangs (round 6 saw two `--config c5` runs out of ~25 sit forever without a line of output)
+    import faulthandler
+    wd = float(os.environ.get("VDETR_BENCH_WATCHDOG", "900"))
+    if wd > 0:
+        faulthandler.dump_traceback_later(wd, repeat=False, file=sys.stderr)
+    a = parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # `python bench.py --gpus N` with nobody else having started the ranks: start them here, one process per GPU, as the
@@ -1543,6 +1572,7 @@ def main():
     # The secondary measurements must not cost the headline: if they are still running after VDETR_BENCH_LEG_TIMEOUT seconds (a hung
     # GPU — round 6 met a library GEMM that never returns, DESIGN.md 4.7 — or a CPU oracle on a loaded host), a watchdog thread prints the
     # line as it stands and leaves.  One rank only: with several, the legs below are the roofline micro-benchmark alone.
+    legs = secondary_legs(a, world, dtype) if rank == 0 else []
     import threading
     emitted, emit_lock = [False], threading.Lock()
 
@@ -1563,24 +1593,15 @@ def main():
             emit()
             sys.stdout.flush()
             os._exit(0)
-    if rank == 0 and world == 1 and leg_timeout > 0:
+    if legs and world == 1 and leg_timeout > 0:
         threading.Thread(target=legs_watchdog, daemon=True).start()
 
     if world > 1 and a.with_backbone_dist and a.config == "c2":
         leg("with_backbone", backbone_leg)  # collective: every rank runs it (own scene each); opt-in, it follows the headline
-    if rank == 0:
-        if not a.no_roofline:
-            leg("roofline", roofline_leg)
-        # the GPU legs first: the CPU baseline leaves 32 OpenMP workers behind that take turns with the launch threads
-        # (with_backbone measured 44.7 ms per step after it, 30.3 before)
-        if world == 1 and a.config == "c2" and not a.no_backbone_leg:
-            leg("with_backbone", backbone_leg)
-        if world == 1 and dtype == "f32" and a.loss == "synthetic" and not a.no_exact_leg:
-            leg("exact_f32_error", exact_leg)  # (writes result["arith"]["exact_f32"]; this key only appears with an error)
-        if world == 1 and a.loss == "synthetic" and not a.no_criterion_leg:
-            leg("criterion", criterion_leg)  # (times the criterion's CPU oracle as well: after the backbone leg for the same reason)
-        if not a.no_cpu_baseline and world == 1:
-            leg("cpu_baseline", cpu_leg)
+    run = {"roofline": roofline_leg, "with_backbone": backbone_leg, "exact_f32_error": exact_leg, "criterion": criterion_leg,
+           "cpu_baseline": cpu_leg}
+    for name in legs:
+        leg(name, run[name])
     legs_done.set()
     if rank == 0:
         emit()
