@@ -1014,6 +1014,30 @@ size_t vdetr_heads_workspace_bytes(int B, int N, int G);
 int vdetr_heads_fwd_f32(const vdetr_heads_desc* d, vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The same G heads in inference form (eval mode, no autograd), ONE launch (heads.hip: heads_infer_kernel).  BatchNorm with
+ * running statistics is a per-channel affine, (h - mean) * rsqrt(var + eps) * gamma + beta, so nothing crosses a token tile: a
+ * workgroup per (token tile, head) runs layer 1, affine + ReLU, layer 2, affine + ReLU and layer 3 with the hidden activations in
+ * LDS, and writes only y.  The hidden convolutions have no bias (GenericMLP's hidden_use_bias=False).  No dropout, no running
+ * statistics update, no atomics: two runs give the same bits.
+ * Needs N % tile == 0, G <= 8, rows <= 32, 16-B aligned x / w1t / w2t / w3 / the eight [G*256] vectors.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct vdetr_heads_infer_desc {
+  int32_t B, N;            /* scenes, tokens per scene */
+  int32_t G, rows;         /* heads of the stage, rows of a head's zero-padded output slab */
+  int32_t tile;            /* tokens per workgroup: 16, 32, or 0 = the library's choice */
+  float eps;
+  const float* x;          /* [N, B, 256] the stage's features, sequence-first */
+  const float* w1t;        /* [G][256 in][256 out]: transposed images of the first layers (vdetr_rb_transpose_f32) */
+  const float* w2t;        /* [G][256 in][256 out]: of the second layers */
+  const float* w3;         /* [G][rows][256] */
+  const float* b3;         /* [G][rows] */
+  const float *mean1, *var1, *gamma1, *beta1;  /* [G*256]: running statistics and affine parameters of block 1 */
+  const float *mean2, *var2, *gamma2, *beta2;  /* of block 2 */
+  float* y;                /* [B, G, rows, N] */
+} vdetr_heads_infer_desc;
+int vdetr_heads_infer_f32(const vdetr_heads_infer_desc* d, vdetr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * PositionEmbeddingLearned (models/helpers.py:17-33: Conv1d(cin, 256) -> BatchNorm1d -> ReLU -> Conv1d(256, 256)) on DETACHED
  * box coordinates, training mode, ONE launch (heads.hip).  The first convolution is linear in `cin` (<= 8) coordinates, so the
  * batch statistics of its 256 outputs follow from the coordinates' mean and covariance (accumulated in fp64 by every workgroup
@@ -1042,6 +1066,12 @@ int vdetr_pos_mlp_fwd_f32(const vdetr_posmlp_desc* d, vdetr_stream_t stream);
  * writes (m->out = the pos rows [N, B, 256], hpre, hact, the statistics) and everything vdetr_rb_qkv_f32 writes; d->pos is not read
  * (NULL or m->out).  B * N = d->rows, a multiple of 16. */
 int vdetr_rb_qkv_pos_f32(const vdetr_rb_qkv_desc* d, const vdetr_posmlp_desc* m, vdetr_stream_t stream);
+/* The two position-MLP launches in inference form: the BatchNorm uses the running statistics, (W1 x + b1 - running_mean)
+ * * rsqrt(running_var + eps) * gamma + beta.  They write only m->out (and, for the qkv form, what vdetr_rb_qkv_f32 writes):
+ * hpre, hact, save_mean, save_invstd and counter are not read or written (NULL allowed), running_mean / running_var are read
+ * and required, momentum is ignored. */
+int vdetr_pos_mlp_infer_f32(const vdetr_posmlp_desc* d, vdetr_stream_t stream);
+int vdetr_rb_qkv_pos_infer_f32(const vdetr_rb_qkv_desc* d, const vdetr_posmlp_desc* m, vdetr_stream_t stream);
 
 /* LDS update-rate probe (mode 0 ds_add_f32, 1 ds_add_u32, 2 plain read-add-write, 3 ds_add_f32 on 8 hot bins):
  * 256 workgroups x 512 threads x `iters` updates.  Measurement hook used by tools/kernel_bench.py --lds. */

@@ -168,6 +168,14 @@ class HeadsDesc(ctypes.Structure):
                                 "workspace")]
 
 
+class HeadsInferDesc(ctypes.Structure):
+    """Mirror of ``vdetr_heads_infer_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "N", "G", "rows", "tile")] + [("eps", c_float)] + [
+        (n, c_void_p) for n in ("x", "w1t", "w2t", "w3", "b3", "mean1", "var1", "gamma1", "beta1", "mean2", "var2", "gamma2", "beta2",
+                                "y")]
+
+
 class AttnParts(ctypes.Structure):
     """Mirror of ``vdetr_attn_parts``."""
 
@@ -333,6 +341,8 @@ _SIGNATURES = {
     "vdetr_heads_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vdetr_heads_fwd_f32": (c_int, [ctypes.POINTER(HeadsDesc), c_void_p]),
     "vdetr_pos_mlp_fwd_f32": (c_int, [ctypes.POINTER(PosMlpDesc), c_void_p]),
+    "vdetr_heads_infer_f32": (c_int, [ctypes.POINTER(HeadsInferDesc), c_void_p]),
+    "vdetr_pos_mlp_infer_f32": (c_int, [ctypes.POINTER(PosMlpDesc), c_void_p]),
     "vdetr_bn_act_bwd_f32": (c_int, [ctypes.POINTER(BnActDesc), ctypes.POINTER(BnActGrads), c_void_p]),
     "vdetr_bn_act_bwd_batch_f32": (c_int, [ctypes.POINTER(BnActDesc), ctypes.POINTER(BnActGrads), c_int, c_void_p]),
     "vdetr_colsum_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_long, c_void_p]),
@@ -380,6 +390,7 @@ _SIGNATURES = {
     "vdetr_rb_qkv_f32": (c_int, [ctypes.POINTER(RbQkvDesc), c_void_p]),
     "vdetr_rb_proj_q_f32": (c_int, [ctypes.POINTER(RbProjQDesc), c_void_p]),
     "vdetr_rb_qkv_pos_f32": (c_int, [ctypes.POINTER(RbQkvDesc), ctypes.POINTER(PosMlpDesc), c_void_p]),
+    "vdetr_rb_qkv_pos_infer_f32": (c_int, [ctypes.POINTER(RbQkvDesc), ctypes.POINTER(PosMlpDesc), c_void_p]),
     "vdetr_rb_ffn_f32": (c_int, [ctypes.POINTER(RbFfnDesc), c_void_p]),
     "vdetr_rb_ffn_parts_f32": (c_int, [ctypes.POINTER(RbFfnDesc), ctypes.POINTER(AttnParts), c_void_p, c_void_p, c_void_p]),
     "vdetr_rb_qkv_bwd_f32": (c_int, [ctypes.POINTER(RbQkvDesc), ctypes.POINTER(RbQkvGrads), c_void_p]),

@@ -17,6 +17,8 @@
 //   heads_l2_kernel   h1 = drop(relu(bn1(pre1)));  pre2[b][g*256 + c][n] = sum_k W2[g][c][k] h1[b][g*256 + k][n]
 //   heads_l3_kernel   h2 = drop(relu(bn2(pre2)));  y[b][g][r][n] = sum_k W3[g][r][k] h2[b][g*256 + k][n] + b3[g][r]   grid (B N / 16, G)
 //   pos_mlp_kernel    out = W2 relu(bn(W1 x)) + b2 on [B, N, cin <= 8] coordinates                 grid (B N / 16)
+//   heads_infer_kernel  the same heads in eval mode (running statistics): all three layers in ONE launch, only y written
+//                       (vdetr_heads_infer_f32; pos_mlp_kernel<CIN, true> is the position MLP's eval form)
 //
 // Matrix products: v_mfma_f32_16x16x4_f32 (exact fp32 products, the library GEMMs' numerics class), MFMA rows = tokens,
 // MFMA column j of tile u = channel 64 w + 4 j + u (rowblock.hip's interleave): a lane's four accumulators of a token are four
@@ -396,6 +398,122 @@ __global__ __launch_bounds__(kHdThreads) void heads_l3_kernel(HdArgs A, int merg
   }
 }
 
+// ---- inference form: the stage's heads in ONE launch ------------------------------------------------------------------------------
+// Eval-mode BatchNorm is a per-channel affine of the running statistics, so nothing crosses a token tile: a workgroup per (token
+// tile, head) stages its x tile in LDS, runs layer 1 (hd_w_run), writes relu(bn1(.)) back over the tile, runs layer 2 the same way
+// and layer 3 as heads_l3_kernel does; only y leaves the chip.  No dropout, no statistics, no atomics.
+typedef vdetr_heads_infer_desc HiArgs;
+
+// relu(((acc - mean) * rsqrt(var + eps)) * gamma + beta) (torch's eval order) of a lane's accumulators into the tile: acc[t][u][r] is
+// channel col + u (ch: the same in the stage's [G*256] vectors) of token 16 t + 4 kg + r, so the four u of (t, r) are one float4 of a row
+template <int NT>
+__device__ __forceinline__ void hd_bn_relu_lds(const f32x4 (&acc)[NT][4], const float* __restrict__ mean, const float* __restrict__ var,
+                                               const float* __restrict__ gamma, const float* __restrict__ beta, int ch, float eps,
+                                               float* xs, int col, int lane) {
+  const f32x4 mu = hd_ld4(mean + ch), vr = hd_ld4(var + ch), ga = hd_ld4(gamma + ch), be = hd_ld4(beta + ch);
+  f32x4 inv;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) inv[u] = rsqrtf(vr[u] + eps);
+  const int kg = lane >> 4;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      f32x4 h;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) h[u] = fmaxf((acc[t][u][r] - mu[u]) * inv[u] * ga[u] + be[u], 0.f);
+      hd_st4(xs + (16 * t + 4 * kg + r) * kHdStride + col, h);
+    }
+}
+
+template <int NT>  // 16 NT tokens per workgroup
+__global__ __launch_bounds__(kHdThreads) void heads_infer_kernel(HiArgs A) {
+  constexpr int kTok = 16 * NT;
+  __shared__ __attribute__((aligned(16))) float xs[kTok * kHdStride];
+  __shared__ float red[4 * 2 * 16 * kTok];  // [wave][row tile][row j][token i]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tps = A.N / kTok, tile = blockIdx.x, b = tile / tps, q0 = (tile - b * tps) * kTok;
+  const int g = blockIdx.y, col0 = 64 * w, c = lane & 15, kg = lane >> 4;
+  const int col = col0 + 4 * c, ch = g * kHdC + col;
+  const float* W1 = A.w1t + (size_t)g * kHdC * kHdC;
+  const float* W2 = A.w2t + (size_t)g * kHdC * kHdC;
+  HdRing R;
+  hd_w_begin(W1, col0, lane, R);
+  {  // the tile's feature rows (token q0 + r of scene b = row (q0 + r) B + b of the sequence-first tensor) -> LDS
+    constexpr int kPer = kTok * kHdC / 4 / kHdThreads;
+    f32x4 v[kPer];
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      const int e = tid + u * kHdThreads, r = e >> 6, c4 = e & 63;
+      v[u] = hd_ld4(A.x + ((size_t)(q0 + r) * A.B + b) * kHdC + 4 * c4);
+    }
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      const int e = tid + u * kHdThreads, r = e >> 6, c4 = e & 63;
+      hd_st4(xs + r * kHdStride + 4 * c4, v[u]);
+    }
+  }
+  __syncthreads();
+  f32x4 acc[NT][4];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+  hd_w_run<NT>(xs, W1, col0, lane, R, acc);
+  hd_w_begin(W2, col0, lane, R);  // (layer 2's first weight steps in flight during the epilogue)
+  __syncthreads();                // every wave has read the x tile: it becomes h1
+  hd_bn_relu_lds<NT>(acc, A.mean1, A.var1, A.gamma1, A.beta1, ch, A.eps, xs, col, lane);
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+  hd_w_run<NT>(xs, W2, col0, lane, R, acc);
+  // layer 3's share of this wave: contraction indices 64 w .. 64 w + 63; B operand = rows of W3 as stored (heads_l3_kernel)
+  const int njt = A.rows > 16 ? 2 : 1;
+  f32x4 wb[2][4];
+#pragma unroll
+  for (int jt = 0; jt < 2; ++jt) {
+    const int row = 16 * jt + c;
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+      wb[jt][m] = row < A.rows ? hd_ld4(A.w3 + ((size_t)g * A.rows + row) * kHdC + 64 * w + 16 * m + 4 * kg) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  __syncthreads();  // every wave has read h1: the tile becomes h2
+  hd_bn_relu_lds<NT>(acc, A.mean2, A.var2, A.gamma2, A.beta2, ch, A.eps, xs, col, lane);
+  __syncthreads();
+  f32x4 acc3[NT][2];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc3[t][0] = acc3[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const f32x4 a = hd_ld4(xs + (16 * t + c) * kHdStride + 64 * w + 16 * m + 4 * kg);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc3[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], wb[0][m][e], acc3[t][0], 0, 0, 0);
+        if (njt > 1) acc3[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], wb[1][m][e], acc3[t][1], 0, 0, 0);
+      }
+    }
+  // acc3[t][jt][r] = this wave's part of y[token 16 t + 4 kg + r][row 16 jt + c]
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[((w * 2 + jt) * 16 + c) * kTok + 16 * t + 4 * kg + r] = acc3[t][jt][r];
+  __syncthreads();
+  constexpr int kWave = 2 * 16 * kTok;
+  for (int o = tid; o < njt * 16 * kTok; o += kHdThreads) {
+    const int jt = o / (16 * kTok), j = (o / kTok) & 15, i = o % kTok, row = 16 * jt + j;
+    if (row >= A.rows) continue;
+    const float s = (red[o] + red[kWave + o]) + (red[2 * kWave + o] + red[3 * kWave + o]);
+    A.y[(((size_t)b * A.G + g) * A.rows + row) * A.N + q0 + i] = s + A.b3[g * A.rows + row];
+  }
+}
+
 // ---- the learned position embedding of a box (PositionEmbeddingLearned) -----------------------------------------------------------
 // Phases of a workgroup (16 tokens): (1) the coordinates' first and second moments over ALL B*N tokens, every workgroup for
 // itself — sums of the offsets from token 0 (the same reference everywhere: what is left to cancel in E[dd] - E[d]E[d] is the
@@ -406,7 +524,9 @@ __global__ __launch_bounds__(kHdThreads) void heads_l3_kernel(HdArgs A, int merg
 typedef vdetr_posmlp_desc PmArgs;
 constexpr int kPmMaxIn = 8;
 
-template <int CIN>
+// INFER: the inference form (vdetr_pos_mlp_infer_f32) — the BatchNorm of the running statistics, phases 1 and the bookkeeping of
+// phase 2 drop out, and only `out` is written.
+template <int CIN, bool INFER>
 __global__ __launch_bounds__(kHdThreads) void pos_mlp_kernel(PmArgs A) {
   constexpr int kMom = CIN + CIN * (CIN + 1) / 2;  // sums + upper triangle of the second moments
   __shared__ __attribute__((aligned(16))) float xs[kHdTok3 * kHdStride];
@@ -431,6 +551,7 @@ __global__ __launch_bounds__(kHdThreads) void pos_mlp_kernel(PmArgs A) {
 #pragma unroll
     for (int i = 0; i < CIN; ++i) xt[t][i] = A.x[((size_t)b * A.N + q0 + t) * CIN + i];  // (wave-uniform addresses: scalar loads)
   // ---- phase 1 ----
+  if constexpr (!INFER) {
   double s[kMom];
 #pragma unroll
   for (int i = 0; i < kMom; ++i) s[i] = 0.0;
@@ -462,8 +583,18 @@ __global__ __launch_bounds__(kHdThreads) void pos_mlp_kernel(PmArgs A) {
     if (lane == 0) mom[i] = r;
   }
   __syncthreads();
+  }
   // ---- phase 2 ----
-  {
+  if constexpr (INFER) {  // relu(((W1 x + b1 - running_mean) * rsqrt(running_var + eps)) * gamma + beta) (torch's eval order)
+    const float rm = A.running_mean[ch], invstd = rsqrtf(A.running_var[ch] + A.eps);
+#pragma unroll
+    for (int i = 0; i < kHdTok3; ++i) {
+      float h = 0.f;
+#pragma unroll
+      for (int k = 0; k < CIN; ++k) h = fmaf(xt[i][k], wv[k], h);
+      xs[i * kHdStride + ch] = fmaxf(((h + bias1) - rm) * invstd * gam + bet, 0.f);
+    }
+  } else {
     const double inv = 1.0 / (double)T;
     double mu[CIN];  // mean offset from the reference token
 #pragma unroll
@@ -561,6 +692,23 @@ extern "C" int vdetr_heads_fwd_f32(const vdetr_heads_desc* d, vdetr_stream_t str
   return check_launch("heads_fwd");
 }
 
+template <bool INFER>
+static int pos_mlp_launch(const vdetr_posmlp_desc* d, vdetr_stream_t stream, const char* op) {
+  const dim3 grid(d->B * d->N / kHdTok3), block(kHdThreads);
+  hipStream_t st = (hipStream_t)stream;
+  switch (d->cin) {
+    case 1: hipLaunchKernelGGL((pos_mlp_kernel<1, INFER>), grid, block, 0, st, *d); break;
+    case 2: hipLaunchKernelGGL((pos_mlp_kernel<2, INFER>), grid, block, 0, st, *d); break;
+    case 3: hipLaunchKernelGGL((pos_mlp_kernel<3, INFER>), grid, block, 0, st, *d); break;  // (key positions: pos_for_key)
+    case 4: hipLaunchKernelGGL((pos_mlp_kernel<4, INFER>), grid, block, 0, st, *d); break;
+    case 5: hipLaunchKernelGGL((pos_mlp_kernel<5, INFER>), grid, block, 0, st, *d); break;
+    case 6: hipLaunchKernelGGL((pos_mlp_kernel<6, INFER>), grid, block, 0, st, *d); break;  // (box centre + size: the decoder's query position)
+    case 7: hipLaunchKernelGGL((pos_mlp_kernel<7, INFER>), grid, block, 0, st, *d); break;
+    default: hipLaunchKernelGGL((pos_mlp_kernel<8, INFER>), grid, block, 0, st, *d); break;
+  }
+  return check_launch(op);
+}
+
 extern "C" int vdetr_pos_mlp_fwd_f32(const vdetr_posmlp_desc* d, vdetr_stream_t stream) {
   VDETR_REQUIRE(d != nullptr, "pos_mlp_fwd: null descriptor");
   VDETR_REQUIRE(d->B > 0 && d->N > 0 && d->N % kHdTok3 == 0, "pos_mlp_fwd: B=%d, N=%d: N must be a positive multiple of %d", d->B, d->N, kHdTok3);
@@ -568,17 +716,37 @@ extern "C" int vdetr_pos_mlp_fwd_f32(const vdetr_posmlp_desc* d, vdetr_stream_t 
   VDETR_REQUIRE(d->x && d->w1 && d->gamma && d->beta && d->w2t && d->hpre && d->hact && d->save_mean && d->save_invstd && d->out, "pos_mlp_fwd: null pointer");
   VDETR_REQUIRE((d->running_mean != nullptr) == (d->running_var != nullptr), "pos_mlp_fwd: running_mean and running_var go together");
   VDETR_REQUIRE(HD_ALIGNED(d->w2t) && HD_ALIGNED(d->b2) && HD_ALIGNED(d->hpre) && HD_ALIGNED(d->hact) && HD_ALIGNED(d->out), "pos_mlp_fwd: operands must be 16-B aligned");
-  const dim3 grid(d->B * d->N / kHdTok3), block(kHdThreads);
+  return pos_mlp_launch<false>(d, stream, "pos_mlp_fwd");
+}
+
+extern "C" int vdetr_pos_mlp_infer_f32(const vdetr_posmlp_desc* d, vdetr_stream_t stream) {
+  VDETR_REQUIRE(d != nullptr, "pos_mlp_infer: null descriptor");
+  VDETR_REQUIRE(d->B > 0 && d->N > 0 && d->N % kHdTok3 == 0, "pos_mlp_infer: B=%d, N=%d: N must be a positive multiple of %d", d->B, d->N, kHdTok3);
+  VDETR_REQUIRE(d->cin >= 1 && d->cin <= kPmMaxIn, "pos_mlp_infer: cin=%d outside [1, %d]", d->cin, kPmMaxIn);
+  VDETR_REQUIRE(d->x && d->w1 && d->gamma && d->beta && d->running_mean && d->running_var && d->w2t && d->out, "pos_mlp_infer: null pointer");
+  VDETR_REQUIRE(HD_ALIGNED(d->w2t) && HD_ALIGNED(d->b2) && HD_ALIGNED(d->out), "pos_mlp_infer: operands must be 16-B aligned");
+  return pos_mlp_launch<true>(d, stream, "pos_mlp_infer");
+}
+
+extern "C" int vdetr_heads_infer_f32(const vdetr_heads_infer_desc* d, vdetr_stream_t stream) {
+  VDETR_REQUIRE(d != nullptr, "heads_infer: null descriptor");
+  VDETR_REQUIRE(d->tile == 0 || d->tile == 16 || d->tile == 32, "heads_infer: tile=%d is not 0, 16 or 32", d->tile);
+  VDETR_REQUIRE(d->G >= 1 && d->G <= 8 && d->rows >= 1 && d->rows <= 32, "heads_infer: G=%d outside [1, 8] or rows=%d outside [1, 32]", d->G, d->rows);
+  // the library's choice, measured on MI355X with G = 5 (us per launch, 16- / 32-token tiles): 1024 tokens 25.6 / 24.9, 4096 tokens
+  // 60 / 66, 16384 tokens 231 / 222.  At 4096 the 32-token grid (640 workgroups of 3 per CU) leaves the last round half empty.
+  const long toks = (long)d->B * d->N;
+  const int tile = d->tile ? d->tile : ((toks <= 1024 || toks >= 16384) && d->N % 32 == 0 ? 32 : 16);
+  VDETR_REQUIRE(d->B > 0 && d->N > 0 && d->N % tile == 0, "heads_infer: B=%d, N=%d: N must be a positive multiple of %d", d->B, d->N, tile);
+  VDETR_REQUIRE((long)d->B * d->N / 16 <= 2147483647L, "heads_infer: too many tokens");
+  VDETR_REQUIRE(d->x && d->w1t && d->w2t && d->w3 && d->b3 && d->y, "heads_infer: null operand");
+  VDETR_REQUIRE(d->mean1 && d->var1 && d->gamma1 && d->beta1 && d->mean2 && d->var2 && d->gamma2 && d->beta2, "heads_infer: null BatchNorm vector");
+  VDETR_REQUIRE(HD_ALIGNED(d->x) && HD_ALIGNED(d->w1t) && HD_ALIGNED(d->w2t) && HD_ALIGNED(d->w3) && HD_ALIGNED(d->mean1) && HD_ALIGNED(d->var1) &&
+                    HD_ALIGNED(d->gamma1) && HD_ALIGNED(d->beta1) && HD_ALIGNED(d->mean2) && HD_ALIGNED(d->var2) && HD_ALIGNED(d->gamma2) &&
+                    HD_ALIGNED(d->beta2), "heads_infer: operands must be 16-B aligned");
   hipStream_t st = (hipStream_t)stream;
-  switch (d->cin) {
-    case 1: hipLaunchKernelGGL(pos_mlp_kernel<1>, grid, block, 0, st, *d); break;
-    case 2: hipLaunchKernelGGL(pos_mlp_kernel<2>, grid, block, 0, st, *d); break;
-    case 3: hipLaunchKernelGGL(pos_mlp_kernel<3>, grid, block, 0, st, *d); break;  // (key positions: pos_for_key)
-    case 4: hipLaunchKernelGGL(pos_mlp_kernel<4>, grid, block, 0, st, *d); break;
-    case 5: hipLaunchKernelGGL(pos_mlp_kernel<5>, grid, block, 0, st, *d); break;
-    case 6: hipLaunchKernelGGL(pos_mlp_kernel<6>, grid, block, 0, st, *d); break;  // (box centre + size: the decoder's query position)
-    case 7: hipLaunchKernelGGL(pos_mlp_kernel<7>, grid, block, 0, st, *d); break;
-    default: hipLaunchKernelGGL(pos_mlp_kernel<8>, grid, block, 0, st, *d); break;
-  }
-  return check_launch("pos_mlp_fwd");
+  if (tile == 32)
+    hipLaunchKernelGGL(heads_infer_kernel<2>, dim3(d->B * d->N / 32, d->G), dim3(kHdThreads), 0, st, *d);
+  else
+    hipLaunchKernelGGL(heads_infer_kernel<1>, dim3(d->B * d->N / 16, d->G), dim3(kHdThreads), 0, st, *d);
+  return check_launch("heads_infer");
 }

@@ -12,7 +12,9 @@ namespace vdetr {
 // rb_qkv: the q and k workgroups (blockIdx.y = 0, 1) now form their own 16 rows of it — same arithmetic, same order as pos_mlp_kernel —,
 // add them to the rows of norm1(tgt) in LDS and go on as before; the q workgroups write everything the position MLP's launch wrote
 // (pos, the hidden pre-/activations, the saved statistics; workgroup (0, 0) the running statistics).  The v workgroups are rb_qkv's.
-template <int CIN>
+// INFER (vdetr_rb_qkv_pos_infer_f32): the position MLP's BatchNorm uses the running statistics (heads.hip: pos_mlp_kernel<., true>);
+// no moments, no bookkeeping, and of the position MLP's tensors only `out` is written.
+template <int CIN, bool INFER>
 __global__ __launch_bounds__(kRbThreads) void rb_qkv_pos_kernel(RbQkvArgs A, vdetr_posmlp_desc M) {
   constexpr int kMom = CIN + CIN * (CIN + 1) / 2;  // sums + upper triangle of the second moments
   __shared__ __attribute__((aligned(16))) float xs[kRbRows * kRbStride];
@@ -52,6 +54,7 @@ __global__ __launch_bounds__(kRbThreads) void rb_qkv_pos_kernel(RbQkvArgs A, vde
       for (int i = 0; i < CIN; ++i) xt[t][i] = M.x[((size_t)b * M.N + q) * CIN + i];
     }
     // ---- the coordinates' first and second moments over all B N tokens (heads.hip: pos_mlp_kernel, phase 1) ----
+    if constexpr (!INFER) {
     double sm[kMom];
 #pragma unroll
     for (int i = 0; i < kMom; ++i) sm[i] = 0.0;
@@ -83,8 +86,18 @@ __global__ __launch_bounds__(kRbThreads) void rb_qkv_pos_kernel(RbQkvArgs A, vde
       if (lane == 0) mom[i] = r;
     }
     __syncthreads();
+    }
     // ---- BatchNorm of this thread's channel, relu(bn(W1 x)) of the 16 tokens into the tile (phase 2) ----
-    {
+    if constexpr (INFER) {  // relu(((W1 x + b1 - running_mean) * rsqrt(running_var + eps)) * gamma + beta) (torch's eval order)
+      const float rm = M.running_mean[ch], invstd = rsqrtf(M.running_var[ch] + M.eps);
+#pragma unroll
+      for (int i = 0; i < kRbRows; ++i) {
+        float h = 0.f;
+#pragma unroll
+        for (int k = 0; k < CIN; ++k) h = fmaf(xt[i][k], wv[k], h);
+        xs[i * kRbStride + ch] = fmaxf(((h + bias1) - rm) * invstd * gam + bet, 0.f);
+      }
+    } else {
       const double inv = 1.0 / (double)T;
       double mu[CIN];
 #pragma unroll
@@ -188,6 +201,23 @@ static int rb_common(int rows, int B, const char* op) {
   return VDETR_OK;
 }
 
+template <bool INFER>
+static int rb_qkv_pos_launch(const vdetr_rb_qkv_desc* d, const vdetr_posmlp_desc* m, vdetr_stream_t stream, const char* op) {
+  const dim3 grid(d->rows / kRbRows, 3), block(kRbThreads);
+  hipStream_t st = (hipStream_t)stream;
+  switch (m->cin) {
+    case 1: hipLaunchKernelGGL((rb_qkv_pos_kernel<1, INFER>), grid, block, 0, st, *d, *m); break;
+    case 2: hipLaunchKernelGGL((rb_qkv_pos_kernel<2, INFER>), grid, block, 0, st, *d, *m); break;
+    case 3: hipLaunchKernelGGL((rb_qkv_pos_kernel<3, INFER>), grid, block, 0, st, *d, *m); break;
+    case 4: hipLaunchKernelGGL((rb_qkv_pos_kernel<4, INFER>), grid, block, 0, st, *d, *m); break;
+    case 5: hipLaunchKernelGGL((rb_qkv_pos_kernel<5, INFER>), grid, block, 0, st, *d, *m); break;
+    case 6: hipLaunchKernelGGL((rb_qkv_pos_kernel<6, INFER>), grid, block, 0, st, *d, *m); break;  // (box centre + size: the decoder's query position)
+    case 7: hipLaunchKernelGGL((rb_qkv_pos_kernel<7, INFER>), grid, block, 0, st, *d, *m); break;
+    default: hipLaunchKernelGGL((rb_qkv_pos_kernel<8, INFER>), grid, block, 0, st, *d, *m); break;
+  }
+  return check_launch(op);
+}
+
 extern "C" int vdetr_rb_qkv_pos_f32(const vdetr_rb_qkv_desc* d, const vdetr_posmlp_desc* m, vdetr_stream_t stream) {
   VDETR_REQUIRE(d != nullptr && m != nullptr, "rb_qkv_pos: null descriptor");
   if (int e = rb_common(d->rows, d->B, "rb_qkv_pos")) return e;
@@ -202,18 +232,21 @@ extern "C" int vdetr_rb_qkv_pos_f32(const vdetr_rb_qkv_desc* d, const vdetr_posm
   VDETR_REQUIRE(d->pos == nullptr || d->pos == m->out, "rb_qkv_pos: pos is computed by the launch (pass NULL or the position MLP's `out`)");
   VDETR_REQUIRE(RB_ALIGNED(d->t) && RB_ALIGNED(d->wt) && RB_ALIGNED(d->b) && RB_ALIGNED(d->x) && RB_ALIGNED(d->out) && RB_ALIGNED(m->w2t) &&
                 RB_ALIGNED(m->b2) && RB_ALIGNED(m->hpre) && RB_ALIGNED(m->hact) && RB_ALIGNED(m->out), "rb_qkv_pos: operands must be 16-B aligned");
-  const dim3 grid(d->rows / kRbRows, 3), block(kRbThreads);
-  hipStream_t st = (hipStream_t)stream;
-  switch (m->cin) {
-    case 1: hipLaunchKernelGGL(rb_qkv_pos_kernel<1>, grid, block, 0, st, *d, *m); break;
-    case 2: hipLaunchKernelGGL(rb_qkv_pos_kernel<2>, grid, block, 0, st, *d, *m); break;
-    case 3: hipLaunchKernelGGL(rb_qkv_pos_kernel<3>, grid, block, 0, st, *d, *m); break;
-    case 4: hipLaunchKernelGGL(rb_qkv_pos_kernel<4>, grid, block, 0, st, *d, *m); break;
-    case 5: hipLaunchKernelGGL(rb_qkv_pos_kernel<5>, grid, block, 0, st, *d, *m); break;
-    case 6: hipLaunchKernelGGL(rb_qkv_pos_kernel<6>, grid, block, 0, st, *d, *m); break;  // (box centre + size: the decoder's query position)
-    case 7: hipLaunchKernelGGL(rb_qkv_pos_kernel<7>, grid, block, 0, st, *d, *m); break;
-    default: hipLaunchKernelGGL(rb_qkv_pos_kernel<8>, grid, block, 0, st, *d, *m); break;
-  }
-  return check_launch("rb_qkv_pos");
+  return rb_qkv_pos_launch<false>(d, m, stream, "rb_qkv_pos");
+}
+
+extern "C" int vdetr_rb_qkv_pos_infer_f32(const vdetr_rb_qkv_desc* d, const vdetr_posmlp_desc* m, vdetr_stream_t stream) {
+  VDETR_REQUIRE(d != nullptr && m != nullptr, "rb_qkv_pos_infer: null descriptor");
+  if (int e = rb_common(d->rows, d->B, "rb_qkv_pos_infer")) return e;
+  VDETR_REQUIRE(d->t && d->wt && d->out && d->x, "rb_qkv_pos_infer: null pointer (wt: the W^T images, vdetr_rb_transpose_f32; x: t + pos, written)");
+  VDETR_REQUIRE(m->B == d->B && m->N > 0 && (long)m->B * m->N == d->rows && d->rows % kRbRows == 0,
+                "rb_qkv_pos_infer: %d x %d tokens for %d rows (a multiple of %d)", m->B, m->N, d->rows, kRbRows);
+  VDETR_REQUIRE(m->cin >= 1 && m->cin <= 8, "rb_qkv_pos_infer: cin=%d outside [1, 8]", m->cin);
+  VDETR_REQUIRE(m->x && m->w1 && m->gamma && m->beta && m->running_mean && m->running_var && m->w2t && m->out,
+                "rb_qkv_pos_infer: null operand of the position MLP");
+  VDETR_REQUIRE(d->pos == nullptr || d->pos == m->out, "rb_qkv_pos_infer: pos is computed by the launch (pass NULL or the position MLP's `out`)");
+  VDETR_REQUIRE(RB_ALIGNED(d->t) && RB_ALIGNED(d->wt) && RB_ALIGNED(d->b) && RB_ALIGNED(d->x) && RB_ALIGNED(d->out) && RB_ALIGNED(m->w2t) &&
+                RB_ALIGNED(m->b2) && RB_ALIGNED(m->out), "rb_qkv_pos_infer: operands must be 16-B aligned");
+  return rb_qkv_pos_launch<true>(d, m, stream, "rb_qkv_pos_infer");
 }
 

@@ -5,7 +5,11 @@ models/helpers.py:74-141) and PositionEmbeddingLearned (helpers.py:17-33).  Host
 ``vdetr_pos_mlp_fwd_f32``: training mode on the GPU only; the launches write every tensor the existing batched backward reads
 (vdetr_transformer._DeferredHeads, helpers.DeferredPosEmbedGrads), with the dropout streams of bn_act.py for the same salts, so a
 stage computes the same values on either path.  ``VDETR_HEADS_FUSED=0`` keeps the one-launch-per-op path (A/B runs, parity tests).
-No CPU path.
+
+Inference (``inference(module)``: eval mode with autograd off, torch.inference_mode included) has forms of its own: a stage's heads
+as ONE launch (``heads_infer``: vdetr_heads_infer_f32) and the position MLP with its running statistics (``pos_mlp_infer``:
+vdetr_pos_mlp_infer_f32, or vdetr_rb_qkv_pos_infer_f32 through rowblock.qkv).  ``INFER = False`` keeps the eval forward on the
+paths it took before they existed (A/B runs, parity tests).  No CPU path.
 """
 import ctypes
 import os
@@ -15,10 +19,18 @@ import torch
 from . import _lib as L
 from . import attention as A
 from . import bn_act as BNA
+from .helpers import buffers_alias
 
 C = 256
 FUSED = os.environ.get("VDETR_HEADS_FUSED", "1") != "0"
 FUSED_POS = os.environ.get("VDETR_POS_FUSED", "1") != "0"
+INFER = True     # the inference forms under eval mode + no autograd (tests and tools/infer_bench.py set False: the A/B reference)
+INFER_TILE = 0   # tokens per workgroup of vdetr_heads_infer_f32: 16, 32 or 0 = the library's choice
+
+
+def inference(module):
+    """eval mode with autograd off (torch.no_grad() or torch.inference_mode()) and the inference forms on"""
+    return INFER and not module.training and not torch.is_grad_enabled()
 
 # ---- W^T images of the [256, 256] weights the forward launches read (the same transposer as rowblock.py: one launch) ---------
 _tables = {}    # (source pointers) -> (device table of source pointers, [n, 256, 256] images)
@@ -165,6 +177,73 @@ def heads_forward(feats_seq, L5, params, stats, salts, rows, h1_out, h2_out):
     return y, rec1, rec2
 
 
+def heads_infer_usable(feats_seq, L5, rows):
+    """heads_usable for the inference form: the running statistics instead of the batch's, no dropout, no momentum"""
+    if not (feats_seq.is_cuda and feats_seq.dtype == torch.float32 and feats_seq.dim() == 3 and feats_seq.is_contiguous()
+            and feats_seq.shape[2] == C and feats_seq.shape[0] % 16 == 0 and feats_seq.data_ptr() % 16 == 0):
+        return False
+    if len(L5) > 8 or rows > 32:
+        return False
+    eps = L5[0][1].eps
+    for l in L5:
+        if not (_ok_weight(l[0].weight) and _ok_weight(l[4].weight) and l[0].bias is None and l[4].bias is None
+                and l[8].bias is not None):
+            return False
+        for bn in (l[1], l[5]):
+            if not (type(bn) is torch.nn.BatchNorm1d and bn.affine and bn.running_mean is not None and bn.eps == eps
+                    and bn.num_features == C):
+                return False
+    return True
+
+
+def _vec(mods, name):
+    """getattr(m, name) of the modules as ONE [G*256] contiguous, 16-B aligned vector: an alias where they are adjacent, else a copy.
+    Running statistics that are not adjacent yet are laid out so, once (what the training path's first call does,
+    vdetr_transformer._bn_group) — not inside a capture, and not under torch.inference_mode (the buffers would become inference
+    tensors that a later training step could not update)."""
+    ts = [getattr(m, name) for m in mods]
+    v = buffers_alias(ts)
+    if v is None and name.startswith("running_") and not torch.cuda.is_current_stream_capturing() and not torch.is_inference_mode_enabled():
+        with torch.no_grad():
+            flat = torch.cat(ts)
+            n = ts[0].shape[0]
+            for i, m in enumerate(mods):
+                setattr(m, name, flat[i * n:(i + 1) * n])
+        v = buffers_alias([getattr(m, name) for m in mods])
+    if v is None or v.data_ptr() % 16:
+        v = torch.cat([t.detach() for t in ts])
+    return v
+
+
+def heads_infer(feats_seq, L5, rows):
+    """The stage's G heads on feats_seq [N, B, 256] in one launch: y [B, G, rows, N], the joint slab the box decode reads."""
+    from .helpers import slot_stack_params
+    N, B, _ = feats_seq.shape
+    G = len(L5)
+    dev = feats_seq.device
+    w_imgs = _images([l[0].weight for l in L5] + [l[4].weight for l in L5], _fresh["on"])
+    w3 = slot_stack_params([l[8].weight for l in L5], rows)
+    b3 = slot_stack_params([l[8].bias for l in L5], rows)
+    if w3 is None or b3 is None or w3.data_ptr() % 16:  # (parameters not laid out as slabs by dist.FlatParams: zero-padded copies)
+        w3 = torch.zeros((G, rows, C), dtype=torch.float32, device=dev)
+        b3 = torch.zeros((G, rows), dtype=torch.float32, device=dev)
+        for g, l in enumerate(L5):
+            r = l[8].weight.shape[0]
+            w3[g, :r].copy_(l[8].weight.detach().reshape(r, C))
+            b3[g, :r].copy_(l[8].bias.detach())
+    vecs = [_vec([l[i] for l in L5], k) for i in (1, 5) for k in ("running_mean", "running_var", "weight", "bias")]
+    y = torch.empty((B, G, rows, N), dtype=torch.float32, device=dev)
+    d = L.HeadsInferDesc()
+    d.B, d.N, d.G, d.rows, d.tile, d.eps = B, N, G, rows, int(INFER_TILE), float(L5[0][1].eps)
+    d.x = feats_seq.data_ptr()
+    d.w1t, d.w2t = w_imgs.data_ptr(), w_imgs.data_ptr() + G * C * C * 4
+    d.w3, d.b3 = w3.data_ptr(), b3.data_ptr()
+    d.mean1, d.var1, d.gamma1, d.beta1, d.mean2, d.var2, d.gamma2, d.beta2 = (v.data_ptr() for v in vecs)
+    d.y = y.data_ptr()
+    L.check(L.lib().vdetr_heads_infer_f32(ctypes.byref(d), L.stream_ptr()), "heads_infer")
+    return y
+
+
 def pos_mlp_usable(module, x_tok):
     """module: helpers.PositionEmbeddingLearned; x_tok [B, N, cin] coordinates"""
     head = module.position_embedding_head
@@ -176,7 +255,7 @@ def pos_mlp_usable(module, x_tok):
 
 
 # Position MLPs whose launch is left to the consumer of their output (vdetr_rb_qkv_pos_f32: the decoder layer's q / k / v projection
-# computes the position rows on its way in): data_ptr of `out` -> (descriptor, tensors it points at).  The decoder turns this on for
+# computes the position rows on its way in): data_ptr of `out` -> (descriptor, tensors it points at, inference form?).  The decoder turns this on for
 # the layers it runs through rowblock.py; a layer that takes another path calls materialize_pos() first.  `out`, the hidden
 # activations and the statistics are NOT valid until one of the two has run.
 _pending_pos = {}
@@ -190,6 +269,42 @@ def lazy_pos(on):
     return prev
 
 
+def pos_mlp_infer_usable(module, x_tok):
+    """pos_mlp_usable for the inference form (vdetr_pos_mlp_infer_f32 / vdetr_rb_qkv_pos_infer_f32)"""
+    head = module.position_embedding_head
+    bn = head[1]
+    return bool(x_tok.is_cuda and x_tok.dtype == torch.float32 and x_tok.dim() == 3 and x_tok.shape[2] <= 8
+                and x_tok.shape[1] % 16 == 0 and head[0].weight.shape[0] == C and _ok_weight(head[3].weight)
+                and type(bn) is torch.nn.BatchNorm1d and bn.affine and bn.running_mean is not None)
+
+
+def pos_mlp_infer(module, x_tok):
+    """The position MLP in inference form: out [N, B, 256] (dense, sequence-first) — launched now, or, with lazy_pos(True), left to
+    rowblock.qkv (or materialize_pos) like pos_mlp_forward's."""
+    conv1, bn, _, conv2 = module.position_embedding_head
+    x_tok = x_tok.detach().contiguous()
+    B, N, cin = x_tok.shape
+    dev = x_tok.device
+    w2t = _images([conv2.weight], _fresh["on"])
+    out = torch.empty((N, B, C), dtype=torch.float32, device=dev)
+    w1 = conv1.weight.detach().reshape(C, cin).contiguous()
+    d = L.PosMlpDesc()
+    d.B, d.N, d.cin = B, N, cin
+    d.x, d.w1 = x_tok.data_ptr(), w1.data_ptr()
+    d.b1 = conv1.bias.data_ptr() if conv1.bias is not None else None
+    d.gamma, d.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
+    d.running_mean, d.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+    d.eps = float(bn.eps)
+    d.w2t = w2t.data_ptr()
+    d.b2 = conv2.bias.data_ptr() if conv2.bias is not None else None
+    d.out = out.data_ptr()
+    if _lazy_pos["on"] and B * N % 16 == 0:
+        _pending_pos[out.data_ptr()] = (d, (x_tok, w1, w2t, out), True)
+    else:
+        L.check(L.lib().vdetr_pos_mlp_infer_f32(ctypes.byref(d), L.stream_ptr()), "pos_mlp_infer")
+    return out
+
+
 def take_pending_pos(pos):
     """the descriptor of a position MLP that was left to the consumer of `pos` (None: `pos` is final)"""
     return _pending_pos.pop(pos.data_ptr(), None) if (_pending_pos and pos is not None) else None
@@ -198,7 +313,9 @@ def take_pending_pos(pos):
 def materialize_pos(pos):
     """launch the position MLP behind `pos` now, if it was left to a consumer that will not run"""
     rec = take_pending_pos(pos)
-    if rec is not None:
+    if rec is not None and rec[2]:
+        L.check(L.lib().vdetr_pos_mlp_infer_f32(ctypes.byref(rec[0]), L.stream_ptr()), "pos_mlp_infer")
+    elif rec is not None:
         L.check(L.lib().vdetr_pos_mlp_fwd_f32(ctypes.byref(rec[0]), L.stream_ptr()), "pos_mlp_fwd")
 
 
@@ -234,7 +351,7 @@ def pos_mlp_forward(module, x_tok):
     d.b2 = conv2.bias.data_ptr() if conv2.bias is not None else None
     d.hpre, d.hact, d.save_mean, d.save_invstd, d.out = hpre.data_ptr(), hact.data_ptr(), sm[0].data_ptr(), sm[1].data_ptr(), out.data_ptr()
     if _lazy_pos["on"] and B * N % 16 == 0 and (B == 1 or N % 4 == 0):
-        _pending_pos[out.data_ptr()] = (d, (x_tok, w1, g, b, w2t, hpre, hact, sm, out))
+        _pending_pos[out.data_ptr()] = (d, (x_tok, w1, g, b, w2t, hpre, hact, sm, out), False)
     else:
         L.check(L.lib().vdetr_pos_mlp_fwd_f32(ctypes.byref(d), L.stream_ptr()), "pos_mlp_fwd")
     rec = (hpre, g, b, sm[0], sm[1], None, (float(bn.eps), float(bn.momentum), 0.0, 0), None)

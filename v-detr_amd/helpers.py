@@ -553,6 +553,10 @@ class PositionEmbeddingLearned(nn.Module):
         head = self.position_embedding_head
         x = xyz.transpose(1, 2)  # [B, C_in, N]; the 1x1 convolution reads the transposed operand in place
         bn = head[1]
+        from . import heads as HD
+        if HD.inference(self) and HD.pos_mlp_infer_usable(self, xyz):
+            # inference: the block as ONE launch with the running statistics (or none yet: left to rowblock.qkv, heads.lazy_pos)
+            return HD.pos_mlp_infer(self, xyz).permute(1, 2, 0)
         if not (self.training and x.is_cuda and type(bn) is nn.BatchNorm1d and bn.momentum is not None and bn.track_running_stats):
             from . import bn_act as BNA  # (cross-replica statistics on this path too while bn_act.set_sync is on)
             return BNA.run_sequential(head, x.contiguous())
@@ -614,8 +618,33 @@ class GenericMLP(nn.Module):
             if p.dim() > 1:
                 init(p)
 
+    def _forward_infer(self, x):
+        """inference (eval mode, autograd off): Conv1d(k=1) -> BatchNorm1d -> ReLU [-> Dropout] blocks as the GEMM + ONE eval-form
+        bn_act launch (running statistics; the convolution's bias enters as pre_bias, not as a launch of its own)"""
+        from . import bn_act as BNA
+        mods = list(self.layers)
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            nxt = mods[i + 1:i + 4]
+            if (type(m) is PointwiseConv1d and len(nxt) >= 2 and type(nxt[0]) is nn.BatchNorm1d and type(nxt[1]) is nn.ReLU
+                    and nxt[0].running_mean is not None and nxt[0].affine):
+                bn = nxt[0]
+                drop = nxt[2] if len(nxt) >= 3 and type(nxt[2]) is nn.Dropout else None
+                h = m(x) if m.bias is None else PointwiseConv1d.forward_no_bias(m, x)
+                x = BNA.bn_act(h, bn.weight, bn.bias, bn.running_mean, bn.running_var, False, bn.eps, 0.0, relu=True,
+                               pre_bias=m.bias)
+                i += 3 if drop is None else 4
+            else:
+                x = m(x)
+                i += 1
+        return x
+
     def forward(self, x):
         mods = list(self.layers)
+        from . import heads as HD
+        if HD.inference(self) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3:
+            return self._forward_infer(x)
         if not (self.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and torch.is_grad_enabled()):
             from . import bn_act as BNA
             return BNA.run_sequential(self.layers, x)

@@ -184,7 +184,9 @@ class _Qkv(torch.autograd.Function):
         d.w, d.b, d.wt = wq.data_ptr(), bq.data_ptr(), wt.data_ptr()
         d.x, d.out = (x.data_ptr() if x is not None else None), out.data_ptr()
         pend = HD.take_pending_pos(pos)
-        if pend is not None:
+        if pend is not None and pend[2]:  # (its inference form: the running statistics, only `pos` written)
+            L.check(L.lib().vdetr_rb_qkv_pos_infer_f32(ctypes.byref(d), ctypes.byref(pend[0]), L.stream_ptr()), "rb_qkv_pos_infer")
+        elif pend is not None:
             # `pos` is the output of a position MLP whose launch was left to this one (heads.lazy_pos): the q / k workgroups compute
             # their rows of it on the way in, the q workgroups write it (and what the MLP's backward reads)
             L.check(L.lib().vdetr_rb_qkv_pos_f32(ctypes.byref(d), ctypes.byref(pend[0]), L.stream_ptr()), "rb_qkv_pos")
@@ -550,11 +552,11 @@ class _Ffn0(torch.autograd.Function):
 # ---- module-level entry points -----------------------------------------------------------------------------------------
 def ffn0_usable(layer, x):
     """FFNLayer `layer` on x [n, B, 256] through vdetr_rb_ffn0_f32: fp32 on the GPU, 256 -> 256 -> 256 with biases, ReLU, plain LayerNorms
-    (the layer's own and the one the caller applies to its output), gradients on"""
+    (the layer's own and the one the caller applies to its output), gradients on — or off in inference (heads.inference)"""
     return bool(FUSED_FFN0 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[-1] == C and layer.normalize_before
                 and layer.linear1.weight.shape == (C, C) and layer.linear2.weight.shape == (C, C) and layer.linear1.bias is not None
                 and layer.linear2.bias is not None and type(layer.activation) is torch.nn.ReLU and _plain_ln(layer.norm)
-                and layer.post_norm is not None and _plain_ln(layer.post_norm) and torch.is_grad_enabled())
+                and layer.post_norm is not None and _plain_ln(layer.post_norm) and (torch.is_grad_enabled() or HD.inference(layer)))
 
 
 def ffn0(layer, x, act_salt, aln_salt):

@@ -1096,6 +1096,14 @@ class TransformerDecoder(nn.Module):
         assert pre_center_normalized is not None and pre_size_normalized is not None
         feats = box_features.permute(1, 2, 0)  # B x C x nQ
         heads = self.mlp_heads[idx] if self.mlp_sep else self.mlp_heads
+        if HD.inference(self) and self._batchable(heads):
+            # inference: the five heads as ONE launch with the running statistics (csrc/heads.hip: heads_infer_kernel), y in place
+            L = self._head_layers(idx)
+            outs = [l[8].weight.shape[0] for l in L]
+            if HD.heads_infer_usable(box_features, L, max(outs)):
+                return box_decode.decode_boxes_joint(HD.heads_infer(box_features, L, max(outs)), outs, pre_center_normalized,
+                                                     pre_size_normalized, point_cloud_dims,
+                                                     self.box_processor.dataset_config.num_angle_bin, self.box_processor.cls_loss)
         raw = self._run_heads(heads, feats)
         if "_joint" in raw:
             y, chans = raw["_joint"]
@@ -1121,6 +1129,8 @@ class TransformerDecoder(nn.Module):
         if defer and self.training and enc_box_features.is_cuda and torch.is_grad_enabled():
             # the W^T images of every stage's heads, of the position MLPs and of the first layer's FFN: one launch (heads.py)
             HD.decoder_refresh(self)
+        elif HD.inference(self) and enc_box_features.is_cuda:
+            HD.decoder_refresh(self)  # (inference reads the same images: this forward's, an eval pass follows optimiser steps)
         output = self.first_layer(enc_box_features)
         normed = self.first_layer.post_normed if fuse_ln else self.norm(output)
         self.first_layer.post_norm = self.first_layer.post_normed = None
