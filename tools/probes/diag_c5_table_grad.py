@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The cut C5 model of tests/test_gpu_model.py's full-config case (2 scenes, 3 RPE layers, rotated boxes) on the device under the
-table gradient's switches: side stream / in line, box kernel (device decides) / general kernel only, dynamic distribution on / off,
-weight gradients parked / in line.  Prints, per cpb MLP parameter group of every layer, the relative difference to the first run."""
+table gradient's switches: side stream / in line, box kernel (device decides) / general kernel only, weight gradients parked / in
+line.  Prints, per cpb MLP parameter group of every layer, the relative difference to the first run."""
 import copy
 import os
 import sys
@@ -22,10 +22,9 @@ inp_cpu = TM._inputs(20000, 3, "cpu", bs)
 gpu = copy.deepcopy(model).to("cuda")
 
 
-def run(async_mode, bwd_kernel, dynamic, park):
+def run(async_mode, bwd_kernel, park):
     A.set_async_table_grad(async_mode)
     A.BWD_KERNEL = bwd_kernel
-    A.DYNAMIC_BWD = dynamic
     gpu.zero_grad(set_to_none=True)
     inp = {k: ([t.detach().to("cuda").requires_grad_(t.requires_grad) for t in v] if isinstance(v, list) else v.to("cuda"))
            for k, v in inp_cpu.items()}
@@ -42,11 +41,11 @@ def run(async_mode, bwd_kernel, dynamic, park):
 
 
 ref = None
-for mode in [("0", 1, True, False), ("0", 0, True, False), ("0", 0, False, False), ("1", 0, True, False), ("1", 0, True, True), ("1", 1, True, True), ("0", 1, True, False)]:
+for mode in [("0", 1, False), ("0", 0, False), ("1", 0, False), ("1", 0, True), ("1", 1, True), ("0", 1, False)]:
     g = run(*mode)
     if ref is None:
         ref = g
-        print("reference: async, bwd_kernel, dynamic, park =", mode)
+        print("reference: async, bwd_kernel, park =", mode)
         continue
     worst = {}
     for n, t in g.items():

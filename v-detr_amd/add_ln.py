@@ -158,7 +158,7 @@ def backward_core(cfg, ysrc, gamma, gamma2, mean, rstd, rng, ln_params, d_y, d_o
     nbytes = L.lib().vdetr_add_ln_bwd_workspace_bytes(ctypes.byref(d))
     # parameter sums after the backward, all LayerNorms in one launch (see DeferredLnGrads): the kernel only leaves
     # its per-workgroup partial sums, in a buffer of their own
-    defer = DeferredParamGrads.enabled and DeferredParamGrads.direct and (d_out2 is not None or gamma2 is None)
+    defer = DeferredParamGrads.enabled and (d_out2 is not None or gamma2 is None)
     if defer:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=ysrc.device)
         d_gamma = d_beta = d_gamma2 = d_beta2 = None

@@ -46,11 +46,6 @@ def new_rng_state(device, seed=None):
     return torch.tensor([seed & 0x7FFFFFFFFFFFFFFF, 0], dtype=torch.int64, device=device)
 
 
-# Per-device master state + the snapshot of the current step.  ``begin_step`` takes a snapshot (a NEW tensor that
-# is never written again, so autograd can keep it by reference) and bumps the master offset with a device op:
-# the same captured hipGraph therefore draws fresh dropout masks on every replay.  Modules that share a snapshot
-# stay independent through their per-module ``salt`` (the by-value seed of the descriptor).
-DYNAMIC_BWD = os.environ.get("VDETR_BWD_DYNAMIC", "1") != "0"
 # forward kernel of the 3DV-RPE attention (vdetr_attn_desc.fwd_kernel): 0 = persistent workgroups (attn_fwd_pipe.hip), 1 = the
 # round-4 grid kernel (A/B runs)
 FWD_KERNEL = int(os.environ.get("VDETR_FWD_KERNEL", "0"))
@@ -61,15 +56,7 @@ TABLE_GRID = 0
 # shared-KV backward: dO V^T, the softmax backward, dV and dK in one pass over the scores (attn_bwd_kv.hip) instead of
 # three library GEMMs around an element-wise kernel.  VDETR_BWD_FUSED=0 keeps the GEMM path (A/B measurements, parity).
 FUSED_KV_BWD = os.environ.get("VDETR_BWD_FUSED", "1") != "0"
-# dQ by attn_bwd_dq.hip (row-owner, exact fp32) instead of the library's batched GEMM.  OFF: alone it wins for per-head K/V (the
-# query self-attention: 11.7 against 19.2 us) and loses for shared K/V (31 against 26 us: every 16-row workgroup re-reads all of
-# K), but in the step these launches run NEXT TO the table-gradient branch on a quarter of the CUs, where a kernel bound by
-# matrix time pays 4x: C2 8.34 ms with the library, 8.37-8.41 with the kernel for the self-attention (VDETR_BWD_DQ=1), 8.45-8.48
-# for both (=2).
-_SELF_FWD8 = os.environ.get("VDETR_SELF_FWD8", "0") != "0"  # A/B switch (read once): see _FusedAttention.forward
 SELF_FWD_BODY = os.environ.get("VDETR_SELF_FWD", "") == "body"  # per-head forward: attn_fwd.hip's body instead of attn_fwd_self.hip (A/B; tests flip it)
-_DQ_KERNEL = os.environ.get("VDETR_BWD_DQ", "0") != "0"
-_DQ_KERNEL_SHARED = os.environ.get("VDETR_BWD_DQ", "0") == "2"
 
 
 # The RPE-table gradient kernel (2.3 ms of a 9 ms step) feeds parameters only: nothing on the backward's critical path waits
@@ -90,12 +77,6 @@ ASYNC_MIN_PAIRS = 1 << 21
 # scene's sampling kernel holds one CU for the first ~4.7 ms of a step: on 64 - 1 CUs every such launch took two rounds.
 # Step 7.31 ms at 192, 7.01 at 190, 7.06 at 188, 7.09 at 184, 7.26 at 176 (profiles/r05_step_bounds.txt).
 ASYNC_TABLE_GRID = int(os.environ.get("VDETR_BWD_ASYNC_GRID", "190"))
-_ASYNC_KV4 = os.environ.get("VDETR_BWD_ASYNC_KV_WAVES", "8") == "4"
-# vdetr_attn_desc.kv_halves = 1 (one workgroup per key tile) while a table kernel is live — 1: the per-head pass only; 2: the
-# shared-K/V pass as well; 0: never.  With the side grid at 192 the per-head form won 0.03 ms (7.36 -> 7.33; the
-# shared-K/V form lost: 7.41); at 190 the default shape is as fast or faster (7.01 / 7.03-7.05 / 7.18 for 0 / 1 / 2).
-# (round 6, on the final step: 0 / 1 / 2 = 6.41-6.42 / 6.39 / 6.58-6.59 ms: the per-head form is the default now)
-KV_ONE_WG = int(os.environ.get("VDETR_BWD_KV_ONE_WG", "1"))
 
 
 _step_side = {}  # device key -> this step's forward ran a cross-attention whose table gradient will go to the side stream
@@ -133,9 +114,6 @@ class SideResults:
                 torch.autograd.backward(roots, grads)
 
 
-_FLUSH_SIDE = os.environ.get("VDETR_FLUSH_SIDE", "1") != "0"
-_FLUSH_SIDE_POS = os.environ.get("VDETR_FLUSH_SIDE_POS", "1") != "0"
-_FLUSH_SIDE_LN = os.environ.get("VDETR_FLUSH_SIDE_LN", "1") != "0"
 _tick = {}
 side_late = []  # parameter-only work other modules hand over for the END of the backward: callables -> [(parameter, gradient)], keep-alive
 
@@ -144,9 +122,10 @@ def flush_layer_params_on_side(ref, rows):
     """Called from the backward pass when every decoder layer's backward has run (vdetr_transformer._LayersDone): the parked
     weight / bias gradients of the layers' linear maps (the items with `rows` rows: 64 of them at the model's size) are computed
     on the side branch — behind the last table kernel — while the main stream goes on with the first layer's and the
-    projection's backward; runtime.flush_weight_grads joins and delivers (SideResults).  Only where that branch is in use."""
+    projection's backward; runtime.flush_weight_grads joins and delivers (SideResults).  Only where that branch is in use.
+    (One batch for all layers: leaving per layer, as each layer's backward ends, made the step slower — DESIGN.md §5.1.)"""
     from .helpers import DeferredParamGrads, DeferredPosEmbedGrads
-    if not (_FLUSH_SIDE and ref.is_cuda and DeferredParamGrads.enabled and DeferredParamGrads.direct and side_branch_in_use(ref.device)):
+    if not (ref.is_cuda and DeferredParamGrads.enabled and side_branch_in_use(ref.device)):
         return
     dev = ref.device
     key = _dev_key(dev)
@@ -167,65 +146,15 @@ def flush_layer_params_on_side(ref, rows):
     with torch.cuda.stream(side):
         ts_mark("side: parked gradients start")
         DeferredParamGrads.flush(select=lambda it: it[2].shape[0] == rows, collect=pairs, keepalive=keep)
-        if _FLUSH_SIDE_POS:  # the layers' learned query-position embeddings: complete as well (one per layer)
-            DeferredPosEmbedGrads.flush(collect=pairs, keepalive=keep)
-        if _FLUSH_SIDE_LN:   # the LayerNorm parameter sums of the layers' residual blocks (the first layer's follow at the flush)
-            from .add_ln import DeferredLnGrads
-            DeferredLnGrads.flush(collect=pairs, keepalive=keep)
+        # the layers' learned query-position embeddings: complete as well (one per layer)
+        DeferredPosEmbedGrads.flush(collect=pairs, keepalive=keep)
+        # the LayerNorm parameter sums of the layers' residual blocks (the first layer's follow at the flush)
+        from .add_ln import DeferredLnGrads
+        DeferredLnGrads.flush(collect=pairs, keepalive=keep)
         for fn, alive in late:  # (e.g. the box heads' weight gradients: vdetr_transformer._DeferredHeads)
             pairs += fn()
             keep.append(alive)
         ts_mark("side: parked gradients end")
-    if pairs:
-        SideResults.pending.append((dev, pairs, keep))
-
-
-# Round 6: the parked parameter gradients of a decoder layer leave for the side branch as soon as that layer's backward has
-# produced them, instead of all layers' together behind the last table kernel.  The step's real timeline (timestamp kernels in the
-# captured graph, tools/probes/step_timeline.py) showed why: during the layers' backward the MAIN chain is the critical path (330-415
-# us per layer on the 66 CUs the table kernel leaves it, against ~300 us per table kernel), so the side stream sits idle for
-# 20-113 us behind every table kernel — 470 us per step — and then ran 480 us of weight-gradient GEMMs after the last one, with
-# the main chain long done.  MEASURED AND NOT KEPT (off by default; VDETR_FLUSH_PER_LAYER=1: the layers' weight gradients, =2: the
-# LayerNorm sums and the position MLPs' as well): per layer the work is 4 / 14 launches and takes 100 / 170 us next to the chain —
-# 8 x that is more than the one batched pass at the end (480 us), the side branch stays the longer one: 6.85 -> 7.06 / 7.47 ms
-# (profiles/r06_step_timeline.txt).
-_FLUSH_PER_LAYER = os.environ.get("VDETR_FLUSH_PER_LAYER", "0") != "0"
-_FLUSH_PER_LAYER_ALL = os.environ.get("VDETR_FLUSH_PER_LAYER", "0") == "2"
-
-
-def side_flush_begin(ref):
-    """Called inside a layer's backward once its parked operands are complete and BEFORE its last launch of the chain: records
-    the fork (the chain's next launch then stays the fork node's first successor: it keeps its hardware queue, see
-    _FusedAttention.backward).  Returns a token for side_flush_end, or None where the side branch is not in use."""
-    from .helpers import DeferredParamGrads
-    if not (_FLUSH_SIDE and _FLUSH_PER_LAYER and ref.is_cuda and DeferredParamGrads.enabled and DeferredParamGrads.direct
-            and side_branch_in_use(ref.device) and _side_keep):
-        return None
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream(ref.device))
-    return ev
-
-
-def side_flush_end(ev, ref, rows):
-    """the parked gradients that were complete at side_flush_begin, computed on the side branch (delivered at the flush: SideResults)"""
-    if ev is None:
-        return
-    from .helpers import DeferredParamGrads, DeferredPosEmbedGrads
-    from .runtime import ts_mark
-    dev = ref.device
-    side = _side_stream(dev)
-    side.wait_event(ev)
-    pairs, keep = [], []
-    with torch.cuda.stream(side):
-        ts_mark("side: layer's parked gradients start")
-        DeferredParamGrads.flush(select=lambda it: it[2].shape[0] == rows, collect=pairs, keepalive=keep)
-        if _FLUSH_PER_LAYER_ALL:  # (the position MLPs' and LayerNorms' parameters too: ~14 launches, 170 us per layer — too long)
-            if _FLUSH_SIDE_POS:
-                DeferredPosEmbedGrads.flush(collect=pairs, keepalive=keep)
-            if _FLUSH_SIDE_LN:
-                from .add_ln import DeferredLnGrads
-                DeferredLnGrads.flush(collect=pairs, keepalive=keep)
-        ts_mark("side: layer's parked gradients end")
     if pairs:
         SideResults.pending.append((dev, pairs, keep))
 
@@ -419,8 +348,7 @@ class DeferredTableGrads:
 def table_grads_parkable(ref):
     """True where `park_table_grads` parks: side-stream table gradients + parked weight gradients, on the GPU, under grad mode"""
     from .helpers import DeferredParamGrads
-    return bool(ASYNC_TABLE_GRAD and DeferredParamGrads.enabled and ref.is_cuda and ref.requires_grad and torch.is_grad_enabled()
-                and os.environ.get("VDETR_BWD_ASYNC_PARK", "1") != "0")
+    return bool(ASYNC_TABLE_GRAD and DeferredParamGrads.enabled and ref.is_cuda and ref.requires_grad and torch.is_grad_enabled())
 
 
 def park_table_grads(tables, mlp=None):
@@ -489,12 +417,10 @@ def side_table_grid(device):
     return max(2, (ASYNC_TABLE_GRID * cus // 256) & ~1)
 
 
-def _fused_kv_ok(want_table):
-    if not FUSED_KV_BWD:
-        return False
-    if want_table:  # the table gradient then reads the dS the fused kernel wrote, with the dynamic distribution's counters
-        return DYNAMIC_BWD
-    return True
+# Per-device master state + the snapshot of the current step.  ``begin_step`` takes a snapshot (a NEW tensor that
+# is never written again, so autograd can keep it by reference) and bumps the master offset with a device op:
+# the same captured hipGraph therefore draws fresh dropout masks on every replay.  Modules that share a snapshot
+# stay independent through their per-module ``salt`` (the by-value seed of the descriptor).
 _master = {}
 _current = {}
 
@@ -636,7 +562,7 @@ def _kv_register(out, q, v, table, vertices, cos_sin, kind, B, H, nQ, nK):
         return None
     r = _KvRec()
     r.q, r.v, r.vertices, r.cos_sin, r.kind, r.dims = q, v, (vertices if table is not None else None), cos_sin, kind, (B, H, nQ, nK)
-    r.want_aux = bool(table is not None and table.requires_grad and DYNAMIC_BWD)
+    r.want_aux = bool(table is not None and table.requires_grad)
     r.prepared, r.emitted = False, None
     r.ws = r.dkv = r.delta = r.aux = None
     lst = _kv_recs.setdefault(_dev_key(q.device), [])
@@ -718,9 +644,7 @@ class _FusedAttention(Function):
         rows = (B, nQ, H) if kind == L.VDETR_ATTN_SHARED_KV else (B, H, nQ)
         lse = torch.empty(rows, dtype=torch.float32, device=q.device)
         scores = torch.empty(rows + (nK,), dtype=torch.float32, device=q.device) if need_grad else None
-        if kind == L.VDETR_ATTN_PER_HEAD and _SELF_FWD8:
-            d.fwd_kernel = 1  # (A/B: the eight-wave workgroups also where the four-wave form would be taken)
-        elif kind == L.VDETR_ATTN_PER_HEAD and SELF_FWD_BODY:
+        if kind == L.VDETR_ATTN_PER_HEAD and SELF_FWD_BODY:
             d.fwd_kernel = 4  # (A/B, parity tests: the general body also where the lean self-attention kernel would be taken)
         if operand_bf16 and not bf16 and FWD_KERNEL == 0:
             d.fwd_kernel = 3  # f32 tensors, q / k / v rounded to one bf16 part each inside the kernels (vdetr_hip.h)
@@ -786,14 +710,14 @@ class _FusedAttention(Function):
             # the caller vouches for axis-aligned boxes (vertices out of the box decode: exact coordinate patterns): the box kernel
             # alone, without the general kernel's launch in front of it; a query that is not a box poisons dtable with NaN
             d.bwd_kernel = 2
-        if want_table and DYNAMIC_BWD:  # norm maxima + query counters for the dynamic distribution (see vdetr_hip.h)
+        if want_table:  # norm maxima + query counters for the dynamic distribution (see vdetr_hip.h)
             aux = _take_zeros(q, (8,), torch.int32)  # 5 words used (vdetr_hip.h: bwd_aux)
             d.bwd_aux = aux.data_ptr()
         delta = torch.empty((B, nQ, H) if shared else (B, H, nQ), dtype=torch.float32, device=q.device)
         # the fused key-side pass where it is built AND inside its limits (attn_bwd_kv.hip:kv_run: a score matrix below 2 GB,
         # at most 65535 of them, 16-B aligned operands); everything else takes the library-GEMM composition as before
         rows_kv, nprob_kv = (4 * nQ, B) if shared else (nQ, B * H)
-        fused = (_fused_kv_ok(want_table) and ((shared and H == 4) or (not shared and not want_table))
+        fused = (FUSED_KV_BWD and ((shared and H == 4) or (not shared and not want_table))
                  and rows_kv * nK * 4 < (1 << 31) and nprob_kv <= 65535 and v.stride(1) % 4 == 0
                  and all(t.data_ptr() % 16 == 0 for t in (v, lse)))
         if not fused:  # (the fused pass computes delta in the first workgroups of its operand-packing launch)
@@ -806,12 +730,12 @@ class _FusedAttention(Function):
             dkv = torch.empty((2, B, nK, k.shape[2]), dtype=torch.float32, device=q.device)
             run_async = want_table and ctx.table_async and _async_wanted(B, nQ, nK)
             # 4 waves fit NEXT TO a table kernel that holds every CU; with CUs left free for the main chain the default shape
-            d.kv_waves = 4 if (run_async or _side_keep) and (ASYNC_TABLE_GRID >= 256 or _ASYNC_KV4) else 8
+            d.kv_waves = 4 if (run_async or _side_keep) and ASYNC_TABLE_GRID >= 256 else 8
             # the query self-attention's pass (256 one-per-CU workgroups at the model's size) next to a live table kernel: one
-            # workgroup per key tile
-            d.kv_halves = 1 if (_side_keep and (KV_ONE_WG >= 2 or (KV_ONE_WG == 1 and not shared))) else 2
+            # workgroup per key tile; the shared-K/V pass keeps two
+            d.kv_halves = 1 if (_side_keep and not shared) else 2
             rec = getattr(ctx, "kv_rec", None)
-            if (rec is not None and rec.prepared and rec.emitted == dout.data_ptr() and (rec.aux is not None) == bool(want_table and DYNAMIC_BWD)
+            if (rec is not None and rec.prepared and rec.emitted == dout.data_ptr() and (rec.aux is not None) == bool(want_table)
                     and in_dtype == torch.float32):
                 # the producer of dout left its images and delta behind, the step's prep launch everything else: the pass alone
                 delta, dkv, aux = rec.delta, rec.dkv, rec.aux
@@ -836,20 +760,9 @@ class _FusedAttention(Function):
                 dtable = _table_accumulator(table)  # (a fill, if any, is in front of the event)
                 fork = torch.cuda.Event()
                 fork.record(torch.cuda.current_stream(q.device))
-            # dQ = scale dS K: the row-owner kernel (attn_bwd_dq.hip; exact fp32 products) for per-head K/V where K is as the
-            # kernel reads it — rows of contiguous floats at a constant stride —, the library's batched GEMM otherwise
-            kd = k if shared else k.reshape(B, nK, C)
-            if (_DQ_KERNEL and (not shared or _DQ_KERNEL_SHARED) and k.dtype == torch.float32 and ds.dtype == torch.float32 and kd.stride(2) == 1
-                    and kd.stride(1) % 4 == 0 and (B == 1 or kd.stride(0) == nK * kd.stride(1))
-                    and kd.data_ptr() % 16 == 0 and ds.data_ptr() % 16 == 0 and B * (1 if shared else H) <= 65535):
-                dq = q.new_empty((B, nQ, C))
-                keep = d.k_row_stride
-                d.k_row_stride = kd.stride(1)
-                try:
-                    L.check(lib.vdetr_attn_bwd_dq_f32(ctypes.byref(d), L.ptr(ds), L.ptr(kd), L.ptr(dq), L.stream_ptr()), "attn_bwd_dq")
-                finally:
-                    d.k_row_stride = keep
-            elif shared:
+            # dQ = scale dS K: the library's batched GEMM.  The row-owner kernel (attn_bwd_dq.hip) wins alone for per-head K/V but
+            # loses next to the table-gradient branch
+            if shared:
                 dq = q.new_empty((B, nQ * H, HEAD_DIM))
                 torch.baddbmm(dq, ds.view(B, nQ * H, nK), k, beta=0.0, alpha=float(scale), out=dq)
                 dq = dq.view(B, nQ, C)

@@ -259,13 +259,12 @@ def pos_mlp_usable(module, x_tok):
 # the layers it runs through rowblock.py; a layer that takes another path calls materialize_pos() first.  `out`, the hidden
 # activations and the statistics are NOT valid until one of the two has run.
 _pending_pos = {}
-POS_IN_QKV = os.environ.get("VDETR_POS_IN_QKV", "1") != "0"
 _lazy_pos = {"on": False}
 
 
 def lazy_pos(on):
     """from here on position MLPs are left to rowblock.qkv (True) or launched at once (False); returns the previous state"""
-    prev, _lazy_pos["on"] = _lazy_pos["on"], bool(on) and POS_IN_QKV
+    prev, _lazy_pos["on"] = _lazy_pos["on"], bool(on)
     return prev
 
 

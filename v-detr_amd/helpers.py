@@ -105,7 +105,6 @@ class DeferredParamGrads:
     still unset takes its slice of the batched result as `.grad` directly)."""
     enabled = False
     pending = []
-    direct = os.environ.get("VDETR_WG_DIRECT", "1") != "0"  # A/B switch (read once)
 
     @staticmethod
     def _view_of_leaf(p):
@@ -119,13 +118,13 @@ class DeferredParamGrads:
     def _deliver(cls, p, g, roots, grads):
         """gradient g of the tensor p a `linear` call used as weight / bias: straight into `.grad` where no accumulation or
         view bookkeeping is needed, through autograd otherwise"""
-        if cls.direct and p.is_leaf and p.grad is None:
+        if p.is_leaf and p.grad is None:
             # a parameter without a gradient yet simply takes its slice of the batched result:
             # AccumulateGrad would clone every such slice (one copy launch per parameter, ~80 per step)
             p.grad = g
             return
         fn = p.grad_fn
-        if cls.direct and type(fn).__name__ == "_AliasBackward":
+        if type(fn).__name__ == "_AliasBackward":
             # an alias of adjacent parameters (cat_params / stack_params / slot_stack_params): hand each parameter its
             # slice, as _Alias.backward would, without one AccumulateGrad launch per parameter
             parts = _Alias.backward(fn, g)[2:]
@@ -189,7 +188,7 @@ class DeferredParamGrads:
                     # rows of the batched result then ARE the leaf's gradient (no stack launch in an UnbindBackward)
                     def order(e):
                         i, it = e
-                        base = cls._view_of_leaf(it[0]) if cls.direct else None
+                        base = cls._view_of_leaf(it[0])
                         return (0, i, 0) if base is None else (1, id(base), it[0].storage_offset())
                     group = [it for _, it in sorted(enumerate(group), key=order)]
                     need_w, need_b = any(it[0] is not None for it in group), any(it[1] is not None for it in group)
@@ -210,7 +209,7 @@ class DeferredParamGrads:
                         if p is None:
                             i += 1
                             continue
-                        base = cls._view_of_leaf(p) if cls.direct else None
+                        base = cls._view_of_leaf(p)
                         k = 1
                         if base is not None and base.numel() % p.numel() == 0:
                             k = base.numel() // p.numel()
@@ -452,9 +451,6 @@ ACTIVATION_DICT = {"relu": nn.ReLU, "gelu": nn.GELU, "leakyrelu": partial(nn.Lea
 WEIGHT_INIT_DICT = {"xavier_uniform": nn.init.xavier_uniform_}
 
 
-_POS_TOKEN_MAJOR = os.environ.get("VDETR_POS_TOKEN_MAJOR", "1") != "0"  # A/B switch (read once), _PosEmbedDeferred.forward
-
-
 class DeferredPosEmbedGrads:
     """The learned query-position embeddings (Conv1d -> BatchNorm -> ReLU -> Conv1d on DETACHED box coordinates, one per decoder
     layer) exist only to train their own parameters: nothing upstream waits for their backward.  With
@@ -523,7 +519,7 @@ class _PosEmbedDeferred(torch.autograd.Function):
         y, rec = BNA.forward_record(h, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, 0.0, 0,
                                     counters=[bn.num_batches_tracked], pre_bias=conv1.bias)
         ctx.rec = (module, x, y, rec)
-        if _POS_TOKEN_MAJOR and y.shape[0] == 1 and conv2.bias is not None:
+        if y.shape[0] == 1 and conv2.bias is not None:
             # one scene: the output layer as out^T [N, C] = y^T W^T + b — ONE launch (the bias rides in the GEMM's epilogue; the
             # channel-major form is a GEMM + a broadcast add), and the [N, B, C] view the decoder adds to its queries twice per
             # layer is then dense memory (the channel-major result reached those adds as a transposed view)
@@ -560,7 +556,7 @@ class PositionEmbeddingLearned(nn.Module):
         if not (self.training and x.is_cuda and type(bn) is nn.BatchNorm1d and bn.momentum is not None and bn.track_running_stats):
             from . import bn_act as BNA  # (cross-replica statistics on this path too while bn_act.set_sync is on)
             return BNA.run_sequential(head, x.contiguous())
-        if DeferredParamGrads.enabled and DeferredParamGrads.direct and not x.requires_grad and torch.is_grad_enabled() \
+        if DeferredParamGrads.enabled and not x.requires_grad and torch.is_grad_enabled() \
                 and head[3].bias is not None:
             return _PosEmbedDeferred.apply(self, x, head[0].weight, head[1].weight, head[1].bias, head[3].weight,
                                            head[3].bias)

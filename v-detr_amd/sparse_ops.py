@@ -193,7 +193,7 @@ class ConvPlan:
                 "src": src, "rows": rows, "slot": slot.contiguous(), "islot": islot}
 
     def select(self, cin, cout):
-        return self.grouping("sorted" if cin * cout >= self.SORTED_MIN_CHANNELS and not _RANGES_ONLY else "ranges")
+        return self.grouping("sorted" if cin * cout >= self.SORTED_MIN_CHANNELS else "ranges")
 
 
 def _group_weight(weight, g):
@@ -253,10 +253,6 @@ class _PlannedConvFn(Function):
         return dfeats, dw, None
 
 
-_RANGES_ONLY = os.environ.get("VDETR_SP_RANGES_ONLY", "0") == "1"  # A/B switch: never use the count-sorted grouping
-_WGRAD_WGS = int(os.environ.get("VDETR_SP_WGRAD_WGS", "768"))  # workgroups per weight-gradient launch (A/B switch)
-
-
 class _PinnedCounts:
     """a ring of pinned host rows for the asynchronous copies of the plans' pair counts (one allocation per process)"""
     rows, width = 512, 64
@@ -287,6 +283,7 @@ class PairPlan:
     plans cost one synchronisation instead of three each."""
 
     _LAZY = ("P", "pairs", "counts", "seg", "tiles", "ntiles", "pin", "pout")
+    WGRAD_WORKGROUPS = 768  # workgroups per weight-gradient launch: ~3 per CU
 
     def __init__(self, nbr, nin):
         K, nout = nbr.shape
@@ -399,7 +396,7 @@ class PairPlan:
         t = 128 if (cin >= 128 and cout >= 128) else 64  # channel tile of vdetr_sp_pairs_wgrad_f32
         key = (-(-cin // t)) * (-(-cout // t))
         if key not in self._chunks:
-            want = max(1, _WGRAD_WGS // key)
+            want = max(1, self.WGRAD_WORKGROUPS // key)
             L = max(64, -(-(-(-self.P // want)) // 16) * 16)
             kidx, start, length, per = PairPlan._cut(self.counts, self.seg, L)
             n = int(kidx.shape[0])
@@ -590,7 +587,7 @@ def bn_act(x, bn, act=None, residual=None):
     # (sp_bn.hip holds one float4 of a row per thread, 256 threads: up to 1024 channels; momentum=None is a cumulative
     # average, which the kernels do not do: both go through the module)
     fused = x.is_cuda and type(bn) is torch.nn.BatchNorm1d and x.shape[1] % 4 == 0 and 0 < x.shape[1] <= 1024 and x.shape[0] > 0 \
-        and not _NO_FUSED_BN and (bn.momentum is not None or not bn.training)
+        and (bn.momentum is not None or not bn.training)
     if not fused:
         from . import bn_act as BNA
         # (with bn_act.set_sync this is still a cross-replica BatchNorm — as tensor expressions — and a rank whose tensor is
@@ -610,7 +607,6 @@ def bn_act(x, bn, act=None, residual=None):
                             bn.num_batches_tracked if bn.track_running_stats else None, training, momentum, bn.eps, _ACT[act])
 
 
-_NO_FUSED_BN = os.environ.get("VDETR_SP_FUSED_BN", "1") == "0"  # A/B switch
 _MODE = os.environ.get("VDETR_SP_MODE", "pairs")  # pairs (fused kernels) | plan (batched library GEMMs) | im2col
 _IM2COL = _MODE == "im2col" or os.environ.get("VDETR_SP_IM2COL", "0") == "1"  # A/B switch: one dense im2col GEMM per layer instead of the plan
 

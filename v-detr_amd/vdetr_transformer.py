@@ -259,7 +259,7 @@ class GlobalShareCrossAttention(nn.Module):
         # they were created before any decoder layer — only after every layer's backward, and waits there; with parked weight
         # gradients the tables' own backward (three GEMMs, written out in DeferredTableGrads.begin_flush) follows the last
         # table kernel ON that stream, next to the flush
-        if A.table_grads_parkable(w1) and os.environ.get("VDETR_BWD_ASYNC_MLP", "1") != "0":
+        if A.table_grads_parkable(w1):
             with torch.no_grad():
                 fused = GlobalShareCrossAttention._cpb_fused(mods[0], w1, b1, w2, 8 * n)
                 if fused is not None:  # hidden activations + tables of all 8 n MLPs in one launch (csrc/cpb_tables.hip)
@@ -617,14 +617,6 @@ class FFNLayer(nn.Module):
 # =====================================================================================================
 _DEFER_HEADS = os.environ.get("VDETR_DEFER_HEADS", "1") != "0"  # A/B switch (read once)
 _CPB_FUSED = os.environ.get("VDETR_CPB_FUSED", "1") != "0"       # the RPE tables' MLPs as one launch (csrc/cpb_tables.hip)
-_STAGE0_WG_SIDE = os.environ.get("VDETR_STAGE0_WG", "inline") == "side"
-_DEFER_STAGE0 = os.environ.get("VDETR_DEFER_STAGE0", "1") != "0"  # the first stage's heads recorded too (round 6; A/B switch)
-# the heads' weight gradients on the side branch (VDETR_HEADS_SIDE): 1 = at once, at the BEGINNING of the backward, where the branch
-# is idle - measured C2 8.376 -> 8.33 ms, but C5 (4 scenes: the GEMMs are 4 x larger and hold the first table kernels up) 26.15 ->
-# 26.61 ms; 2 (default) = at the END of the backward with the layers' weight gradients (attention.flush_layer_params_on_side):
-# C2 8.33 -> 8.26 ms (two runs each), C5 25.01 -> 24.80; 0 = on the main stream inside the heads' backward
-_HEADS_SIDE = os.environ.get("VDETR_HEADS_SIDE", "2") != "0"
-_HEADS_SIDE_LATE = os.environ.get("VDETR_HEADS_SIDE", "2") == "2"
 
 
 class _DeferredHeads(torch.autograd.Function):
@@ -685,14 +677,12 @@ class _DeferredHeads(torch.autograd.Function):
         w1 = stack_params([r["w1"].detach().reshape(G * C, C) for r in recs])    # [S,G*C,C]
         # The three weight-gradient GEMMs and the output bias sum feed parameters only.  Where this step's table gradients run on
         # a side branch (attention.side_branch_in_use) and parameter gradients are delivered at the flush anyway, they go to that
-        # branch - it is idle until the first decoder layer's key-side pass - behind ONE fork after the last input-gradient
-        # operand exists: 180 us of GEMMs leave the chain (VDETR_HEADS_SIDE=1; off by default, see _HEADS_SIDE)
+        # branch at the END of the backward, with the layers' weight gradients (attention.flush_layer_params_on_side); launched at
+        # once, at its beginning, they held up C5's first table kernels (docs/DESIGN_rounds1-4.md §4.4e)
         from .helpers import DeferredParamGrads
         # (the first stage's node is the LAST thing the backward pass reaches: its weight gradients in line, under the side branch's
         #  tail, not behind it)
-        on_side = (_HEADS_SIDE and dY.is_cuda and DeferredParamGrads.enabled and DeferredParamGrads.direct
-                   and A.side_branch_in_use(dev) and not r0.get("inline_wg", False))
-        late = _HEADS_SIDE_LATE and not r0.get("wg_side_now", False)
+        on_side = (dY.is_cuda and DeferredParamGrads.enabled and A.side_branch_in_use(dev) and not r0.get("inline_wg", False))
 
         def weight_grads(dx2, dx1):
             db3 = dY.sum(dim=(1, 4))                                                               # [S,G,rows]
@@ -714,10 +704,6 @@ class _DeferredHeads(torch.autograd.Function):
         # ---- first hidden block
         dx1 = torch.empty_like(dh1)
         dbn1 = BNA.backward_from_records([r["bn1"] for r in recs], [dh1[s] for s in range(S)], [dx1[s] for s in range(S)])
-        fork = None
-        if on_side and not late:  # (recorded here, waited for behind the chain's next launch: the chain keeps its queue)
-            fork = torch.cuda.Event()
-            fork.record(torch.cuda.current_stream(dev))
         if one:  # the transposed product: rows = queries, i.e. the [nQ,B,C] layout the layers want (no permuted view to copy)
             dft = torch.bmm(dx1.view(S, G * C, N).transpose(1, 2), w1)                             # [S,N,C]
             out = [dft[s].view(N, 1, C) for s in range(S)]
@@ -733,14 +719,8 @@ class _DeferredHeads(torch.autograd.Function):
                 return pairs
             for s in range(S):
                 out += [None, dbn1[s][1], dbn1[s][2], None, dbn2[s][1], dbn2[s][2], None, None]
-            if late:  # at the END of the backward, behind the last table kernel (attention.flush_layer_params_on_side)
-                A.side_late.append((lambda: pairs_of(*weight_grads(dx2, dx1)), (dY, h2, h1, f, dx2, dx1)))
-                return (None, None, *out)
-            side = A._side_stream(dev)
-            side.wait_event(fork)
-            with torch.cuda.stream(side):
-                pairs = pairs_of(*weight_grads(dx2, dx1))
-            A.SideResults.pending.append((dev, pairs, (dY, h2, h1, f, dx2, dx1)))
+            # at the END of the backward, behind the last table kernel (attention.flush_layer_params_on_side)
+            A.side_late.append((lambda: pairs_of(*weight_grads(dx2, dx1)), (dY, h2, h1, f, dx2, dx1)))
             return (None, None, *out)
         db3, dw3, dw2, dw1 = weight_grads(dx2, dx1)
         for s, r in enumerate(recs):
@@ -1137,15 +1117,11 @@ class TransformerDecoder(nn.Module):
         # the first stage's heads on all encoder tokens: recorded like the later stages' (the fused launches of csrc/heads.hip where
         # the shapes fit) and differentiated by a _DeferredHeads node of its own — the last thing the backward pass reaches
         recorded = self._stage_recorded(0, point_cloud_dims, normed, enc_box_predictions["center_normalized"],
-                                        enc_box_predictions["size_normalized"]) if (defer and _DEFER_STAGE0) else None
+                                        enc_box_predictions["size_normalized"]) if defer else None
         if recorded is not None:
             box_prediction, rec0 = recorded
-            # the first stage's node is the LAST the backward reaches: its weight gradients in line (VDETR_STAGE0_WG=side: on the
-            # side branch at once, behind whatever that still has queued)
-            if _STAGE0_WG_SIDE:
-                rec0["wg_side_now"] = True
-            else:
-                rec0["inline_wg"] = True
+            # the first stage's node is the LAST the backward reaches: its weight gradients in line
+            rec0["inline_wg"] = True
             self._attach_deferred([rec0], [box_prediction])
         else:
             box_prediction = self.get_proposal_box_predictions_refine(
