@@ -873,6 +873,16 @@ int vdetr_nms3d_f32(const float* corners, const float* score, const int32_t* cls
                     int B, int K, double iou_threshold, int old_type, uint8_t* keep, void* workspace, size_t workspace_bytes,
                     vdetr_stream_t stream);
 
+/* Rotated-box NMS (the reference's --rotated_nms has no working path, this defines it): the greedy NMS
+ * above with ONE change, the overlap of boxes i and j is the reference's box3d_iou(corners_i, corners_j)
+ * (utils/box_util.py:122-147: the clipped x-z footprints times the common height, float64 on the float32 corners; i is the
+ * better-scored box) instead of the IoU of the axis-aligned extents.  old_type divides the intersection volume by
+ * box3d_vol(corners_j).  Same arguments, limits and status codes as vdetr_nms3d_f32; the workspace is larger. */
+size_t vdetr_nms3d_rot_workspace_bytes(int B, int K);
+int vdetr_nms3d_rot_f32(const float* corners, const float* score, const int32_t* cls, const uint8_t* valid, const int64_t* order,
+                        int B, int K, double iou_threshold, int old_type, uint8_t* keep, void* workspace,
+                        size_t workspace_bytes, vdetr_stream_t stream);
+
 /* Points inside every predicted box: counts (B,K) i32 += #{n : points[b,n] in boxes[b,k]} (ZERO-FILLED by the caller).
  * Replaces mmcv points_in_boxes_all + sum as used by parse_predictions' remove_empty_box (utils/ap_calculator.py:78-93)
  * without the (B,N,K) flag tensor.  points (B,N,3) f32; boxes (B,K,7) f32 = centre xyz, sizes dx dy dz, yaw rz (the
@@ -888,6 +898,13 @@ int vdetr_box_point_count_f32(const float* points, const float* boxes, int B, in
 int vdetr_box3d_iou_max_f64(const float* pred_corners, const int32_t* pred_img, const int32_t* pred_cls, int P,
                             const float* gt_corners, const int32_t* gt_cls, const int32_t* img_gt_begin, double* ovmax,
                             int32_t* jmax, vdetr_stream_t stream);
+
+/* The reference's box3d_iou for all pairs: out (Na,Nb) f64, out[a,b] = box3d_iou(corners_a[a], corners_b[b]) with
+ * corners_a (Na,8,3) f32 and corners_b (Nb,8,3) f32 (box a is the subject polygon of the clip, box b the clip polygon).
+ * The same routine as the matcher above and the rotated NMS; nearly coincident rotated boxes give the reference's
+ * ill-conditioned values (hull of a clip that divided by ~0), not a cleaned-up IoU.  Na * Nb <= 2^30. */
+int vdetr_box3d_iou_pairs_f64(const float* corners_a, int Na, const float* corners_b, int Nb, double* out,
+                              vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Sparse-convolution backbone: index kernels behind the MinkowskiEngine call sites of the

@@ -352,9 +352,13 @@ _SIGNATURES = {
     "vdetr_nms3d_workspace_bytes": (c_size_t, [c_int, c_int]),
     "vdetr_nms3d_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int, c_void_p,
                         c_void_p, c_size_t, c_void_p]),
+    "vdetr_nms3d_rot_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "vdetr_nms3d_rot_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int, c_void_p,
+                            c_void_p, c_size_t, c_void_p]),
     "vdetr_box_point_count_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_box3d_iou_max_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
+    "vdetr_box3d_iou_pairs_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vdetr_morton_sort_max": (c_int, []),
     "vdetr_morton_order_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vdetr_pack_chunk_floats": (c_int, []),

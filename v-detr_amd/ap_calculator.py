@@ -6,8 +6,9 @@ the empty-box test (``vdetr_box_point_count_f32``: no (B,N,K) flag tensor), the 
 three launches) and the confidence test stay on the GPU; only the kept boxes are assembled into the reference's list format
 after ONE device->host copy.  No CPU path: CPU tensors raise.
 
-``config_dict`` is the reference's (``get_ap_config_dict``, ap_calculator.py:285-321).  ``rotated_nms`` is not supported (the
-reference prints a box and then fails on an undefined ``pred_mask``).
+``config_dict`` is the reference's (``get_ap_config_dict``, ap_calculator.py:285-321).  ``rotated_nms``, which the reference
+tests first and then leaves without a ``pred_mask``, is the 3-D NMS with the rotated ``box3d_iou`` as its overlap
+(DESIGN.md 6.3).
 """
 import itertools
 
@@ -72,8 +73,9 @@ def prediction_masks(predicted_boxes, sem_cls_probs, objectness_probs, angle_pro
     keep [B,K] bool = pred_mask & (obj_prob > conf_thresh), pred_sem_cls [B,K], nonempty [B,K] bool)."""
     L.require_gpu(predicted_boxes, "predicted_boxes")
     cfg = config_dict
-    if cfg.get("rotated_nms"):
-        raise NotImplementedError("rotated_nms: the reference has no working path either (ap_calculator.py:112-113)")
+    rotated = bool(cfg.get("rotated_nms"))
+    if rotated and not cfg["use_3d_nms"]:
+        raise ValueError("rotated_nms is a 3-D NMS (box3d_iou of the rotated boxes): it cannot be combined with use_3d_nms=False")
     corners = predicted_boxes.detach().float()
     obj = objectness_probs.detach().float()
     sem = sem_cls_probs.detach().float()
@@ -85,15 +87,15 @@ def prediction_masks(predicted_boxes, sem_cls_probs, objectness_probs, angle_pro
         nonempty = nonempty_box_mask(point_cloud, predicted_boxes_CSA.detach().float(), obj, cfg["empty_pt_thre"])
     else:
         nonempty = torch.ones((B, K), dtype=torch.bool, device=obj.device)
-    if cfg.get("no_nms"):
+    if cfg.get("no_nms") and not rotated:   # the reference looks at rotated_nms first (ap_calculator.py:113-115)
         pred_mask = nonempty
     elif not cfg["use_3d_nms"]:
         pred_mask = batched_nms_3d(_plane_corners(corners), obj, None, nonempty, cfg["nms_iou"], cfg["use_old_type_nms"])
     elif not cfg["cls_nms"]:
-        pred_mask = batched_nms_3d(corners, obj, None, nonempty, cfg["nms_iou"], cfg["use_old_type_nms"])
+        pred_mask = batched_nms_3d(corners, obj, None, nonempty, cfg["nms_iou"], cfg["use_old_type_nms"], rotated)
     else:
         score = obj * angle_probs.detach().float() if cfg.get("angle_nms") else obj
-        pred_mask = batched_nms_3d(corners, score, pred_sem_cls, nonempty, cfg["nms_iou"], cfg["use_old_type_nms"])
+        pred_mask = batched_nms_3d(corners, score, pred_sem_cls, nonempty, cfg["nms_iou"], cfg["use_old_type_nms"], rotated)
     keep = pred_mask & (obj > cfg["conf_thresh"])
     return dict(pred_mask=pred_mask, keep=keep, pred_sem_cls=pred_sem_cls, nonempty=nonempty)
 

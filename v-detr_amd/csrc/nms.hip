@@ -10,6 +10,8 @@
 //      `inter / (area_i + area_j - inter) > thr` (or inter / area_j for old_type) times the class equality;
 //   3. one wave walks the boxes in score order: a box still alive is kept and ORs its row into the dead set.
 // Greedy suppression is inherently sequential in the kept boxes; the walk costs ~100 cycles per box.
+// The rotated form (vdetr_nms3d_rot_f32) replaces steps 1 and 2: the corners themselves in rank order, and
+// the relation from the reference's box3d_iou of the two boxes (nms3d_rot_relation_kernel, next to the clip routine below).
 #include "wave.h"
 
 namespace vdetr {
@@ -25,24 +27,30 @@ struct NmsParams {
   float* ext;                 // [B,K,6] extents in rank order (rank r = r-th best box: order[K-1-r])
   int* rcls;                  // [B,K] class in rank order; < 0: invalid box (matches nothing)
   unsigned long long* rel;    // [B,K,W] "rank r suppresses rank 64w+t" bits, W = ceil(K/64)
+  float* rcorn;               // [B,K,8,3] corners in rank order (rotated NMS; then ext is unused), else NULL
   int K, W, old_type;
   double thr;
 };
 
-// 1. extents + classes in rank order
+// 1. extents (or, for the rotated relation, the 24 corner floats) + classes in rank order
 __global__ __launch_bounds__(256) void nms3d_prepare_kernel(NmsParams P) {
   const int b = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x, K = P.K;
   if (r >= K) return;
   const int i = (int)P.order[(size_t)b * K + K - 1 - r];
   const float* c = P.corners + ((size_t)b * K + i) * 24;
-  float lo[3] = {c[0], c[1], c[2]}, hi[3] = {c[0], c[1], c[2]};
-  for (int k = 1; k < 8; ++k)
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = fminf(lo[a], c[k * 3 + a]);
-      hi[a] = fmaxf(hi[a], c[k * 3 + a]);
-    }
-  float* e = P.ext + ((size_t)b * K + r) * 6;
-  for (int a = 0; a < 3; ++a) e[a] = lo[a], e[3 + a] = hi[a];
+  if (P.rcorn) {  // rotated NMS: the relation needs the box itself, not its hull
+    float* o = P.rcorn + ((size_t)b * K + r) * 24;
+    for (int k = 0; k < 24; ++k) o[k] = c[k];
+  } else {
+    float lo[3] = {c[0], c[1], c[2]}, hi[3] = {c[0], c[1], c[2]};
+    for (int k = 1; k < 8; ++k)
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = fminf(lo[a], c[k * 3 + a]);
+        hi[a] = fmaxf(hi[a], c[k * 3 + a]);
+      }
+    float* e = P.ext + ((size_t)b * K + r) * 6;
+    for (int a = 0; a < 3; ++a) e[a] = lo[a], e[3 + a] = hi[a];
+  }
   const bool ok = P.valid == nullptr || P.valid[(size_t)b * K + i] != 0;
   P.rcls[(size_t)b * K + r] = ok ? (P.cls ? P.cls[(size_t)b * K + i] : 0) : -1 - r;
 }
@@ -233,15 +241,12 @@ __device__ __forceinline__ double box3d_vol64(const float* c) {
   };
   return (len(0, 1) * len(1, 2)) * len(0, 4);
 }
-__device__ double footprint_intersection(const float* c1, const float* c2) {
+// subject / clip: the two footprints as float64 (x, z) of corners 3, 2, 1, 0: counter-clockwise (box_util.py:135-136)
+__device__ double footprint_intersection(const P2* subject, const P2* clip) {
   P2 out[10], in[10];
   int n = 4;
-  P2 clip[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {  // rect = corners 3, 2, 1, 0 (x, z): counter-clockwise (box_util.py:135-136)
-    out[i] = P2{(double)c1[(3 - i) * 3], (double)c1[(3 - i) * 3 + 2]};
-    clip[i] = P2{(double)c2[(3 - i) * 3], (double)c2[(3 - i) * 3 + 2]};
-  }
+  for (int i = 0; i < 4; ++i) out[i] = subject[i];
   P2 cp1 = clip[3];
   for (int cv = 0; cv < 4; ++cv) {
     const P2 cp2 = clip[cv];
@@ -306,6 +311,16 @@ __device__ double footprint_intersection(const float* c1, const float* c2) {
   }
   return 0.5 * fabs(acc);
 }
+__device__ __forceinline__ void footprint64(const float* c, P2* rect) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) rect[i] = P2{(double)c[(3 - i) * 3], (double)c[(3 - i) * 3 + 2]};
+}
+__device__ __forceinline__ double footprint_intersection(const float* c1, const float* c2) {
+  P2 r1[4], r2[4];
+  footprint64(c1, r1);
+  footprint64(c2, r2);
+  return footprint_intersection(r1, r2);
+}
 __global__ __launch_bounds__(128) void box3d_iou_max_kernel(const float* __restrict__ pred, const int* __restrict__ pred_img,
                                                             const int* __restrict__ pred_cls, int P, const float* __restrict__ gt,
                                                             const int* __restrict__ gt_cls, const int* __restrict__ img_gt_begin,
@@ -332,6 +347,82 @@ __global__ __launch_bounds__(128) void box3d_iou_max_kernel(const float* __restr
   jmax[d] = arg;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The reference's box3d_iou for all pairs: out[a, b] = box3d_iou(corners_a[a], corners_b[b]) (box a is the subject of the
+// clip, box b the clip polygon, as in box_util.py:139).  One thread per pair.
+__global__ __launch_bounds__(128) void box3d_iou_pairs_kernel(const float* __restrict__ ca, const float* __restrict__ cb, int Na,
+                                                              int Nb, double* __restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * 128 + threadIdx.x;
+  if (e >= (size_t)Na * Nb) return;
+  const float* c1 = ca + (e / Nb) * 24;
+  const float* c2 = cb + (e % Nb) * 24;
+  float a[24], b[24];
+  for (int k = 0; k < 24; ++k) a[k] = c1[k], b[k] = c2[k];
+  const double area = footprint_intersection(a, b);
+  const double ymax = fmin((double)a[1], (double)b[1]), ymin = fmax((double)a[13], (double)b[13]);
+  const double inter_vol = area * fmax(0.0, ymax - ymin);
+  out[e] = inter_vol / ((box3d_vol64(a) + box3d_vol64(b)) - inter_vol);
+}
+
+// 2r. the rotated relation: the overlap of ranks r and s is the reference's box3d_iou(corners_r, corners_s)
+//     instead of the IoU of the two hulls.  Grid (K/64, 4W, B): ONE wave owns 64 ranks r and a quarter word (16 partners s),
+//     staged in LDS as float64 footprint, top / bottom height and volume.  The clip is ~40 doubles of polygon state with
+//     dynamic indices (private memory) and a few hundred fp64 operations, so a lane first collects the partners that pass
+//     the exact pre-tests (s > r, same class, heights overlap: otherwise inter is exactly 0 or NaN and never above a threshold
+//     >= 0) as a bit mask and then clips only those: the wave runs as many clips as its busiest lane has candidates, not 16.
+struct RotBox {
+  P2 rect[4];
+  double top, bottom, vol;
+};
+__global__ __launch_bounds__(64) void nms3d_rot_relation_kernel(NmsParams P) {
+  __shared__ RotBox sbox[kNmsQuarter];
+  __shared__ int scls[kNmsQuarter];
+  const int b = blockIdx.z, piece = blockIdx.y, K = P.K, W = P.W;
+  const int r = blockIdx.x * 64 + threadIdx.x, s0 = piece * kNmsQuarter;
+  unsigned short* out = reinterpret_cast<unsigned short*>(P.rel + (size_t)b * K * W);
+  if (s0 + kNmsQuarter - 1 <= (int)(blockIdx.x * 64) || s0 >= K) {  // every pair of this wave has s <= r
+    if (r < K) out[(size_t)r * W * 4 + piece] = 0;
+    return;
+  }
+  const float* __restrict__ rc = P.rcorn + (size_t)b * K * 24;
+  const int* __restrict__ cls = P.rcls + (size_t)b * K;
+  auto load = [&](int i, RotBox& o) {
+    float c[24];
+    for (int k = 0; k < 24; ++k) c[k] = rc[(size_t)i * 24 + k];
+    footprint64(c, o.rect);
+    o.top = (double)c[1];
+    o.bottom = (double)c[13];
+    o.vol = box3d_vol64(c);
+  };
+  if (threadIdx.x < kNmsQuarter) {
+    const int s = s0 + threadIdx.x;
+    load(min(s, K - 1), sbox[threadIdx.x]);
+    scls[threadIdx.x] = s < K ? cls[s] : -1;  // a negative class (invalid box, see prepare) matches nothing
+  }
+  __syncthreads();
+  if (r >= K) return;
+  const int cr = cls[r];
+  RotBox A;
+  load(r, A);
+  const bool always_divide = !(P.thr >= 0.0);
+  unsigned cand = 0u, bits = 0u;
+#pragma unroll
+  for (int t = 0; t < kNmsQuarter; ++t) {
+    const double h = fmax(0.0, fmin(A.top, sbox[t].top) - fmax(A.bottom, sbox[t].bottom));
+    if (s0 + t > r && scls[t] == cr && cr >= 0 && (h > 0.0 || always_divide)) cand |= 1u << t;
+  }
+  while (cand) {
+    const int t = __ffs(cand) - 1;
+    cand &= cand - 1u;
+    const RotBox& S = sbox[t];
+    const double area = footprint_intersection(A.rect, S.rect);
+    const double inter = area * fmax(0.0, fmin(A.top, S.top) - fmax(A.bottom, S.bottom));
+    const double o = P.old_type ? inter / S.vol : inter / ((A.vol + S.vol) - inter);
+    if (o > P.thr) bits |= 1u << t;
+  }
+  out[(size_t)r * W * 4 + piece] = (unsigned short)bits;
+}
+
 }  // namespace
 }  // namespace vdetr
 
@@ -345,16 +436,23 @@ extern "C" size_t vdetr_nms3d_workspace_bytes(int B, int K) {
   return nms_align((size_t)B * K * W * 8) + nms_align((size_t)B * K * 6 * 4) + nms_align((size_t)B * K * 4) + 256;
 }
 
-extern "C" int vdetr_nms3d_f32(const float* corners, const float* score, const int32_t* cls, const uint8_t* valid,
-                               const int64_t* order, int B, int K, double iou_threshold, int old_type, uint8_t* keep,
-                               void* workspace, size_t workspace_bytes, vdetr_stream_t stream) {
-  VDETR_REQUIRE(B >= 0 && K >= 0, "nms3d: negative dimension");
+extern "C" size_t vdetr_nms3d_rot_workspace_bytes(int B, int K) {
+  if (B <= 0 || K <= 0) return 0;
+  const size_t W = (K + 63) / 64;
+  return nms_align((size_t)B * K * W * 8) + nms_align((size_t)B * K * 24 * 4) + nms_align((size_t)B * K * 4) + 256;
+}
+
+static int nms3d_launch(bool rotated, const float* corners, const float* score, const int32_t* cls, const uint8_t* valid,
+                        const int64_t* order, int B, int K, double iou_threshold, int old_type, uint8_t* keep, void* workspace,
+                        size_t workspace_bytes, vdetr_stream_t stream) {
+  const char* op = rotated ? "nms3d_rot" : "nms3d";
+  VDETR_REQUIRE(B >= 0 && K >= 0, "%s: negative dimension", op);
   if (B == 0 || K == 0) return VDETR_OK;
-  VDETR_REQUIRE(corners && score && order && keep, "nms3d: null pointer");
-  VDETR_REQUIRE(K <= 4096 && B <= 65535, "nms3d: %d scenes x %d boxes: limits are 65535 x 4096", B, K);
-  const size_t need = vdetr_nms3d_workspace_bytes(B, K);
+  VDETR_REQUIRE(corners && score && order && keep, "%s: null pointer", op);
+  VDETR_REQUIRE(K <= 4096 && B <= 65535, "%s: %d scenes x %d boxes: limits are 65535 x 4096", op, B, K);
+  const size_t need = rotated ? vdetr_nms3d_rot_workspace_bytes(B, K) : vdetr_nms3d_workspace_bytes(B, K);
   if (!workspace || workspace_bytes < need) {
-    set_error("nms3d: workspace %zu B < required %zu B", workspace_bytes, need);
+    set_error("%s: workspace %zu B < required %zu B", op, workspace_bytes, need);
     return VDETR_ERR_WORKSPACE;
   }
   NmsParams P;
@@ -363,14 +461,20 @@ extern "C" int vdetr_nms3d_f32(const float* corners, const float* score, const i
   uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
   P.rel = reinterpret_cast<unsigned long long*>(base);
   base += nms_align((size_t)B * K * P.W * 8);
-  P.ext = reinterpret_cast<float*>(base);
-  base += nms_align((size_t)B * K * 6 * 4);
+  P.ext = rotated ? nullptr : reinterpret_cast<float*>(base);
+  P.rcorn = rotated ? reinterpret_cast<float*>(base) : nullptr;
+  base += nms_align((size_t)B * K * (rotated ? 24 : 6) * 4);
   P.rcls = reinterpret_cast<int*>(base);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(nms3d_prepare_kernel, dim3(ceil_div(K, 256), B), dim3(256), 0, st, P);
   if (int e = check_launch("nms3d_prepare")) return e;
-  hipLaunchKernelGGL(nms3d_relation_kernel, dim3(ceil_div(K, 256), P.W * 4, B), dim3(256), 0, st, P);
-  if (int e = check_launch("nms3d_relation")) return e;
+  if (rotated) {
+    hipLaunchKernelGGL(nms3d_rot_relation_kernel, dim3(ceil_div(K, 64), P.W * 4, B), dim3(64), 0, st, P);
+    if (int e = check_launch("nms3d_rot_relation")) return e;
+  } else {
+    hipLaunchKernelGGL(nms3d_relation_kernel, dim3(ceil_div(K, 256), P.W * 4, B), dim3(256), 0, st, P);
+    if (int e = check_launch("nms3d_relation")) return e;
+  }
   const size_t relb = (size_t)K * P.W * sizeof(unsigned long long);
   const int in_lds = relb <= 150 * 1024;
   const size_t lds = in_lds ? relb : 0;
@@ -381,6 +485,31 @@ extern "C" int vdetr_nms3d_f32(const float* corners, const float* score, const i
     hipLaunchKernelGGL(nms3d_walk_kernel<false>, dim3(B), dim3(kNmsThreads), 0, st, P);
   }
   return check_launch("nms3d_walk");
+}
+
+extern "C" int vdetr_nms3d_f32(const float* corners, const float* score, const int32_t* cls, const uint8_t* valid,
+                               const int64_t* order, int B, int K, double iou_threshold, int old_type, uint8_t* keep,
+                               void* workspace, size_t workspace_bytes, vdetr_stream_t stream) {
+  return nms3d_launch(false, corners, score, cls, valid, order, B, K, iou_threshold, old_type, keep, workspace, workspace_bytes,
+                      stream);
+}
+
+extern "C" int vdetr_nms3d_rot_f32(const float* corners, const float* score, const int32_t* cls, const uint8_t* valid,
+                                   const int64_t* order, int B, int K, double iou_threshold, int old_type, uint8_t* keep,
+                                   void* workspace, size_t workspace_bytes, vdetr_stream_t stream) {
+  return nms3d_launch(true, corners, score, cls, valid, order, B, K, iou_threshold, old_type, keep, workspace, workspace_bytes,
+                      stream);
+}
+
+extern "C" int vdetr_box3d_iou_pairs_f64(const float* corners_a, int Na, const float* corners_b, int Nb, double* out,
+                                         vdetr_stream_t stream) {
+  VDETR_REQUIRE(Na >= 0 && Nb >= 0, "box3d_iou_pairs: negative count");
+  if (Na == 0 || Nb == 0) return VDETR_OK;
+  VDETR_REQUIRE(corners_a && corners_b && out, "box3d_iou_pairs: null pointer");
+  VDETR_REQUIRE((size_t)Na * Nb <= ((size_t)1 << 30), "box3d_iou_pairs: %d x %d pairs > 2^30", Na, Nb);
+  hipLaunchKernelGGL(box3d_iou_pairs_kernel, dim3((unsigned)(((size_t)Na * Nb + 127) / 128)), dim3(128), 0, (hipStream_t)stream,
+                     corners_a, corners_b, Na, Nb, out);
+  return check_launch("box3d_iou_pairs");
 }
 
 extern "C" int vdetr_box_point_count_f32(const float* points, const float* boxes, int B, int N, int K, int32_t* counts,
