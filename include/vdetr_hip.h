@@ -40,7 +40,7 @@ typedef void* vdetr_stream_t; /* hipStream_t */
 int vdetr_abi_version(void); /* 3: vdetr_attn_desc carries the launch shape (table_grid, kv_waves, fwd_kernel, fwd_sched); the
                                 process-wide setters vdetr_attn_bwd_table_set_grid / vdetr_attn_bwd_kv_set_waves are gone */
 const char* vdetr_last_error(void);
-int vdetr_ab_switches(void); /* 1: a probe build that reads VDETR_* environment switches (once per process); 0: the shipped build, which reads none */
+int vdetr_ab_switches(void); /* always 0: the library reads no environment variable and has no probe build that would (kept for callers of ABI 3) */
 
 /* ------------------------------------------------------------------------------------------------
  * (iii) pointnet2 ops.  One symbol per function of bindings.cpp:9-22.

@@ -1,5 +1,5 @@
 """The package's environment switches are a fixed, documented set: an A/B path whose loser was never kept does not come back
-through a new VDETR_* read without this list (and INTEGRATION.md §7b) changing with it."""
+through a new VDETR_* read without this list (and INTEGRATION.md §7b) changing with it.  The native library has none at all."""
 import glob
 import os
 import re
@@ -42,3 +42,17 @@ def test_kept_switches_are_documented():
         doc = fh.read()
     missing = sorted(n for n in KEPT if not re.search(re.escape(n) + r"(?![A-Z0-9_])", doc))
     assert not missing, f"not in INTEGRATION.md: {missing}"
+
+
+def test_native_library_reads_no_environment():
+    """v-detr_amd/csrc: no getenv and no VDETR_AB(name, default) site, in code or comment: every launch decision of the library is
+    written out, and vdetr_ab_switches() returns 0 unconditionally."""
+    paths = sorted(glob.glob(os.path.join(ROOT, "v-detr_amd", "csrc", "*")))
+    assert len(paths) > 20, paths
+    hits = []
+    for path in paths:
+        with open(path, errors="replace") as fh:
+            for no, line in enumerate(fh, 1):
+                if "getenv" in line or "VDETR_AB" in line:
+                    hits.append(f"{os.path.basename(path)}:{no}: {line.strip()[:100]}")
+    assert not hits, "\n".join(hits)

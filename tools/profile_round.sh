@@ -74,7 +74,6 @@ python3 tools/op_census.py --top 60 > $out/op_census.txt 2>&1 < /dev/null
 bash tools/pmc_spconv.sh $tag > /dev/null 2>&1; cat gpurun_out/pmc_sp_$tag/pmc_sq_pass*.txt > $out/spconv_pmc_sq.txt 2>/dev/null
 # per-launch HBM bytes for bench.py's `roofline.traffic`, from THIS run's PMC passes (copy to profiles/rNN_pmc_traffic.json)
 python3 tools/pmc_traffic.py $out > $out/pmc_traffic.json 2>/dev/null
-python3 tools/fps_variants.py > $out/fps_variants.txt 2>&1 < /dev/null
 [ -x tools/probes/bin/lat_probe ] && timeout 120 tools/probes/bin/lat_probe > $out/lat_probe.txt 2>&1
 # the launcher path the driver uses for N > 1, with one rank (RCCL communicator, gradient all-reduce captured in the graph)
 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --force-dist --steps 20 --warmup 3 --no-cpu-baseline --no-criterion-leg --no-exact-leg --no-backbone-leg --no-roofline > $out/bench_torchrun_1rank.json 2> $out/bench_torchrun_1rank.err; echo "exit code $?" >> $out/bench_torchrun_1rank.err

@@ -12,11 +12,8 @@ constexpr int kRpeHeads = 4;     // the RPE lane layout carries the heads of one
 constexpr int kRpeVerts = 8;     // 8 box vertices (vdetr_transformer.py:710)
 constexpr float kNegBig = -1e30f;
 // Cache policy of the score-sized streams (S, dS: 67 MB per layer and direction at C2, twice the 32 MB of L2): `nt` keeps them
-// from evicting what the small kernels between the attention kernels re-use (weights, activations).  -DVDETR_STREAM_NT=0: off.
-#ifndef VDETR_STREAM_NT
-#define VDETR_STREAM_NT 1
-#endif
-constexpr int kStreamAux = VDETR_STREAM_NT ? 2 : 0;  // raw buffer aux bits: 2 = nt (slc)
+// from evicting what the small kernels between the attention kernels re-use (weights, activations).
+constexpr int kStreamAux = 2;  // raw buffer aux bits: 2 = nt (slc)
 
 // Table-gradient kernels, dynamic query distribution: the most queries one persistent workgroup may take, given the even share
 // `per_wg`.  The int32 histogram's fixed-point scale is sized for this many queries (a power of two below 2^30 / bound), so the

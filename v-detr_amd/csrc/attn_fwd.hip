@@ -37,16 +37,13 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 
-// -DVDETR_FWD_SPLIT=1 (build option, OFF by default): fp32 operands on the bf16 matrix unit, x = hi + lo (bf16, round-to-nearest),
+// kFwdSplit (off; it was a build option): fp32 operands on the bf16 matrix unit, x = hi + lo (bf16, round-to-nearest),
 // products as the three leading cross terms (2^-16 per product, fp32 accumulate): QK^T is 6 instructions of 16 cycles instead of
 // 16 of 32, PV 12 of 8 instead of 16 of 32 — and matrix time ADDS to VALU time on this chip.  Measured: forward
 // 176 -> 161 us, captured C2 step 9.55 -> 9.44 ms; every output stays within 1e-3 of the oracle, but scores that are off by 1e-5
 // instead of 1e-7 flip near-tie proposal selections downstream: the whole-model parity case with three ragged scenes then has 39
 // token rows of the feature gradient outside its tolerance (tests/test_gpu_model.py).  The forward keeps exact fp32 products.
-#ifndef VDETR_FWD_SPLIT
-#define VDETR_FWD_SPLIT 0
-#endif
-constexpr bool kFwdSplit = VDETR_FWD_SPLIT != 0;
+constexpr bool kFwdSplit = false;
 __device__ __forceinline__ void fwd_split8(const f32x4& x0, const f32x4& x1, bf16x8& hi, bf16x8& lo) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -243,8 +240,7 @@ __device__ __forceinline__ void attn_fwd_body(AttnParams P) {
       for (int r = 0; r < 4; ++r) {
         if (qrow[r] < nQ) {
           const size_t row = PERHEAD ? (((size_t)b * H + head) * nQ + qrow[r]) : (((size_t)b * nQ + qrow[r]) * H + r);
-          if (VDETR_STREAM_NT) __builtin_nontemporal_store(sc[r], &P.scores[row * nK + key]);  // 67 MB per layer: past L2
-          else P.scores[row * nK + key] = sc[r];
+          __builtin_nontemporal_store(sc[r], &P.scores[row * nK + key]);  // 67 MB per layer: past L2
         }
       }
     }
@@ -382,6 +378,8 @@ __global__ __launch_bounds__(4 * kWave) void attn_fwd_perhead4_kernel(AttnParams
 // The RPE attention with the instantiation chosen per workgroup IN the kernel (its 4 queries are axis-aligned boxes or not:
 // the test attn_fwd_body repeats).  Launching the two instantiations side by side cost a 1024-workgroup launch of
 // immediate exits per layer (6 us with the 133 KB LDS reservation); both bodies use the same register budget.
+// Only BF16 = false is instantiated (with bf16 operands the merged kernel spills 11 registers: vdetr_attn_fwd_bf16 launches the
+// two instantiations side by side); the parameter stays so that the kernel keeps its symbol.
 template <bool BF16>
 __global__ __launch_bounds__(kFwdThreads) void attn_fwd_rpe_auto_kernel(AttnParams P) {
   const int g = (threadIdx.x & 63) >> 4;
@@ -533,15 +531,10 @@ static int pipe_split(const vdetr_attn_desc* d) { return !pipe_eligible(d) ? 0 :
 // key split so that small query counts still fill the chip (shared kinds only)
 static int choose_ksplit(const vdetr_attn_desc* d) {
   if (d->kind != VDETR_ATTN_SHARED_KV) {
-    // per-head kind: the query self-attention launches H * nQ/16 = 256 workgroups at the model's size, i.e. exactly one
-    // per CU — two rounds whenever a CU is busy elsewhere (see below).  Two key halves per (head, query tile) instead.
-    // (measured: no gain at nQ = nK = 1024 — the 25 us workgroups are prologue / merge dominated and the combine launch
-    // costs what the second round did; kept behind VDETR_FWD_KSPLIT_PERHEAD for larger self-attentions.  Also tried: the
-    // per-head instantiation compiled for 128 VGPRs (two workgroups per CU, so that the 256 workgroups fit next to a busy
-    // CU): 27 spilled registers, 48.7 instead of 41.4 us inside the step)
-    const int ph = VDETR_AB("VDETR_FWD_KSPLIT_PERHEAD", 1);
-    const int ntiles = (d->nK + 15) / 16;
-    return (ph > 1 && ntiles >= 2 * ph * kFwdWaves) ? ph : 1;
+    // per-head kind: no key split.  Two key halves per (head, query tile) gained nothing at nQ = nK = 1024: the 25 us
+    // workgroups are prologue / merge dominated and the combine launch costs what the second round did;
+    // the four-wave workgroups below are what fills the chip next to a busy CU.
+    return 1;
   }
   const long wgs = (long)d->B * ((d->nQ + 3) / 4);
   const int ntiles = (d->nK + 15) / 16;
@@ -552,8 +545,7 @@ static int choose_ksplit(const vdetr_attn_desc* d) {
   // stream (measured: 307 us instead of 181 us per launch).  Finer workgroups let the hardware dispatcher
   // balance the load over whatever CUs are free (4.02 -> 5 rounds of 1/4 size instead of 2 of full size); the price is the
   // per-workgroup prologue + merge (~6 us) and the combine kernel.
-  const int forced = VDETR_AB("VDETR_FWD_KSPLIT", 0);
-  const int fine = forced > 0 ? forced : 4;  // step time at 1/2/4/8: 18.13 / 17.91 / 17.74 / 18.06 ms
+  const int fine = 4;  // step time at 1/2/4/8: 18.13 / 17.91 / 17.74 / 18.06 ms
   if (d->table && ks < fine && wgs >= 64) {
     while (ks < fine && ks * 2 * kFwdWaves <= ntiles) ks *= 2;
   }
@@ -643,13 +635,13 @@ static int attn_fwd_run(const vdetr_attn_desc* d, const float* q, const float* k
     VDETR_REQUIRE((size_t)d->nK * P.k_stride < (1u << 30) && (size_t)d->nK * P.v_stride < (1u << 30) && (size_t)4 * d->nK < (1u << 30),
                   "attn_fwd: nK=%d too large for the persistent forward's 32-bit tile offsets", d->nK);
     if (int e = attn_fwd_pipe_launch(P, sched, device_cu_count(), kv_img, pipe_split(d), d->kv_img != nullptr, true, st)) return e;
-  } else if (perhead && VDETR_AB("VDETR_FWD_SELF", 1) && attn_fwd_self_eligible(d, ks)) {
+  } else if (perhead && attn_fwd_self_eligible(d, ks)) {
     if (int e = attn_fwd_self_launch(P, st)) return e;  // the lean kernel of the decoder's own case (attn_fwd_self.hip)
   } else if (perhead) {
     dim3 grid((d->nQ + 15) / 16, d->H * ks, d->B);
     const long wgs = (long)grid.x * grid.y * grid.z;
-    const int four = VDETR_AB("VDETR_FWD_PERHEAD4", -1);  // -1: where the eight-wave workgroups would (almost) fill the chip or more
-    if (d->fwd_kernel != 1 && (four > 0 || (four < 0 && 10 * wgs > 9 * (long)device_cu_count()))) {  // (fwd_kernel 1: the eight-wave form, A/B)
+    // four-wave workgroups where the eight-wave ones would (almost) fill the chip or more (fwd_kernel 1: the eight-wave form, A/B)
+    if (d->fwd_kernel != 1 && 10 * wgs > 9 * (long)device_cu_count()) {
       const size_t lds4 = (size_t)4 * kWave * 24 * 4 > (size_t)4 * 16 * kPPad * 4 ? (size_t)4 * kWave * 24 * 4 : (size_t)4 * 16 * kPPad * 4;
       if (int e = set_lds(attn_fwd_perhead4_kernel, lds4, "attn_fwd")) return e;
       hipLaunchKernelGGL(attn_fwd_perhead4_kernel, grid, dim3(4 * kWave), lds4, st, P);
@@ -660,21 +652,11 @@ static int attn_fwd_run(const vdetr_attn_desc* d, const float* q, const float* k
   } else {
     dim3 grid((d->nQ + 3) / 4, ks, d->B);
     if (rpe) {
-      const int box_env = VDETR_AB("VDETR_FWD_BOX", 1);
-      const int box_rot = VDETR_AB("VDETR_FWD_BOX_ROT", 1);
-      P.box_path = box_env && (!d->cos_sin || box_rot);  // (VDETR_FWD_BOX_ROT=0: rotated boxes take the general body)
-      const int auto_env = VDETR_AB("VDETR_FWD_AUTO", 1);
-      if (P.box_path && auto_env) {  // one launch, the box / general body chosen per workgroup on the device
-        if (int e = set_lds(attn_fwd_rpe_auto_kernel<false>, lds, "attn_fwd")) return e;
-        hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<false>), grid, dim3(kFwdThreads), lds, st, P);
-      } else {
-        if (int e = set_lds(attn_fwd_kernel<false, true, false>, lds, "attn_fwd")) return e;
-        hipLaunchKernelGGL((attn_fwd_kernel<false, true, false>), grid, dim3(kFwdThreads), lds, st, P);
-        if (P.box_path) {
-          if (int e = set_lds(attn_fwd_kernel<false, true, true>, lds, "attn_fwd")) return e;
-          hipLaunchKernelGGL((attn_fwd_kernel<false, true, true>), grid, dim3(kFwdThreads), lds, st, P);
-        }
-      }
+      // one launch, the box / general body chosen per workgroup on the device; rotated boxes take the box body too
+      // (docs/DESIGN_rounds1-4.md 4.3)
+      P.box_path = true;
+      if (int e = set_lds(attn_fwd_rpe_auto_kernel<false>, lds, "attn_fwd")) return e;
+      hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<false>), grid, dim3(kFwdThreads), lds, st, P);
     } else {
       if (int e = set_lds(attn_fwd_kernel<false, false>, lds, "attn_fwd")) return e;
       hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, dim3(kFwdThreads), lds, st, P);
@@ -767,22 +749,13 @@ extern "C" int vdetr_attn_fwd_bf16(const vdetr_attn_desc* d, const void* q, cons
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((d->nQ + 3) / 4, ks, d->B);
   if (rpe) {
-    const int box_env = VDETR_AB("VDETR_FWD_BOX", 1);
-    const int box_rot = VDETR_AB("VDETR_FWD_BOX_ROT", 1);
-    P.box_path = box_env && (!d->cos_sin || box_rot);
-    // (the merged kernel of the fp32 path spills 11 registers when built for bf16 operands: opt-in only)
-    const int auto_env = VDETR_AB("VDETR_FWD_AUTO", 0);
-    if (P.box_path && auto_env == 2) {
-      if (int e = set_lds(attn_fwd_rpe_auto_kernel<true>, lds, "attn_fwd_bf16")) return e;
-      hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<true>), grid, dim3(kFwdThreads), lds, st, P);
-    } else {
-      if (int e = set_lds(attn_fwd_kernel<false, true, false, true>, lds, "attn_fwd_bf16")) return e;
-      hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true>), grid, dim3(kFwdThreads), lds, st, P);
-      if (P.box_path) {
-        if (int e = set_lds(attn_fwd_kernel<false, true, true, true>, lds, "attn_fwd_bf16")) return e;
-        hipLaunchKernelGGL((attn_fwd_kernel<false, true, true, true>), grid, dim3(kFwdThreads), lds, st, P);
-      }
-    }
+    // the general and the box instantiation side by side over the same grid (the merged kernel of the fp32 path spills 11
+    // registers when built for bf16 operands)
+    P.box_path = true;
+    if (int e = set_lds(attn_fwd_kernel<false, true, false, true>, lds, "attn_fwd_bf16")) return e;
+    hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true>), grid, dim3(kFwdThreads), lds, st, P);
+    if (int e = set_lds(attn_fwd_kernel<false, true, true, true>, lds, "attn_fwd_bf16")) return e;
+    hipLaunchKernelGGL((attn_fwd_kernel<false, true, true, true>), grid, dim3(kFwdThreads), lds, st, P);
   } else {
     if (int e = set_lds(attn_fwd_kernel<false, false, false, true>, lds, "attn_fwd_bf16")) return e;
     hipLaunchKernelGGL((attn_fwd_kernel<false, false, false, true>), grid, dim3(kFwdThreads), lds, st, P);

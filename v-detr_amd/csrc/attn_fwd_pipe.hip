@@ -303,8 +303,7 @@ __device__ __forceinline__ void pipe_tile(const AttnParams& P, const f32x4* tab,
     float* sp = A.sp + (tile << 4);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      if (VDETR_STREAM_NT) __builtin_nontemporal_store(sc[r], sp + r * nK);  // 67 MB per layer: past L2
-      else sp[r * nK] = sc[r];
+      __builtin_nontemporal_store(sc[r], sp + r * nK);  // 67 MB per layer: past L2
     }
   }
   // ---- online softmax (a row lives across the 16 lanes of a DPP row) ----------------------------------------------------

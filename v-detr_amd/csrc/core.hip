@@ -1,8 +1,6 @@
 // core.hip — error reporting + ABI version for libvdetr_hip.so.
 #include "common.h"
 
-#include <stdlib.h>
-
 #include <mutex>
 #include <unordered_map>
 
@@ -44,12 +42,6 @@ int device_cu_count() {
   }
   return n;
 }
-#ifdef VDETR_AB_SWITCHES
-int ab_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-#endif
 }  // namespace vdetr
 
 // One wave writes the device's constant-rate wall clock (100 MHz) to *slot: a timeline of a CAPTURED step without a tracer
@@ -64,11 +56,5 @@ extern "C" int vdetr_probe_timestamp(uint64_t* slot, vdetr_stream_t stream) {
 }
 
 extern "C" int vdetr_abi_version(void) { return 3; }
-extern "C" int vdetr_ab_switches(void) {
-#ifdef VDETR_AB_SWITCHES
-  return 1;
-#else
-  return 0;
-#endif
-}
+extern "C" int vdetr_ab_switches(void) { return 0; }  // the library has no environment switch left (include/vdetr_hip.h)
 extern "C" const char* vdetr_last_error(void) { return vdetr::g_err; }

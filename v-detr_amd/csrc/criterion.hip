@@ -1092,8 +1092,7 @@ extern "C" int vdetr_lsa_f64(const vdetr_lsa_batch* batch, int32_t* status, vdet
   }
   // up to 4096 columns: <= 4 columns per lane in a 1024-thread workgroup; beyond: <= 8
   const bool small = nc_cap <= 4096;
-  const int cols_per_lane = VDETR_AB("VDETR_LSA_COLS", 4);
-  const int cpl = cols_per_lane < 1 ? 1 : (cols_per_lane > 8 ? 8 : cols_per_lane);
+  constexpr int cpl = 4;  // columns per lane that size the workgroup (docs/DESIGN_rounds1-4.md 4.10)
   int threads = ((nc_cap + cpl - 1) / cpl + 63) & ~63;
   threads = threads > 1024 ? 1024 : threads;
   const size_t lds_base = (size_t)nr_cap * 8 + 64 * 8 + (size_t)nr_cap * 8 + (size_t)nc_cap * 8;  // + rbase
@@ -1105,7 +1104,7 @@ extern "C" int vdetr_lsa_f64(const vdetr_lsa_batch* batch, int32_t* status, vdet
   rc = set_lds(lsa_kernel<CPT, MAXT>, lds, "lsa");                                                                   \
   if (rc != VDETR_OK) return rc;                                                                                     \
   hipLaunchKernelGGL((lsa_kernel<CPT, MAXT>), dim3(wgs), dim3(threads), lds, (hipStream_t)stream, padded, status, nr_cap, nc_cap, cpl, cache_bytes)
-  if (small && cpl <= 4) {
+  if (small) {
     VDETR_LSA_LAUNCH(4, 1024);
   } else {
     VDETR_LSA_LAUNCH(8, 1024);

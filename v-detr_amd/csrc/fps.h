@@ -50,7 +50,7 @@ struct RowsParams {
 };
 
 struct RowsPlan {  // geometry chosen on the host for one launch
-  int waves;       // 4, 8 or 16 waves per workgroup
+  int waves;       // waves per workgroup: 16
   int bucket_pts;  // 64 points per bucket
 };
 

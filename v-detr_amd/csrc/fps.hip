@@ -87,6 +87,8 @@ __device__ __forceinline__ unsigned long long fps_clock() {
   return t;
 }
 
+// Only DEBUG = false is instantiated: the per-phase cycle counters had their last use in round 4 (docs/DESIGN_rounds1-4.md
+// 4.1); the parameter stays so that the kernel keeps its symbol and its code.
 template <bool DEBUG>
 __global__ __launch_bounds__(kFpsThreads) void fps_kernel(FpsParams Pin) {
   FpsParams P = Pin;
@@ -417,18 +419,6 @@ extern "C" int vdetr_furthest_point_sampling_f32(const float* xyz, int b, int n,
   P.xyz = xyz; P.idx = idx; P.n = n; P.m = m;
   P.nscenes = 0;
   P.ref_log2 = ref_log2_of(n); P.ref_block = 1 << P.ref_log2;
-  const bool debug = VDETR_AB("VDETR_FPS_DEBUG", 0) != 0;
-  if (debug) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fps_cyc), z, sizeof(z));
-    hipLaunchKernelGGL(fps_kernel<true>, dim3(b), dim3(kFpsThreads), 0, (hipStream_t)stream, P);
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(z, HIP_SYMBOL(g_fps_cyc), sizeof(z));
-    for (int i = 0; i < 2; ++i)
-      fprintf(stderr, "[fps debug] wave %d cycles/round: buckets %llu, wave-argmax+lds %llu, barrier wait %llu, decode %llu\n",
-              i ? 7 : 0, z[i * 4] / (m - 1), z[i * 4 + 1] / (m - 1), z[i * 4 + 2] / (m - 1), z[i * 4 + 3] / (m - 1));
-    return check_launch("furthest_point_sampling");
-  }
   hipLaunchKernelGGL(fps_kernel<false>, dim3(b), dim3(kFpsThreads), 0, (hipStream_t)stream, P);
   return check_launch("furthest_point_sampling");
 }

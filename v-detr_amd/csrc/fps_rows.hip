@@ -1,7 +1,7 @@
 // fps_rows.hip — furthest point sampling, the fast path of vdetr_furthest_point_sampling(_varlen)_f32.
 // Bit-exact with the reference's result (third_party/pointnet2/_ext_src/src/sampling_gpu.cu:73-176), like fps.hip,
 // and built on the same exact box-skip argument (see fps.hip's header); what differs is how a round's dependent
-// chain is laid out.  What the measurements behind it say (tools/probes/lat_probe.hip, tools/fps_variants.py, one CU):
+// chain is laid out.  What the measurements behind it say (tools/probes/lat_probe.hip, profiles/r03_b_fps_variants.txt, one CU):
 //   * a wave retires one instruction of this kind of code every ~8-10 cycles, dependent or not, and every TAKEN
 //     branch costs a refetch: the round is an instruction-count and control-flow problem, not a bandwidth one
 //     (an L2-resident 1 KB bucket fetch is ~300 cycles, an LDS round trip ~60, s_barrier ~25);
@@ -87,7 +87,8 @@ __device__ __forceinline__ unsigned long long rows_clock() {
 constexpr int kBP = 64;  // points per bucket: one wave-wide load
 constexpr int kKB = 4;   // buckets in flight per wave
 
-// W waves per scene, at most NS buckets per owner lane (compile-time bound of the slot loops)
+// W waves per scene, at most NS buckets per owner lane (compile-time bound of the slot loops).  Only W = 16 and DEBUG = false
+// are instantiated; both parameters stay so that the kernels keep their symbols and their code.
 template <int W, int NS, bool DEBUG>
 __global__ __launch_bounds__(W * kWave) void fps_rows_kernel(RowsParams Pin) {
   constexpr int T = W * kWave;
@@ -519,12 +520,9 @@ __global__ __launch_bounds__(W * kWave) void fps_rows_kernel(RowsParams Pin) {
 // ---- host --------------------------------------------------------------------------------------------------------
 
 bool fps_rows_plan(int nmax, RowsPlan* plan) {
-  const int env_impl = VDETR_AB("VDETR_FPS_IMPL", 0);  // 2: fps.hip's kernel always
-  const int env_waves = VDETR_AB("VDETR_FPS_WAVES", 0);
-  if (env_impl == 2 || nmax <= 0) return false;
+  if (nmax <= 0) return false;
   const long nb = ((long)nmax + kBP - 1) / kBP;
-  int waves = (env_waves == 4 || env_waves == 8 || env_waves == 16) ? env_waves : 16;
-  while (waves < 16 && nb > (long)kRowsSlots * kWave * waves) waves *= 2;
+  const int waves = 16;  // 16 waves beat 8 and 4 by 1.5x / 2x (header; docs/DESIGN_rounds1-4.md 4.1)
   if (nb > (long)kRowsSlots * kWave * waves) return false;
   plan->waves = waves;
   plan->bucket_pts = kBP;
@@ -532,20 +530,7 @@ bool fps_rows_plan(int nmax, RowsPlan* plan) {
 }
 
 template <int W, int NS>
-static int launch_rows(RowsParams& P, int b, size_t lds, bool debug, hipStream_t stream) {
-  if (debug) {
-    int rc = set_lds(fps_rows_kernel<W, NS, true>, lds, "furthest_point_sampling");
-    if (rc != VDETR_OK) return rc;
-    hipLaunchKernelGGL((fps_rows_kernel<W, NS, true>), dim3(b), dim3(W * kWave), lds, stream, P);
-    (void)hipDeviceSynchronize();
-    unsigned long long z[16][8];
-    (void)hipMemcpyFromSymbol(z, HIP_SYMBOL(g_rows_cyc), sizeof(z));
-    const unsigned long long r = P.m > 1 ? P.m - 1 : 1;
-    for (int i = 0; i < W; ++i)
-      fprintf(stderr, "[fps rows debug] W=%d NS=%d wave %2d cycles/round: test %llu batches %llu reduce %llu barrier %llu decode %llu | batches/round %.2f buckets/round %.2f\n",
-              W, NS, i, z[i][0] / r, z[i][1] / r, z[i][2] / r, z[i][3] / r, z[i][4] / r, (double)z[i][5] / (double)r, (double)z[i][6] / (double)r);
-    return check_launch("furthest_point_sampling");
-  }
+static int launch_rows(RowsParams& P, int b, size_t lds, hipStream_t stream) {
   int rc = set_lds(fps_rows_kernel<W, NS, false>, lds, "furthest_point_sampling");
   if (rc != VDETR_OK) return rc;
   hipLaunchKernelGGL((fps_rows_kernel<W, NS, false>), dim3(b), dim3(W * kWave), lds, stream, P);
@@ -553,11 +538,6 @@ static int launch_rows(RowsParams& P, int b, size_t lds, bool debug, hipStream_t
 }
 
 int fps_rows_launch(RowsParams& P, int b, const RowsPlan& pl, hipStream_t stream) {
-  const bool debug = VDETR_AB("VDETR_FPS_DEBUG", 0) != 0;
-  // VDETR_FPS_TREE: 0 = runs of 64 sorted points always; 1 (default) = tree leaves in the slots the runs need (a
-  // second slot per owner lane costs more in the box test than the tighter boxes win: 4.92 vs 4.28 ms at 40k points);
-  // 2 = room for 2 n / 64 + 64 leaves
-  const int env_tree = VDETR_AB("VDETR_FPS_TREE", 1);
   long capmax = 0, runmax = 0;
   for (int i = 0; i < b; ++i) {
     const long runs = ((long)P.scenes[i].n + kBP - 1) / kBP;
@@ -568,8 +548,9 @@ int fps_rows_launch(RowsParams& P, int b, const RowsPlan& pl, hipStream_t stream
   for (int i = 0; i < b; ++i) {
     const long runs = ((long)P.scenes[i].n + kBP - 1) / kBP;
     long cap = fps_rows_cap(P.scenes[i].n, pl.waves);  // what the workspace holds
-    if (env_tree == 0) cap = 0;
-    else if (env_tree == 1) cap = cap < run_slots ? cap : run_slots;
+    // tree leaves only in the slots the runs need: a second slot per owner lane costs more in the box test than the
+    // tighter boxes win (4.92 vs 4.28 ms at 40k points)
+    cap = cap < run_slots ? cap : run_slots;
     P.scenes[i].cap_buckets = (int)cap;
     const long most = cap > runs ? cap : runs;
     capmax = capmax > most ? capmax : most;
@@ -577,20 +558,13 @@ int fps_rows_launch(RowsParams& P, int b, const RowsPlan& pl, hipStream_t stream
   size_t lds = (size_t)(kRowsHistWords + kRowsCells) * sizeof(int);
   if ((size_t)capmax * sizeof(float4) > lds) lds = (size_t)capmax * sizeof(float4);
   const int ns = (int)((capmax + per_slot - 1) / per_slot);
-  switch (pl.waves) {
-    case 16:
-      if (ns <= 1) return launch_rows<16, 1>(P, b, lds, debug, stream);
-      if (ns <= 2) return launch_rows<16, 2>(P, b, lds, debug, stream);
-      return launch_rows<16, 4>(P, b, lds, debug, stream);
-    case 8:
-      if (ns <= 2) return launch_rows<8, 2>(P, b, lds, debug, stream);
-      return launch_rows<8, 4>(P, b, lds, debug, stream);
-    case 4:
-      if (ns <= 2) return launch_rows<4, 2>(P, b, lds, debug, stream);
-      return launch_rows<4, 4>(P, b, lds, debug, stream);
+  if (pl.waves != 16) {
+    set_error("furthest_point_sampling: no kernel for %d waves", pl.waves);
+    return VDETR_ERR_ARG;
   }
-  set_error("furthest_point_sampling: no kernel for %d waves", pl.waves);
-  return VDETR_ERR_ARG;
+  if (ns <= 1) return launch_rows<16, 1>(P, b, lds, stream);
+  if (ns <= 2) return launch_rows<16, 2>(P, b, lds, stream);
+  return launch_rows<16, 4>(P, b, lds, stream);
 }
 
 }  // namespace vdetr

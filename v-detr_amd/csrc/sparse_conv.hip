@@ -27,10 +27,6 @@ namespace vdetr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef VDETR_SP_PROBE
-#define VDETR_SP_PROBE 0  // measurements only.  1: operands loaded once (MFMA loop alone), 2: loads alone (folded with adds)
-#endif
-
 constexpr long long kKeyBias = 32768;
 
 __device__ __forceinline__ long long sp_key_add(long long key, int dx, int dy, int dz, bool& ok) {
@@ -156,10 +152,7 @@ __global__ __launch_bounds__(256) void sp_gather_kernel(const float* __restrict_
     // Eight offsets at a time: their map entries are loaded together, then their rows — an index -> row chain per offset
     // (27 dependent round trips per thread) left the kernel latency-bound at 3.4 TB/s.  The additions keep the offset order:
     // deterministic sums.
-#ifndef VDETR_SP_GATHER_G
-#define VDETR_SP_GATHER_G 8
-#endif
-    constexpr int G = VDETR_SP_GATHER_G;
+    constexpr int G = 8;
     for (int k0 = 0; k0 < K; k0 += G) {
       int u[G];
 #pragma unroll
@@ -248,11 +241,9 @@ namespace vdetr {
 // tiles [ntiles][3] = (offset k, first pair, pair count <= 128)
 constexpr int kSpTileM = 128;
 
-#ifndef VDETR_SP_WAVES
-#define VDETR_SP_WAVES 2  // waves per SIMD of the matrix-core kernels (more than 2 halves the MFMA rate)
-#endif
+constexpr int kSpWavesPerSimd = 2;  // of the matrix-core kernels (docs/DESIGN_rounds1-4.md §4.12: more than 2 halves the MFMA rate)
 template <bool TRANS, int WR, int WC, int RT, int CT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, VDETR_SP_WAVES))) void sp_pairs_gemm_kernel(const float* __restrict__ X, const int* __restrict__ arow,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, kSpWavesPerSimd))) void sp_pairs_gemm_kernel(const float* __restrict__ X, const int* __restrict__ arow,
                                                            const float* __restrict__ W, const int* __restrict__ tiles,
                                                            int CA, int CB, int wk_stride, float* __restrict__ Y) {
   // CA = contraction width (row length of X), CB = output width.  W[k] is [Cin][Cout] row-major; !TRANS: CA = Cin, CB = Cout,
@@ -287,35 +278,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, VDETR_SP
   for (int kc = 0; kc < CA; kc += 16) {
     f32x4 a[RT];
     float b[CT][4];
-    const int kl = (VDETR_SP_PROBE == 1 || VDETR_SP_PROBE == 3) ? 0 : kc;
-    if (VDETR_SP_PROBE == 3) asm volatile("" ::: "memory");  // 3: the loads stay in the loop but always hit the same lines
 #pragma unroll
-    for (int i = 0; i < RT; ++i) a[i] = *reinterpret_cast<const f32x4*>(xrow[i] + kl);
+    for (int i = 0; i < RT; ++i) a[i] = *reinterpret_cast<const f32x4*>(xrow[i] + kc);
 #pragma unroll
     for (int t = 0; t < CT; ++t) {
       if (TRANS) {  // W[k][n][kc + 4g .. +3]: one float4
-        const f32x4 v = *reinterpret_cast<const f32x4*>(wcol[t] + kl);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(wcol[t] + kc);
         b[t][0] = v[0]; b[t][1] = v[1]; b[t][2] = v[2]; b[t][3] = v[3];
       } else {      // W[k][kc + 4g + s][n]
 #pragma unroll
-        for (int s = 0; s < 4; ++s) b[t][s] = wcol[t][(size_t)(kl + s) * CB];
+        for (int s = 0; s < 4; ++s) b[t][s] = wcol[t][(size_t)(kc + s) * CB];
       }
     }
-#if VDETR_SP_PROBE == 2
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int t = 0; t < CT; ++t) acc[i][t][s] += a[i][s] + b[t][s];
-#else
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
       for (int i = 0; i < RT; ++i)
 #pragma unroll
         for (int t = 0; t < CT; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][s], b[t][s], acc[i][t], 0, 0, 0);
-#endif
   }
   // accumulator: lane (g, c) holds rows 4 g + r, column c of every 16 x 16 tile
 #pragma unroll
@@ -364,7 +344,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, (KSUB ==
     int ntiles, int CA, int CB, int wk_stride, float* __restrict__ Y, int* __restrict__ ticket) {
   constexpr int RT = 4, CT = 4;
   static_assert(!SPLIT || KSUB == 2, "the split-bf16 form contracts 32 channels per step");
-  // ticket != NULL (default; VDETR_SP_TICKET=0 for the static stride): work items are handed out by a device counter (the first
+  // ticket != NULL (what the host always passes; NULL = a static stride of the grid): work items are handed out by a device counter (the first
   // gridDim.x statically), so that a CU busy with another stream's long kernel — the next scene's 9 ms sampling — takes no
   // items instead of making its workgroup start a round late: worth 1.1-2 ms of 26.7 in the training step.  (Tried: every
   // WAVE drawing 64 x 64 quadrants on its own, no LDS / barrier — the four quadrants of an item then run on four CUs and their
@@ -417,9 +397,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, (KSUB ==
     }
   };
   auto load_ops = [&](const unsigned (&xo)[RT], rsrc_t rW, int kc0, f32x4 (&a)[KSUB][RT], f32x4 (&b)[KSUB][CT]) {
-#if defined(VDETR_SP_PROBE) && (VDETR_SP_PROBE == 1 || VDETR_SP_PROBE == 3)
-    kc0 = 0;  // measurements only: every K-step reads the same (cache-resident) operands
-#endif
 #pragma unroll
     for (int u = 0; u < KSUB; ++u) {
       const int kc = kc0 + 16 * u;
@@ -539,7 +516,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, (KSUB ==
 // channels) in LDS (float4 per thread, rows of >= 256 B: coalesced), double-buffered, and the waves read their MFMA operands
 // from there (a pair is one k-slot: A[m = ci][k] = X[pair][ci], B[k][n = co] = dY[pair][co]).
 template <int WR, int WC, int RT, int CT, int SB, bool SPLIT = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, VDETR_SP_WAVES))) void sp_pairs_wgrad_kernel(const float* __restrict__ X, const float* __restrict__ dY,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, kSpWavesPerSimd))) void sp_pairs_wgrad_kernel(const float* __restrict__ X, const float* __restrict__ dY,
                                                             const int* __restrict__ pin, const int* __restrict__ pout,
                                                             const int* __restrict__ chunks, int Cin, int Cout,
                                                             float* __restrict__ part) {
@@ -702,16 +679,6 @@ extern "C" int vdetr_sp_pairs_gemm_f32(const float* x, const int32_t* arow, cons
   const int CA = transposed ? cout : cin, CB = transposed ? cin : cout;
   VDETR_REQUIRE(CA % 16 == 0, "sp_pairs_gemm: contraction width %d must be a multiple of 16", CA);
   hipStream_t st = (hipStream_t)stream;
-#ifdef VDETR_SP_PADTEST
-  const int pad = VDETR_AB("VDETR_SP_LDS_PAD", 0);  // unused LDS: caps the workgroups per CU
-  if (pad > 0) {
-    dim3 grid(ntiles, ceil_div(CB, 128));
-    auto kern = transposed ? sp_pairs_gemm_kernel<true, 2, 2, 4, 4> : sp_pairs_gemm_kernel<false, 2, 2, 4, 4>;
-    if (set_lds(kern, pad, "sp_pairs_gemm") != VDETR_OK) return VDETR_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, grid, dim3(256), pad, st, x, arow, w, tiles, CA, CB, cin * cout, y);
-    return check_launch("sp_pairs_gemm");
-  }
-#endif
   if (CB <= 64) {  // narrow output: 128 x 64 tiles
     dim3 grid(ntiles, ceil_div(CB, 64));
     if (transposed)
@@ -719,11 +686,10 @@ extern "C" int vdetr_sp_pairs_gemm_f32(const float* x, const int32_t* arow, cons
     else
       hipLaunchKernelGGL((sp_pairs_gemm_kernel<false, 4, 1, 2, 4>), grid, dim3(256), 0, st, x, arow, w, tiles, CA, CB, cin * cout, y);
   } else {
-    // persistent = 2 (default): one workgroup per CU, K-steps of 32 (the next 32 x (A, B) operands in flight under 128 MFMAs =
-    // 1.7 us: covers a row fetched from HBM); 1: two workgroups per CU, K-steps of 16; 0: the plain kernel.  A/B switch.
-    const int persistent = VDETR_AB("VDETR_SP_PERSISTENT", 2);
-    const int ksub = persistent == 2 && CA % 64 == 0 ? 2 : 1;
-    if (persistent && CA % 32 == 0) {
+    // the persistent kernel wherever the contraction allows it, with K-steps of 32 where it is a multiple of 64 channels (the next
+    // 32 x (A, B) operands in flight under the MFMAs cover a row fetched from HBM; docs/DESIGN_rounds1-4.md §4.12)
+    const int ksub = CA % 64 == 0 ? 2 : 1;
+    if (CA % 32 == 0) {
       // per-device state (CU count, work-counter ring), created under a lock on the device's first launch: a process may
       // drive several GPUs from several threads
       struct DevState { int cus = 0; int* ring = nullptr; std::atomic<unsigned> next{0}; };
@@ -740,46 +706,37 @@ extern "C" int vdetr_sp_pairs_gemm_f32(const float* x, const int32_t* arow, cons
         }
       }
       const int cus = D.cus;
-      // workgroups per CU: the fp32 K-step of 32 is 1.7 us of MFMA (covers a gathered row's latency with one workgroup);
-      // the split-bf16 one is 0.4 us: two workgroups keep twice the loads in flight (VDETR_SP_PER_CU overrides)
-      const int split_pc = VDETR_AB("VDETR_SP_SPLIT", 1);
-      const int per_cu_env = VDETR_AB("VDETR_SP_PER_CU", 0);
-      const int per_cu = per_cu_env > 0 ? per_cu_env : (ksub == 2 && !split_pc ? 1 : 2);
+      // two workgroups per CU: a split-bf16 K-step of 32 is 0.4 us of MFMA and an fp32 one of 16 is 0.85 us, against the 1.7 us
+      // that cover a gathered row's latency: two workgroups keep twice the loads in flight
+      constexpr int per_cu = 2;
       const int nwork = ntiles * ceil_div(CB, 128);
-      // `spare` CUs are left to whatever else is running (A/B switch): with a grid of exactly one workgroup per CU, a CU that is
-      // busy with another stream's long kernel (the next scene's 9 ms sampling) makes its workgroup start a round late
-      const int spare = VDETR_AB("VDETR_SP_SPARE_CUS", 0);
-      const int slots = per_cu * (cus - spare) > 0 ? per_cu * (cus - spare) : 1;
+      const int slots = per_cu * cus > 0 ? per_cu * cus : 1;
       dim3 grid(nwork < slots ? nwork : slots);
-      // VDETR_SP_SPLIT=0: exact fp32 products (v_mfma_f32_16x16x4_f32) everywhere; default: split-bf16 products where the
-      // contraction is a multiple of 64 channels (the wide layers, which hold the time)
-      const int split = VDETR_AB("VDETR_SP_SPLIT", 1);
-      auto kern = ksub == 2 ? (split ? (transposed ? sp_pairs_gemm_persistent_kernel<true, 2, true> : sp_pairs_gemm_persistent_kernel<false, 2, true>)
-                                     : (transposed ? sp_pairs_gemm_persistent_kernel<true, 2> : sp_pairs_gemm_persistent_kernel<false, 2>))
+      // split-bf16 products where the contraction is a multiple of 64 channels (the wide layers, which hold the time), exact
+      // fp32 products (v_mfma_f32_16x16x4_f32) elsewhere (docs/DESIGN_rounds1-4.md §4.12, round 3)
+      auto kern = ksub == 2 ? (transposed ? sp_pairs_gemm_persistent_kernel<true, 2, true> : sp_pairs_gemm_persistent_kernel<false, 2, true>)
                             : (transposed ? sp_pairs_gemm_persistent_kernel<true, 1> : sp_pairs_gemm_persistent_kernel<false, 1>);
-      int* ticket = nullptr;
-      const int use_ticket = VDETR_AB("VDETR_SP_TICKET", 1);  // A/B switch
-      if (use_ticket) {  // a (work counter, exit counter) pair per launch out of a ring: launches of different streams may overlap
-        constexpr unsigned kRing = 4096;
-        if (!D.ring) {  // zeroed once; every launch leaves its pair zeroed again (the kernel's last workgroup resets it)
-          std::lock_guard<std::mutex> lock(dev_mu);
-          if (!D.ring) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-              set_error("sp_pairs_gemm: the first launch on a device allocates its work counters and cannot be captured into a "
-                        "hipGraph: run the layer once eagerly first");
-              return VDETR_ERR_LAUNCH;
-            }
-            int* r = nullptr;
-            if (hipMalloc(&r, 2 * kRing * sizeof(int)) != hipSuccess || hipMemset(r, 0, 2 * kRing * sizeof(int)) != hipSuccess) {
-              set_error("sp_pairs_gemm: cannot allocate the work counters");
-              return VDETR_ERR_LAUNCH;
-            }
-            D.ring = r;
+      // a (work counter, exit counter) pair per launch out of a ring: launches of different streams may overlap.  (The static
+      // stride lost 1.1-2 ms of the training step next to the sampling kernel: sp_pairs_gemm_persistent_kernel.)
+      constexpr unsigned kRing = 4096;
+      if (!D.ring) {  // zeroed once; every launch leaves its pair zeroed again (the kernel's last workgroup resets it)
+        std::lock_guard<std::mutex> lock(dev_mu);
+        if (!D.ring) {
+          hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+          if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+            set_error("sp_pairs_gemm: the first launch on a device allocates its work counters and cannot be captured into a "
+                      "hipGraph: run the layer once eagerly first");
+            return VDETR_ERR_LAUNCH;
           }
+          int* r = nullptr;
+          if (hipMalloc(&r, 2 * kRing * sizeof(int)) != hipSuccess || hipMemset(r, 0, 2 * kRing * sizeof(int)) != hipSuccess) {
+            set_error("sp_pairs_gemm: cannot allocate the work counters");
+            return VDETR_ERR_LAUNCH;
+          }
+          D.ring = r;
         }
-        ticket = D.ring + 2 * (D.next.fetch_add(1) % kRing);
       }
+      int* ticket = D.ring + 2 * (D.next.fetch_add(1) % kRing);
       hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, x, arow, w, tiles, ntiles, CA, CB, cin * cout, y, ticket);
       return check_launch("sp_pairs_gemm");
     }
@@ -802,16 +759,9 @@ extern "C" int vdetr_sp_pairs_wgrad_f32(const float* x, const float* dy, const i
   VDETR_REQUIRE(cin % 4 == 0 && cout % 4 == 0, "sp_pairs_wgrad: channel counts must be multiples of 4 (float4 rows)");
   if (cin >= 128 && cout >= 128) {
     dim3 grid(nchunks, ceil_div(cin, 128), ceil_div(cout, 128));
-#ifndef VDETR_SP_WGRAD_SB
-#define VDETR_SP_WGRAD_SB 16
-#endif
-    const int split = VDETR_AB("VDETR_SP_SPLIT", 1);
-    if (split)
-      hipLaunchKernelGGL((sp_pairs_wgrad_kernel<2, 2, 4, 4, 32, true>), grid, dim3(256), 0, (hipStream_t)stream, x, dy, pin, pout,
-                         chunks, cin, cout, partials);
-    else
-      hipLaunchKernelGGL((sp_pairs_wgrad_kernel<2, 2, 4, 4, VDETR_SP_WGRAD_SB>), grid, dim3(256), 0, (hipStream_t)stream, x, dy, pin,
-                         pout, chunks, cin, cout, partials);
+    // split-bf16 products, 32 pairs per matrix instruction (docs/DESIGN_rounds1-4.md §4.12, round 3)
+    hipLaunchKernelGGL((sp_pairs_wgrad_kernel<2, 2, 4, 4, 32, true>), grid, dim3(256), 0, (hipStream_t)stream, x, dy, pin, pout,
+                       chunks, cin, cout, partials);
   } else {
     dim3 grid(nchunks, ceil_div(cin, 64), ceil_div(cout, 64));
     hipLaunchKernelGGL((sp_pairs_wgrad_kernel<4, 1, 1, 4, 32>), grid, dim3(256), 0, (hipStream_t)stream, x, dy, pin, pout, chunks,
