@@ -861,6 +861,58 @@ int vdetr_match_cost_ext_batch_f32(const vdetr_match_desc* descs, const vdetr_io
 int vdetr_set_loss_ext_batch_f32(const vdetr_setloss_desc* descs, const vdetr_iou_ext* exts, int n, vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Scene preparation (reference datasets/scannet.py:510-626, ScannetDetectionDataset.__getitem__ after the
+ * scan is loaded): flip / rotate / translate / scale a ragged batch of clouds and their axis-aligned boxes, take the
+ * clouds' bounds and build the criterion's gt_* tensors.  Two launches, no host round trip: the point kernel (one workgroup
+ * per scene-aligned tile of VDETR_SCENE_PREP_TILE kept rows) writes the packed cloud and one min / max partial per tile into
+ * the workspace; the target kernel (one workgroup per scene) merges them and writes every target.
+ * Precision model, as numpy on the reference's dtypes: a cloud is float32; rotation and translation (fp64 array operands) are
+ * done in fp64 and rounded back to float32 each, the scale (a Python float there) is a float32 product with the scale
+ * rounded to float32; the boxes turn fp64 at the rotation and stay so up to the outputs; the
+ * normalisations run in float32; the corners are the fp64 sum of float32 half sizes and centres.
+ * ---------------------------------------------------------------------------------------------- */
+#define VDETR_SCENE_PREP_TILE 256
+#define VDETR_SCENE_PREP_PARAMS 8 /* doubles per scene: flip_x, flip_y (0 / 1), cos, sin of the angle, trans xyz, scale */
+#define VDETR_COLOR_KEEP 0        /* columns 3:6 are copied */
+#define VDETR_COLOR_MEAN 1        /* (rgb - (109.8, 97.2, 83.8)) / 256.0 in fp64 (scannet.py:454) */
+#define VDETR_COLOR_UNIT 2        /* rgb / 255.0 - 0.5 in float32 (scannet.py:456) */
+typedef struct vdetr_scene_prep_desc {
+  int32_t B;            /* scenes (<= 4096) */
+  int32_t C;            /* feature columns after xyz: a row is 3 + C floats; columns past the colours are copied */
+  int32_t G;            /* box slots of the input (<= max_obj) */
+  int32_t max_obj;      /* rows of every target (MAX_NUM_OBJ) */
+  int32_t num_points;   /* > 0: `choices` is given and every scene keeps num_points rows; 0: every scene keeps all its rows */
+  int32_t color_mode;   /* VDETR_COLOR_*; MEAN / UNIT need C >= 3 */
+  int32_t num_classes;  /* rows of mean_size */
+  int32_t choices_i64;  /* `choices` holds int64 (1) or int32 (0) */
+  const float* points;      /* [offsets[B], 3+C] */
+  const int32_t* offsets;   /* [B+1] DEVICE copy of the host offsets the entry points are given */
+  const void* choices;      /* [B, num_points] row of the scene that output row j copies (repeats allowed), or NULL */
+  const double* params;     /* [B, VDETR_SCENE_PREP_PARAMS] */
+  const float* boxes;       /* [B, G, 6] centre, size; slots >= box_counts[b] are not read */
+  const int64_t* box_counts;  /* [B] */
+  const int64_t* box_classes; /* [B, G] class index of every present box */
+  const double* mean_size;  /* [num_classes, 3] */
+  float* out_points;        /* packed [kept rows, 3+C]: scene b starts at row b * num_points, or offsets[b] */
+  float *dims_min, *dims_max;          /* [B,3] bounds of the kept, augmented float32 xyz */
+  float* corners;                      /* [B,max_obj,8,3] camera frame */
+  float *centers, *centers_norm;       /* [B,max_obj,3] */
+  float *sizes, *sizes_norm, *size_residual; /* [B,max_obj,3] */
+  int64_t *angle_class, *sem_cls;      /* [B,max_obj] */
+  float *angle_residual, *angles, *present;  /* [B,max_obj] */
+} vdetr_scene_prep_desc;
+/* offsets_host: the B+1 row offsets as a HOST array, read at call time (the grid is sized from them); a scene without rows
+ * is an argument error.  The workspace holds 6 floats per tile.  vdetr_scene_prep_points_f32 reads points / offsets /
+ * choices / params and writes out_points and the workspace; vdetr_scene_prep_targets_f32 reads that workspace (same
+ * offsets_host, same stream or ordered after it) and writes dims_* and the targets.  A choice outside its scene poisons
+ * its output row with NaN instead of reading out of bounds. */
+size_t vdetr_scene_prep_workspace_bytes(const int32_t* offsets_host, int B, int num_points);
+int vdetr_scene_prep_points_f32(const vdetr_scene_prep_desc* desc, const int32_t* offsets_host, void* workspace,
+                                size_t workspace_bytes, vdetr_stream_t stream);
+int vdetr_scene_prep_targets_f32(const vdetr_scene_prep_desc* desc, const int32_t* offsets_host, const void* workspace,
+                                 size_t workspace_bytes, vdetr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Greedy 3-D NMS of a scene's predictions (reference utils/nms.py:78-162 nms_3d_faster /
  * nms_3d_faster_samecls as called from utils/ap_calculator.py:165-220 on the min / max extents of the 8 box corners).
  * corners (B,K,8,3) f32, score (B,K) f32, cls (B,K) i32 or NULL (class-agnostic nms_3d_faster), valid (B,K) u8 or NULL

@@ -1,0 +1,205 @@
+"""GPU: the scene preparation (v-detr_amd/scene_prep.py -> csrc/scene_prep.hip) against the fixture made by the
+reference's own loader (tests/golden/scene_prep.npz) and against the numpy restatement at sizes the fixture does not hold.
+
+Labels, gt_box_present and the angle tensors are decisions or constants: identical.  Points, bounds and the float targets:
+the larger of 2 float32 ulps of the reference value and 1e-9 absolute.  Why: the one step whose fp64 result may differ from
+numpy's is the 3-term dot of the rotation (summation order, FMA in the BLAS), by a few 1e-16 relative to its operands; rounded
+to float32 that is at most 1 ulp, and the two float32-rounded steps that follow (translation, scale) can double it; the floor
+covers results that cancel to near zero.  With a zero angle every product of the dot is exact, and the device has to equal
+the restatement in every value."""
+import numpy as np
+import pytest
+import torch
+
+import scene_prep_restatement as SR
+from test_scene_prep_restatement import CASES, golden, params_of, same_bits
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+FLOATS, EXACT = SR.FLOAT_KEYS, SR.EXACT_KEYS
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def cfg():
+    from vdetr_amd.dataset_config import ScannetDatasetConfig
+    return ScannetDatasetConfig()
+
+
+def run(c, params=None, **kw):
+    """a case dictionary (the fixture's keys) through prepare_scenes -> numpy dict, ``point_clouds`` concatenated"""
+    from vdetr_amd.scene_prep import prepare_scenes
+    if "color_mean" not in kw and "use_color" in c:
+        kw["color_mean"] = float(c["color_mean"]) if bool(c["use_color"]) else None
+    out = prepare_scenes(dev(c["points"]), c["offsets"], dev(c["boxes"]), dev(c["box_counts"]), dev(c["box_classes"]),
+                         params or params_of(c), cfg(), choices=c.get("choices"), **kw)
+    got = {k: v.cpu().numpy() for k, v in out.items() if k != "point_clouds"}
+    got["sizes"] = [len(p) for p in out["point_clouds"]]
+    got["out_points"] = torch.cat(out["point_clouds"]).cpu().numpy()
+    return got
+
+
+def worst(got, want):
+    """largest float32-ulp difference over points, bounds and float targets (values below the absolute floor count as 0)"""
+    w = 0.0
+    for k in FLOATS + ("out_points",):
+        u = SR.ulps(got[k], want[k])
+        u[np.abs(got[k].astype(np.float64) - want[k].astype(np.float64)) <= 1e-9] = 0
+        w = max(w, float(u.max()) if u.size else 0.0)
+    return w
+
+
+def assert_close(got, want, what):
+    for k in EXACT:
+        assert same_bits(got[k], want[k]), (what, k)
+    print(f"{what}: largest difference {worst(got, want):.2f} float32 ulps")
+    for k in FLOATS + ("out_points",):
+        assert SR.within(got[k], want[k]), (what, k, float(SR.ulps(got[k], want[k]).max()))
+
+
+def assert_same(got, want, what):
+    for k in EXACT + FLOATS + ("out_points",):
+        assert same_bits(got[k], want[k]), (what, k)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_device_matches_the_reference_fixture(name):
+    c = golden()[name]
+    got = run(c)
+    assert got["sizes"] == np.diff(c["out_offsets"]).tolist()
+    assert_close(got, c, name)
+    for k in EXACT + FLOATS:
+        assert got[k].dtype == c[k].dtype and got[k].shape == c[k].shape, k
+    if name == "eval":                                               # nothing is turned: every value is the reference's
+        assert_same(got, c, name)
+
+
+def random_case(seed, sizes, G, counts, C=0, angle=True, trans=True, scale=True):
+    from vdetr_amd.scene_prep import AugmentParams
+    rng = np.random.default_rng(seed)
+    B = len(sizes)
+    c = {"points": rng.uniform([-4, -3, 0] + [0] * C, [4, 3, 3] + [255] * C, (sum(sizes), 3 + C)).astype(np.float32),
+         "offsets": np.cumsum([0] + list(sizes)).astype(np.int32),
+         "boxes": np.concatenate([rng.uniform([-4, -3, 0], [4, 3, 3], (B, G, 3)), rng.uniform(0.2, 2.0, (B, G, 3))], 2).astype(np.float32),
+         "box_counts": np.array(counts, np.int64), "box_classes": rng.integers(0, 18, (B, G))}
+    p = AugmentParams(rng.random(B) > 0.5, rng.random(B) > 0.5, rng.uniform(-0.09, 0.09, B) if angle else np.zeros(B),
+                      rng.uniform(-0.4, 0.4, (B, 3)) if trans else np.zeros((B, 3)), rng.uniform(0.6, 1.4, B) if scale else np.ones(B))
+    return c, p
+
+
+def restate(c, p, **kw):
+    with np.errstate(all="ignore"):
+        want = SR.prepare_batch(c["points"], c["offsets"], c["boxes"], c["box_counts"], c["box_classes"], p, cfg().mean_size_arr,
+                                choices=c.get("choices"), **kw)
+    want["out_points"] = np.concatenate(want["point_clouds"])
+    return want
+
+
+@pytest.mark.parametrize("seed,sizes,G,counts", [(1, (1, 63, 64, 65), 64, (64, 0, 1, 33)), (2, (1023, 1025, 20000, 1), 1, (1, 0, 1, 1)),
+                                                 (3, (65, 20000, 1023, 64), 0, (0, 0, 0, 0)), (4, (1025, 63, 1, 1023), 64, (5, 64, 0, 17))])
+def test_sizes_against_the_restatement(seed, sizes, G, counts):
+    """scene sizes around the 256-row tile and the 64-lane wave, single points, more tiles than lanes; 0, 1 and 64 box slots"""
+    c, p = random_case(seed, sizes, G, counts)
+    assert p.flip_x.any() or p.flip_y.any()
+    got, want = run(c, p), restate(c, p)
+    assert got["sizes"] == list(sizes)
+    assert_close(got, want, f"sizes {sizes} G {G}")
+
+
+@pytest.mark.parametrize("seed,C,color_mean", [(5, 0, None), (6, 3, -1.0), (7, 4, 0.5)])
+def test_zero_angle_is_exact(seed, C, color_mean):
+    """rot_angle = 0 with flips, translation and scale: every product of the dot is exact, so points, bounds and all targets
+    equal the restatement's; also through ``choices`` and with a feature column past the colours"""
+    c, p = random_case(seed, (1, 257, 64, 3000), 64, (64, 0, 7, 1), C=C, angle=False)
+    assert (p.flip_x | p.flip_y).any() and not (p.flip_x & p.flip_y).all()
+    assert_same(run(c, p, color_mean=color_mean), restate(c, p, color_mean=color_mean), "zero angle")
+    rng = np.random.default_rng(seed)
+    c["choices"] = np.stack([rng.integers(0, n, 300) for n in np.diff(c["offsets"])]).astype(np.int32 if seed % 2 else np.int64)
+    got = run(c, p, color_mean=color_mean)
+    assert got["sizes"] == [300] * 4
+    assert_same(got, restate(c, p, color_mean=color_mean), "zero angle, choices")
+
+
+def test_bounds_are_the_extremes_of_the_returned_points():
+    from vdetr_amd.scene_prep import prepare_scenes
+    c, p = random_case(8, (1, 255, 256, 257, 20000), 3, (1, 2, 3, 0, 1))
+    for choices in (None, np.random.default_rng(0).integers(0, 1, (5, 513))):       # every choice is row 0: one point kept
+        out = prepare_scenes(dev(c["points"]), c["offsets"], dev(c["boxes"]), dev(c["box_counts"]), dev(c["box_classes"]), p, cfg(),
+                             choices=choices)
+        for b, cloud in enumerate(out["point_clouds"]):
+            assert torch.equal(out["point_cloud_dims_min"][b], cloud[:, :3].min(0)[0])
+            assert torch.equal(out["point_cloud_dims_max"][b], cloud[:, :3].max(0)[0])
+        if choices is not None:
+            assert torch.equal(out["point_cloud_dims_min"], out["point_cloud_dims_max"])
+
+
+def test_two_calls_are_identical_and_a_side_stream_changes_nothing():
+    c, p = random_case(9, (5000, 1, 700), 64, (40, 64, 0), C=3)
+    first, second = run(c, p, color_mean=-1.0), run(c, p, color_mean=-1.0)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        third = run(c, p, color_mean=-1.0)
+    for k in EXACT + FLOATS + ("out_points",):
+        assert first[k].tobytes() == second[k].tobytes() == third[k].tobytes(), k
+
+
+def test_criterion_on_prepared_targets_equals_the_fixture_targets():
+    """the device SetCriterion on fixed random outputs: targets from prepare_scenes against the fixture's own, uploaded"""
+    from oracle.make_golden import synthetic_stage
+    from vdetr_amd.criterion import build_criterion, default_criterion_args
+    from vdetr_amd.scene_prep import TARGET_KEYS, prepare_scenes
+    c = golden()["aug_noratio"]
+    out = prepare_scenes(dev(c["points"]), c["offsets"], dev(c["boxes"]), dev(c["box_counts"]), dev(c["box_classes"]), params_of(c), cfg())
+    B = 3
+    keep = slice(1, 3)                                               # the one-point scene has no extent (its targets hold nan)
+    g = torch.Generator().manual_seed(3)
+    stages = [synthetic_stage(g, cfg(), B, 256, 1)] + [synthetic_stage(g, cfg(), B, 128, 18) for _ in range(2)]
+    seed_xyz = torch.rand((B, 256, 3), generator=g) * torch.tensor([8.0, 6.0, 3.0]) - torch.tensor([4.0, 3.0, 0.0])
+    point_logits = torch.randn((B, 256, 18), generator=g) - 1
+
+    def outputs():
+        st = [{k: v[keep].detach().to(DEV).requires_grad_(v.requires_grad) for k, v in s.items()} for s in stages]
+        return {"outputs": st[-1], "aux_outputs": st[:-1], "seed_xyz": seed_xyz[keep].to(DEV),
+                "enc_outputs": {"point_cls_logits": point_logits[keep].to(DEV).requires_grad_(True)}}
+
+    results = []
+    for targets in ({k: out[k][keep].contiguous() for k in TARGET_KEYS}, {k: dev(c[k][keep]) for k in TARGET_KEYS}):
+        crit = build_criterion(default_criterion_args(), cfg())
+        loss, loss_dict = crit(outputs(), targets)
+        results.append((float(loss), {k: float(v) for k, v in loss_dict.items()}, crit.last_assignments()[0]))
+    (la, da, ma), (lb, db, mb) = results
+    assert np.isfinite(la) and la > 0
+    for (ia, ka), (ib, kb) in zip(ma, mb):
+        assert torch.equal(ka, kb) and torch.equal(ia * (ka > 0), ib * (kb > 0))
+    np.testing.assert_allclose(la, lb, rtol=1e-3)
+    for k in db:
+        np.testing.assert_allclose(da[k], db[k], rtol=1e-3, atol=1e-6, err_msg=k)
+
+
+def test_bad_arguments_are_rejected_on_the_host():
+    from vdetr_amd.scene_prep import AugmentParams, prepare_scenes
+    c, p = random_case(10, (10, 20), 2, (1, 2))
+    args = lambda **kw: [kw.get("points", dev(c["points"])), kw.get("offsets", c["offsets"]), kw.get("boxes", dev(c["boxes"])),  # noqa: E731
+                         dev(c["box_counts"]), dev(c["box_classes"]), kw.get("params", p), cfg()]
+    with pytest.raises(ValueError, match="no points"):
+        prepare_scenes(*args(offsets=np.array([0, 0, 30], np.int32)))
+    with pytest.raises(ValueError, match="no points"):
+        prepare_scenes(*args(offsets=torch.tensor([0, 30, 30], dtype=torch.int32)))
+    with pytest.raises(RuntimeError, match="CPU not supported"):
+        prepare_scenes(*args(points=torch.from_numpy(c["points"])))
+    with pytest.raises(RuntimeError, match="CPU not supported"):
+        prepare_scenes(*args(boxes=torch.from_numpy(c["boxes"])))
+    for bad in (np.array([[0, 10]] * 2), np.array([[0, -1]] * 2), torch.tensor([[0, 9], [20, 0]])):   # scene 0 holds rows 0..9
+        with pytest.raises(ValueError, match="outside"):
+            prepare_scenes(*args(), choices=bad)
+    with pytest.raises(ValueError):
+        prepare_scenes(*args(params=AugmentParams.identity(3)))
+    with pytest.raises(ValueError, match="columns"):
+        prepare_scenes(*args(), color_mean=-1.0)
+    with pytest.raises(ValueError, match="max_num_obj"):
+        prepare_scenes(*args(), max_num_obj=1)
+    ok = prepare_scenes(*args(), choices=np.array([[0, 9, 9], [19, 0, 0]]), max_num_obj=2)
+    assert ok["gt_box_centers"].shape == (2, 2, 3) and [len(q) for q in ok["point_clouds"]] == [3, 3]

@@ -8,3 +8,14 @@ checkpoint key layout.  Device side: ``lib/libvdetr_hip.so`` (hand-written HIP k
 its tensors are not on the GPU or when the HIP library is missing.
 """
 __version__ = "0.1.0"
+
+_SCENE_PREP = ("AugmentParams", "draw_augment_params", "prepare_scenes", "nyu40_to_class")
+
+
+def __getattr__(name):
+    # the scene preparation (scene_prep.py) is the package's loader-facing interface; resolved on first use so that importing the
+    # package stays free of torch
+    if name in _SCENE_PREP:
+        from . import scene_prep
+        return getattr(scene_prep, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -275,6 +275,19 @@ class IouExt(ctypes.Structure):
         (n, c_void_p) for n in ("center", "size", "angle", "d_center", "d_size", "d_angle")]
 
 
+VDETR_SCENE_PREP_TILE, VDETR_SCENE_PREP_PARAMS = 256, 8
+VDETR_COLOR_KEEP, VDETR_COLOR_MEAN, VDETR_COLOR_UNIT = 0, 1, 2
+
+
+class ScenePrepDesc(ctypes.Structure):
+    """Mirror of ``vdetr_scene_prep_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "C", "G", "max_obj", "num_points", "color_mode", "num_classes", "choices_i64")] + [
+        (n, c_void_p) for n in ("points", "offsets", "choices", "params", "boxes", "box_counts", "box_classes", "mean_size",
+                                "out_points", "dims_min", "dims_max", "corners", "centers", "centers_norm", "sizes", "sizes_norm",
+                                "size_residual", "angle_class", "sem_cls", "angle_residual", "angles", "present")]
+
+
 class SpBnDesc(ctypes.Structure):
     """Mirror of ``vdetr_spbn_desc``."""
 
@@ -377,6 +390,9 @@ _SIGNATURES = {
     "vdetr_set_loss_batch_f32": (c_int, [ctypes.POINTER(SetLossDesc), c_int, c_void_p]),
     "vdetr_match_cost_ext_batch_f32": (c_int, [ctypes.POINTER(MatchDesc), ctypes.POINTER(IouExt), c_int, c_void_p]),
     "vdetr_set_loss_ext_batch_f32": (c_int, [ctypes.POINTER(SetLossDesc), ctypes.POINTER(IouExt), c_int, c_void_p]),
+    "vdetr_scene_prep_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "vdetr_scene_prep_points_f32": (c_int, [ctypes.POINTER(ScenePrepDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vdetr_scene_prep_targets_f32": (c_int, [ctypes.POINTER(ScenePrepDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
     "vdetr_sp_kernel_map_i32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vdetr_sp_inverse_map_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_sp_gather_cols_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

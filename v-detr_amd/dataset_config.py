@@ -24,6 +24,9 @@ class ScannetDatasetConfig:
             [0.59359559, 0.59124924, 0.73919014], [0.50867595, 0.50656087, 0.30136236],
             [1.15115265, 1.0546296, 0.49706794], [0.47535286, 0.49249493, 0.58021168]])
         self.mean_size_arr_hard_anchor = np.ones((18, 3))  # scannet.py:93-95
+        # scannet.py:65-70: the nyu40 ids of the 18 classes, as the last column of a scan's _bbox.npy holds them
+        self.nyu40ids = np.array([3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39])
+        self.nyu40id2class = {int(nyu40id): i for i, nyu40id in enumerate(self.nyu40ids)}
 
     def box_parametrization_to_corners(self, box_center_unnorm, box_size, box_angle):
         """scannet.py:168-171"""

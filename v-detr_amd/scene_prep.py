@@ -1,0 +1,180 @@
+"""A loaded scan -> the model's ``inputs`` and the criterion's ``targets`` on the device (reference
+datasets/scannet.py:510-626, ``ScannetDetectionDataset.__getitem__`` after the files are read).
+
+The loader hands over raw arrays: the packed clouds of a batch, their boxes and the per-scene augmentation parameters
+(``draw_augment_params`` draws them from ``np.random`` exactly as the reference consumes it, so a seed gives the reference's
+own augmentation; ``AugmentParams.identity`` is the evaluation split).  ``prepare_scenes`` then flips, rotates, translates and
+scales clouds and boxes, takes ``point_cloud_dims_min/max`` and builds the ``gt_*`` tensors in two launches on the current
+stream (csrc/scene_prep.hip), with no host round trip.  File reading, the split lists, the colour and cuboid augmentations
+and ``use_height`` stay with the loader.  No CPU path.
+"""
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+TARGET_KEYS = ("gt_box_corners", "gt_box_centers", "gt_box_centers_normalized", "gt_angle_class_label", "gt_angle_residual_label",
+               "gt_box_sem_cls_label", "gt_box_present", "gt_box_sizes", "gt_box_sizes_normalized", "gt_box_sizes_residual_label",
+               "gt_box_angles")
+
+
+@dataclass
+class AugmentParams:
+    """Per-scene parameters of scannet.py:516-541: flips (bool [B]), rot_angle [B], trans [B,3], scale [B] (float64)."""
+    flip_x: np.ndarray
+    flip_y: np.ndarray
+    rot_angle: np.ndarray
+    trans: np.ndarray
+    scale: np.ndarray
+
+    @classmethod
+    def identity(cls, B):
+        """augment=False: nothing is flipped, turned, moved or scaled"""
+        return cls(np.zeros(B, bool), np.zeros(B, bool), np.zeros(B), np.zeros((B, 3)), np.ones(B))
+
+    def __len__(self):
+        return len(self.rot_angle)
+
+    def table(self):
+        """[B, 8] float64 rows (flip_x, flip_y, cos, sin, trans xyz, scale): what the kernels read"""
+        angle = np.asarray(self.rot_angle, np.float64)
+        return np.ascontiguousarray(np.concatenate(
+            [np.asarray(self.flip_x, np.float64)[:, None], np.asarray(self.flip_y, np.float64)[:, None], np.cos(angle)[:, None],
+             np.sin(angle)[:, None], np.asarray(self.trans, np.float64).reshape(-1, 3), np.asarray(self.scale, np.float64)[:, None]], 1))
+
+
+def draw_augment_params(B, rot_ratio, trans_ratio, scale_ratio, random=np.random):
+    """Draws B scenes' parameters from ``random`` (``np.random`` or a ``RandomState``) scene by scene in the order of
+    scannet.py:516-540: two flips, the angle, then the translation only if trans_ratio > 0 and the scale only if
+    scale_ratio > 0 — a ratio of 0 leaves the stream where the reference leaves it."""
+    p = AugmentParams.identity(B)
+    for b in range(B):
+        p.flip_x[b] = random.random() > 0.5
+        p.flip_y[b] = random.random() > 0.5
+        p.rot_angle[b] = ((random.random() * np.pi / 18) - np.pi / 36) * rot_ratio / 5.0
+        if trans_ratio > 0.0:
+            p.trans[b] = (random.random(size=3) - 0.5) * trans_ratio / 0.5
+        if scale_ratio > 0.0:
+            p.scale[b] = 1 + (random.random() - 0.5) * scale_ratio / 0.5
+    return p
+
+
+def nyu40_to_class(nyu40_ids, dataset_config):
+    """The last column of a scan's ``_bbox.npy`` -> class indices, on the host (scannet.py:607-610)."""
+    table = dataset_config.nyu40id2class
+    return np.array([table[int(x)] for x in np.asarray(nyu40_ids).reshape(-1)], np.int64).reshape(np.shape(nyu40_ids))
+
+
+def _host_i32(a, name):
+    if torch.is_tensor(a):
+        a = a.cpu().numpy()   # a device tensor costs one synchronisation here: pass offsets as the loader has them, on the host
+    a = np.ascontiguousarray(np.asarray(a), dtype=np.int64)
+    if a.ndim != 1 or len(a) < 1:
+        raise ValueError(f"{name} must hold B + 1 row offsets")
+    return a
+
+
+def prepare_scenes(points, offsets, boxes, box_counts, box_classes, params, dataset_config, *, choices=None, color_mean=None,
+                   max_num_obj=None):
+    """points [N,3+C] f32 (packed scenes), offsets [B+1] (host array / CPU tensor; a device tensor is read back once), boxes
+    [B,G,6] f32 centre + size, box_counts [B], box_classes [B,G] int64 class indices (``nyu40_to_class``), params
+    ``AugmentParams`` -> dict of device tensors: ``point_clouds`` (list of [n_i,3+C] views of one packed tensor),
+    ``point_cloud_dims_min/max`` [B,3] and the eleven ``gt_*`` tensors [B,MAX_NUM_OBJ,...] of scannet.py:591-626.
+
+    ``choices`` [B,num_points] int32/int64: output row j of scene b is the scene's row choices[b,j] (pc_util.random_sampling's
+    ``pc[choices]``, repeats allowed) and the bounds cover the kept rows; a host array is range-checked here, a device tensor
+    cannot be without a synchronisation (the kernel turns an index outside the scene into a row of NaN).  ``color_mean``: None
+    leaves columns 3:6, negative is ``(rgb - MEAN_COLOR_RGB) / 256.0``, otherwise ``rgb / 255.0 - 0.5`` (scannet.py:453-456)."""
+    for t, name in ((points, "points"), (boxes, "boxes"), (box_counts, "box_counts"), (box_classes, "box_classes")):
+        L.require_gpu(t, name)
+    L.require_float(points, "points")
+    L.require_float(boxes, "boxes")
+    dev = points.device
+    off = _host_i32(offsets, "offsets")
+    B = len(off) - 1
+    if points.dim() != 2 or points.shape[1] < 3:
+        raise ValueError(f"points must be [N, 3+C], got {tuple(points.shape)}")
+    if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 6:
+        raise ValueError(f"boxes must be [{B}, G, 6], got {tuple(boxes.shape)}")
+    N, W = points.shape
+    G = boxes.shape[1]
+    M = int(dataset_config.max_num_obj if max_num_obj is None else max_num_obj)
+    if G > M:
+        raise ValueError(f"{G} box slots > max_num_obj {M}")
+    if tuple(box_counts.shape) != (B,) or tuple(box_classes.shape) != (B, G) or len(params) != B:
+        raise ValueError("box_counts [B], box_classes [B,G] and params must describe the B scenes of offsets")
+    if off[0] != 0 or off[-1] != N or N >= 2 ** 31:
+        raise ValueError(f"offsets run from {off[0]} to {off[-1]}, points has {N} rows")
+    sizes = np.diff(off)
+    if (sizes <= 0).any():
+        raise ValueError(f"scene {int(np.argmax(sizes <= 0))} has no points (point_cloud.min would fail, scannet.py:563)")
+    mode = L.VDETR_COLOR_KEEP if color_mean is None else L.VDETR_COLOR_MEAN if color_mean < 0 else L.VDETR_COLOR_UNIT
+    if mode != L.VDETR_COLOR_KEEP and W < 6:
+        raise ValueError(f"color_mean needs rgb in columns 3:6, points has {W} columns")
+
+    num_points = 0
+    if choices is not None:
+        if not torch.is_tensor(choices):
+            choices = torch.from_numpy(np.ascontiguousarray(choices))
+        if choices.dim() != 2 or choices.shape[0] != B or choices.shape[1] < 1 or choices.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"choices must be int32 / int64 [{B}, num_points]")
+        if not choices.is_cuda:
+            c = choices.numpy()
+            if (c < 0).any() or (c >= sizes[:, None]).any():
+                raise ValueError("choices hold a row outside their scene")
+            choices = choices.to(dev, non_blocking=True)
+        choices = choices.contiguous()
+        num_points = choices.shape[1]
+    keep_rows = [num_points] * B if num_points else sizes.tolist()
+    rows = int(sum(keep_rows))
+
+    points, boxes = points.detach().contiguous(), boxes.detach().contiguous()
+    counts = box_counts.detach().to(torch.int64).contiguous()
+    classes = box_classes.detach().to(torch.int64).contiguous()
+    off32 = np.ascontiguousarray(off, dtype=np.int32)
+    off_dev = torch.from_numpy(off32).to(dev, non_blocking=True)
+    table = torch.from_numpy(params.table()).to(dev, non_blocking=True)
+    mean = torch.from_numpy(np.ascontiguousarray(dataset_config.mean_size_arr, dtype=np.float64)).to(dev, non_blocking=True)
+
+    f32 = dict(dtype=torch.float32, device=dev)
+    i64 = dict(dtype=torch.int64, device=dev)
+    out = torch.empty((rows, W), **f32)
+    ret = {"point_cloud_dims_min": torch.empty((B, 3), **f32), "point_cloud_dims_max": torch.empty((B, 3), **f32),
+           "gt_box_corners": torch.empty((B, M, 8, 3), **f32), "gt_box_centers": torch.empty((B, M, 3), **f32),
+           "gt_box_centers_normalized": torch.empty((B, M, 3), **f32), "gt_angle_class_label": torch.empty((B, M), **i64),
+           "gt_angle_residual_label": torch.empty((B, M), **f32), "gt_box_sem_cls_label": torch.empty((B, M), **i64),
+           "gt_box_present": torch.empty((B, M), **f32), "gt_box_sizes": torch.empty((B, M, 3), **f32),
+           "gt_box_sizes_normalized": torch.empty((B, M, 3), **f32), "gt_box_sizes_residual_label": torch.empty((B, M, 3), **f32),
+           "gt_box_angles": torch.empty((B, M), **f32)}
+    ret["point_clouds"] = list(torch.split(out, keep_rows)) if B else []
+    if B == 0:
+        return ret
+
+    d = L.ScenePrepDesc()
+    d.B, d.C, d.G, d.max_obj, d.num_points, d.color_mode = B, W - 3, G, M, num_points, mode
+    d.num_classes, d.choices_i64 = mean.shape[0], int(choices is not None and choices.dtype == torch.int64)
+    d.points, d.offsets, d.params, d.mean_size = points.data_ptr(), off_dev.data_ptr(), table.data_ptr(), mean.data_ptr()
+    d.choices = choices.data_ptr() if choices is not None else None
+    d.boxes, d.box_counts, d.box_classes = boxes.data_ptr(), counts.data_ptr(), classes.data_ptr()
+    d.out_points, d.dims_min, d.dims_max = out.data_ptr(), ret["point_cloud_dims_min"].data_ptr(), ret["point_cloud_dims_max"].data_ptr()
+    for field, key in (("corners", "gt_box_corners"), ("centers", "gt_box_centers"), ("centers_norm", "gt_box_centers_normalized"),
+                       ("sizes", "gt_box_sizes"), ("sizes_norm", "gt_box_sizes_normalized"),
+                       ("size_residual", "gt_box_sizes_residual_label"), ("angle_class", "gt_angle_class_label"),
+                       ("sem_cls", "gt_box_sem_cls_label"), ("angle_residual", "gt_angle_residual_label"),
+                       ("angles", "gt_box_angles"), ("present", "gt_box_present")):
+        setattr(d, field, ret[key].data_ptr())
+    host = off32.ctypes.data_as(ctypes.c_void_p)
+    nbytes = L.lib().vdetr_scene_prep_workspace_bytes(host, B, num_points)
+    ws = L.workspace(nbytes, dev)
+    _launch_pair(d, host, ws, nbytes)
+    return ret
+
+
+def _launch_pair(d, host_offsets, ws, nbytes):
+    """the two launches on the current stream (tools/scene_prep_bench.py times exactly this)"""
+    lib, stream = L.lib(), L.stream_ptr()
+    L.check(lib.vdetr_scene_prep_points_f32(ctypes.byref(d), host_offsets, L.ptr(ws), nbytes, stream), "scene_prep_points")
+    L.check(lib.vdetr_scene_prep_targets_f32(ctypes.byref(d), host_offsets, L.ptr(ws), nbytes, stream), "scene_prep_targets")
