@@ -913,6 +913,56 @@ int vdetr_scene_prep_targets_f32(const vdetr_scene_prep_desc* desc, const int32_
                                  size_t workspace_bytes, vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The cuboid crop of a training scene and the sampling after it (reference utils/random_cuboid.py:38-98 and
+ * pc_util.random_sampling as called from datasets/scannet.py:476-498).  The host draws every scene's attempts from the random
+ * stream and uploads them as one table; vdetr_cuboid_crop_f32 (five launches) decides all of them at once: the raw clouds'
+ * bounds, every attempt's crop box, per tile of VDETR_CUBOID_TILE rows and attempt the count and the float32 min / max of the
+ * rows inside, per scene the FIRST attempt that is valid, keeps >= min_points rows and (if the scene filters its boxes) at
+ * least one box centre within the kept rows' min / max, the box list compacted in its order, and the winning attempt's rows
+ * compacted in ascending order into kept_rows.  No attempt accepted: trial -1, every row and every box kept (the reference's
+ * fallback).  The host reads `result` back (the one synchronisation: how many numbers the sampling draws depends on the kept
+ * count), draws the sample and vdetr_cuboid_compose_i32 (one launch) maps it through kept_rows to rows of the scene.
+ * Precision model, the reference's dtypes operation by operation: range_xyz = float32 max - float32 min in float32 (NaN if a
+ * coordinate is NaN); new_range = (double)range * crop_range / 2.0; max / min_xyz = (double)centre row +- new_range; a row
+ * is inside when (double)x <= max and >= min on all three axes (false for NaN); a box is kept when its centre, in its own
+ * dtype, lies within the float32 min / max of the kept rows, both ends inclusive.  All decisions are exact comparisons.
+ * ---------------------------------------------------------------------------------------------- */
+#define VDETR_CUBOID_TILE 256
+#define VDETR_CUBOID_ATTEMPT_LANES 128 /* workgroup of the per-attempt kernels: one lane per attempt, in passes above 128 */
+#define VDETR_CUBOID_MAX_TRIALS 1024
+#define VDETR_CUBOID_TRIAL 4  /* doubles per attempt: crop_range xyz, centre row of the scene (-1: the aspect test failed) */
+#define VDETR_CUBOID_RESULT 4 /* int32 per scene: accepted attempt or -1, kept rows, kept boxes, 0 */
+typedef struct vdetr_cuboid_desc {
+  int32_t B;           /* scenes (<= 4096) */
+  int32_t W;           /* floats per row of `points` (>= 3; xyz first) */
+  int32_t G;           /* box slots */
+  int32_t T;           /* attempts per scene (1 .. VDETR_CUBOID_MAX_TRIALS) */
+  int32_t min_points;  /* >= 1 */
+  int32_t boxes_f64;   /* boxes / out_boxes hold double (1) or float (0) */
+  int32_t num_points;  /* vdetr_cuboid_compose_i32: sampled rows per scene */
+  int32_t reserved;
+  const float* points;        /* [offsets[B], W] */
+  const int32_t* offsets;     /* [B+1] DEVICE copy of offsets_host */
+  const double* trials;       /* [B, T+1, VDETR_CUBOID_TRIAL]; row T of a scene: (filter its boxes 0 / 1, 0, 0, 0) */
+  const void* boxes;          /* [B, G, 6] centre, size; slots >= box_counts[b] are not read */
+  const int64_t* box_counts;  /* [B] */
+  const int64_t* box_classes; /* [B, G] */
+  void* out_boxes;            /* [B, G, 6] the kept boxes in their order, then zero rows */
+  int64_t* out_counts;        /* [B] */
+  int64_t* out_classes;       /* [B, G] */
+  int32_t* result;            /* [B, VDETR_CUBOID_RESULT] */
+  int32_t* kept_rows;         /* [offsets[B]]: scene b's kept rows, ascending, at offsets[b] .. offsets[b] + result[b][1] */
+  const int32_t* drawn;       /* [B, num_points] indices into a scene's kept rows (compose) */
+  int32_t* choices;           /* [B, num_points] rows of the scene (compose); -1 for an index outside the kept rows */
+} vdetr_cuboid_desc;
+/* offsets_host as for the scene preparation.  The workspace holds the partials (9 floats per tile, 6 doubles per scene and
+ * attempt, 7 words per tile and attempt, 1 word per tile) and only lives for the call. */
+size_t vdetr_cuboid_workspace_bytes(const int32_t* offsets_host, int B, int T);
+int vdetr_cuboid_crop_f32(const vdetr_cuboid_desc* desc, const int32_t* offsets_host, void* workspace, size_t workspace_bytes,
+                          vdetr_stream_t stream);
+int vdetr_cuboid_compose_i32(const vdetr_cuboid_desc* desc, const int32_t* offsets_host, vdetr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Greedy 3-D NMS of a scene's predictions (reference utils/nms.py:78-162 nms_3d_faster /
  * nms_3d_faster_samecls as called from utils/ap_calculator.py:165-220 on the min / max extents of the 8 box corners).
  * corners (B,K,8,3) f32, score (B,K) f32, cls (B,K) i32 or NULL (class-agnostic nms_3d_faster), valid (B,K) u8 or NULL

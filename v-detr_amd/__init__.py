@@ -9,7 +9,8 @@ its tensors are not on the GPU or when the HIP library is missing.
 """
 __version__ = "0.1.0"
 
-_SCENE_PREP = ("AugmentParams", "draw_augment_params", "prepare_scenes", "nyu40_to_class")
+_SCENE_PREP = ("AugmentParams", "draw_augment_params", "prepare_scenes", "nyu40_to_class", "crop_and_sample", "draw_cuboid_trials",
+               "CuboidTrials")
 
 
 def __getattr__(name):

@@ -288,6 +288,17 @@ class ScenePrepDesc(ctypes.Structure):
                                 "size_residual", "angle_class", "sem_cls", "angle_residual", "angles", "present")]
 
 
+VDETR_CUBOID_TILE, VDETR_CUBOID_MAX_TRIALS, VDETR_CUBOID_TRIAL, VDETR_CUBOID_RESULT = 256, 1024, 4, 4
+
+
+class CuboidDesc(ctypes.Structure):
+    """Mirror of ``vdetr_cuboid_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "W", "G", "T", "min_points", "boxes_f64", "num_points", "reserved")] + [
+        (n, c_void_p) for n in ("points", "offsets", "trials", "boxes", "box_counts", "box_classes", "out_boxes", "out_counts",
+                                "out_classes", "result", "kept_rows", "drawn", "choices")]
+
+
 class SpBnDesc(ctypes.Structure):
     """Mirror of ``vdetr_spbn_desc``."""
 
@@ -393,6 +404,9 @@ _SIGNATURES = {
     "vdetr_scene_prep_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "vdetr_scene_prep_points_f32": (c_int, [ctypes.POINTER(ScenePrepDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
     "vdetr_scene_prep_targets_f32": (c_int, [ctypes.POINTER(ScenePrepDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vdetr_cuboid_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "vdetr_cuboid_crop_f32": (c_int, [ctypes.POINTER(CuboidDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vdetr_cuboid_compose_i32": (c_int, [ctypes.POINTER(CuboidDesc), c_void_p, c_void_p]),
     "vdetr_sp_kernel_map_i32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vdetr_sp_inverse_map_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_sp_gather_cols_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -5,8 +5,10 @@ The loader hands over raw arrays: the packed clouds of a batch, their boxes and 
 (``draw_augment_params`` draws them from ``np.random`` exactly as the reference consumes it, so a seed gives the reference's
 own augmentation; ``AugmentParams.identity`` is the evaluation split).  ``prepare_scenes`` then flips, rotates, translates and
 scales clouds and boxes, takes ``point_cloud_dims_min/max`` and builds the ``gt_*`` tensors in two launches on the current
-stream (csrc/scene_prep.hip), with no host round trip.  File reading, the split lists, the colour and cuboid augmentations
-and ``use_height`` stay with the loader.  No CPU path.
+stream (csrc/scene_prep.hip), with no host round trip.  ``crop_and_sample`` is the step before it in the training split, the
+cuboid crop and the sampling (scannet.py:476-498, csrc/cuboid.hip): it replays the random stream attempt by attempt and returns
+the ``choices`` that ``prepare_scenes`` takes.  File reading, the split lists, the colour augmentations and ``use_height`` stay
+with the loader.  No CPU path.
 """
 import ctypes
 from dataclasses import dataclass
@@ -178,3 +180,171 @@ def _launch_pair(d, host_offsets, ws, nbytes):
     lib, stream = L.lib(), L.stream_ptr()
     L.check(lib.vdetr_scene_prep_points_f32(ctypes.byref(d), host_offsets, L.ptr(ws), nbytes, stream), "scene_prep_points")
     L.check(lib.vdetr_scene_prep_targets_f32(ctypes.byref(d), host_offsets, L.ptr(ws), nbytes, stream), "scene_prep_targets")
+
+
+# ---- the cuboid crop and the sampling after it (reference utils/random_cuboid.py, pc_util.random_sampling) -----------
+@dataclass
+class CuboidTrials:
+    """One scene's attempts as random_cuboid.py:43-50 draws them: ``crop_range`` [T,3] float64, ``center`` [T] int64 (the row
+    the crop is centred on; -1 where the aspect test failed and none was drawn), ``valid`` [T] bool, and ``states``: the
+    generator's state just after each attempt."""
+    crop_range: np.ndarray
+    center: np.ndarray
+    valid: np.ndarray
+    states: list
+    random: object
+
+    def rewind(self, trial):
+        """puts the generator to "just after attempt ``trial``"; -1 (the fallback) is after the last attempt"""
+        self.random.set_state(self.states[trial])
+
+
+def _aspect_ok(crop, aspect):
+    """the smaller over the larger edge of the xy, xz or yz face reaches ``aspect`` (float64 quotients)"""
+    pairs = crop[[[0, 1], [0, 2], [1, 2]]]
+    return bool((pairs.min(1) / pairs.max(1) >= aspect).any())
+
+
+def draw_cuboid_trials(n_points, random=np.random, *, aspect=0.8, min_crop=0.5, max_crop=1.0, max_trials=100):
+    """Draws ``max_trials`` attempts for a scene of ``n_points`` rows from ``random`` (``np.random`` or a ``RandomState``): every
+    attempt takes ``rand(3)``; one whose aspect test passes, which is decided here, also takes ``choice(n_points)``.  The
+    reference stops at the attempt it accepts, which depends on the points: ``CuboidTrials.rewind`` puts the generator back
+    there once the device has said which one it was.  Host only."""
+    crop = np.zeros((max_trials, 3))
+    center = np.full(max_trials, -1, np.int64)
+    valid = np.zeros(max_trials, bool)
+    states = []
+    for t in range(max_trials):
+        crop[t] = min_crop + random.rand(3) * (max_crop - min_crop)
+        valid[t] = _aspect_ok(crop[t], aspect)
+        if valid[t]:
+            center[t] = random.choice(n_points)
+        states.append(random.get_state())
+    return CuboidTrials(crop, center, valid, states, random)
+
+
+def crop_and_sample(points, offsets, boxes, box_counts, box_classes, randoms, num_points, *, min_points=30000, aspect=0.8,
+                    min_crop=0.5, max_crop=1.0, max_trials=100, filter_boxes=None):
+    """``RandomCuboid`` and ``random_sampling`` of the training split (scannet.py:476-498) for a packed batch.  points / offsets
+    / box_counts / box_classes as in ``prepare_scenes``; boxes [B,G,6] float32 or float64 (the reference filters on the file's
+    array); ``randoms``: B distinct legacy generators (``RandomState`` or the ``np.random`` module), one per scene; from a
+    generator's state at the call this reproduces the reference's crop and sampling of that scene and leaves the generator
+    where the reference leaves it.  ``filter_boxes`` host bool [B]: whether an attempt must keep a box centre (default
+    ``box_counts > 0``; the reference's literal test is ``instance_bboxes.sum() > 0`` over all seven columns of the file).
+
+    -> dict: ``choices`` int32 [B,num_points] on the device, rows of the original scene (for ``prepare_scenes(choices=...)`` and
+    for the loader's per-point labels); ``boxes`` / ``box_counts`` / ``box_classes``: the kept boxes in their order, zero rows
+    after them, shapes unchanged; ``trial`` host [B]: the accepted attempt or -1 for the fallback (scene and boxes unchanged);
+    ``kept_points`` host [B]; ``kept_rows``: per scene a device view of the crop's rows, ascending.
+
+    Six launches whatever B and the number of attempts (csrc/cuboid.hip) and ONE read-back of (trial, kept points, kept
+    boxes) per scene, the call's only synchronisation.  It is inherent: ``np.random.choice(n_kept, num_points, replace=n_kept <
+    num_points)`` consumes the stream differently for every ``n_kept``.  No CPU path."""
+    for t, name in ((points, "points"), (boxes, "boxes"), (box_counts, "box_counts"), (box_classes, "box_classes")):
+        L.require_gpu(t, name)
+    L.require_float(points, "points")
+    if boxes.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("boxes must be a float or double tensor")
+    dev = points.device
+    off = _host_i32(offsets, "offsets")
+    B = len(off) - 1
+    if points.dim() != 2 or points.shape[1] < 3:
+        raise ValueError(f"points must be [N, 3+C], got {tuple(points.shape)}")
+    if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 6:
+        raise ValueError(f"boxes must be [{B}, G, 6], got {tuple(boxes.shape)}")
+    N, W = points.shape
+    G = boxes.shape[1]
+    if tuple(box_counts.shape) != (B,) or tuple(box_classes.shape) != (B, G):
+        raise ValueError("box_counts [B] and box_classes [B,G] must describe the B scenes of offsets")
+    if off[0] != 0 or off[-1] != N or N >= 2 ** 31:
+        raise ValueError(f"offsets run from {off[0]} to {off[-1]}, points has {N} rows")
+    sizes = np.diff(off)
+    if (sizes <= 0).any():
+        raise ValueError(f"scene {int(np.argmax(sizes <= 0))} has no points")
+    num_points, min_points, max_trials = int(num_points), int(min_points), int(max_trials)
+    if num_points < 1:
+        raise ValueError(f"num_points {num_points} < 1")
+    if min_points < 1:
+        raise ValueError(f"min_points {min_points} < 1 (an empty crop has no bounds)")
+    if not 1 <= max_trials <= L.VDETR_CUBOID_MAX_TRIALS:
+        raise ValueError(f"max_trials {max_trials} outside 1 .. {L.VDETR_CUBOID_MAX_TRIALS}")
+    randoms = list(randoms)
+    if len(randoms) != B:
+        raise ValueError(f"{len(randoms)} generators for {B} scenes")
+    if len({id(r) for r in randoms}) != B:
+        raise ValueError("two scenes share a generator: a scene's draws would start where another scene's end, which depends on "
+                         "its points (call scene by scene with B = 1 for one stream)")
+    if filter_boxes is not None:
+        filter_boxes = np.asarray(filter_boxes, bool)
+        if filter_boxes.shape != (B,):
+            raise ValueError(f"filter_boxes must be a host bool array [{B}]")
+
+    counts = box_counts.detach().to(torch.int64).contiguous()
+    classes = box_classes.detach().to(torch.int64).contiguous()
+    points, boxes = points.detach().contiguous(), boxes.detach().contiguous()
+    ret = {"boxes": torch.empty_like(boxes), "box_counts": torch.empty_like(counts), "box_classes": torch.empty_like(classes),
+           "choices": torch.empty((B, num_points), dtype=torch.int32, device=dev), "trial": np.zeros(B, np.int64),
+           "kept_points": np.zeros(B, np.int64), "kept_rows": []}
+    if B == 0:
+        return ret
+
+    # 1. host: every scene's attempts, one table
+    trials = [draw_cuboid_trials(int(n), r, aspect=aspect, min_crop=min_crop, max_crop=max_crop, max_trials=max_trials)
+              for n, r in zip(sizes, randoms)]
+    table = np.zeros((B, max_trials + 1, L.VDETR_CUBOID_TRIAL))
+    for b, t in enumerate(trials):
+        table[b, :max_trials, :3], table[b, :max_trials, 3] = t.crop_range, t.center
+    filter_dev = None
+    if filter_boxes is None:
+        filter_dev = (counts > 0).to(torch.float64)                    # stays on the device: no read-back for the default
+    else:
+        table[:, max_trials, 0] = filter_boxes
+    table = torch.from_numpy(table).to(dev, non_blocking=True)
+    if filter_dev is not None:
+        table[:, max_trials, 0] = filter_dev
+    off32 = np.ascontiguousarray(off, dtype=np.int32)
+    off_dev = torch.from_numpy(off32).to(dev, non_blocking=True)
+    result = torch.empty((B, L.VDETR_CUBOID_RESULT), dtype=torch.int32, device=dev)
+    kept_rows = torch.empty(N, dtype=torch.int32, device=dev)
+
+    # 2. device: five launches
+    d = L.CuboidDesc()
+    d.B, d.W, d.G, d.T, d.min_points, d.boxes_f64, d.num_points = B, W, G, max_trials, min(min_points, 2 ** 31 - 1), int(
+        boxes.dtype == torch.float64), num_points
+    d.points, d.offsets, d.trials = points.data_ptr(), off_dev.data_ptr(), table.data_ptr()
+    d.boxes, d.box_counts, d.box_classes = boxes.data_ptr(), counts.data_ptr(), classes.data_ptr()
+    d.out_boxes, d.out_counts, d.out_classes = ret["boxes"].data_ptr(), ret["box_counts"].data_ptr(), ret["box_classes"].data_ptr()
+    d.result, d.kept_rows, d.choices = result.data_ptr(), kept_rows.data_ptr(), ret["choices"].data_ptr()
+    host = off32.ctypes.data_as(ctypes.c_void_p)
+    nbytes = L.lib().vdetr_cuboid_workspace_bytes(host, B, max_trials)
+    ws = L.workspace(nbytes, dev)
+    alive = (points, boxes, counts, classes, table, off_dev, result, kept_rows, ret)
+    _launch_crop(d, host, ws, nbytes, alive)
+
+    # 3. the one read-back
+    res = result.cpu().numpy()
+    ret["trial"], ret["kept_points"] = res[:, 0].astype(np.int64), res[:, 1].astype(np.int64)
+    ret["kept_rows"] = [kept_rows[off[b]:off[b] + res[b, 1]] for b in range(B)]
+
+    # 4. host: every generator to where the reference stopped drawing attempts, then the sample as random_sampling draws it
+    drawn = np.empty((B, num_points), np.int32)
+    for b, t in enumerate(trials):
+        t.rewind(int(res[b, 0]))
+        n_kept = int(res[b, 1])
+        drawn[b] = t.random.choice(n_kept, num_points, replace=n_kept < num_points)
+
+    # 5. device: choices[b, j] = kept_rows[b][drawn[b, j]]
+    drawn_dev = torch.from_numpy(drawn).to(dev, non_blocking=True)
+    d.drawn = drawn_dev.data_ptr()
+    _launch_compose(d, host, alive + (drawn_dev,))
+    return ret
+
+
+def _launch_crop(d, host_offsets, ws, nbytes, alive):
+    """the five launches on the current stream (tools/cuboid_bench.py times exactly these and holds on to ``alive``, the tensors
+    the descriptor points into)"""
+    L.check(L.lib().vdetr_cuboid_crop_f32(ctypes.byref(d), host_offsets, L.ptr(ws), nbytes, L.stream_ptr()), "cuboid_crop")
+
+
+def _launch_compose(d, host_offsets, alive):
+    L.check(L.lib().vdetr_cuboid_compose_i32(ctypes.byref(d), host_offsets, L.stream_ptr()), "cuboid_compose")
