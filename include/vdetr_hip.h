@@ -963,6 +963,54 @@ int vdetr_cuboid_crop_f32(const vdetr_cuboid_desc* desc, const int32_t* offsets_
 int vdetr_cuboid_compose_i32(const vdetr_cuboid_desc* desc, const int32_t* offsets_host, vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The colour augmentations, the height channel and the SUN RGB-D colour step of a training scan (reference
+ * datasets/scannet.py:202-295, 436-451, 461-464, 544-560).  The host draws every random number in the reference's order and
+ * uploads it; the device does the per-point arithmetic in numpy's precision, operation by operation, so the results EQUAL
+ * the reference's (NaN positions included):
+ *   drop        float32 product with 0 / 1
+ *   contrast    lo / hi = float32 min / max of the dropped colours per scene and channel (a NaN is handed on); scale =
+ *               255 / (hi - lo) in float32 (a constant channel gives inf, then NaN); (float)(1 - b) * x + (float)b * ((x - lo)
+ *               * scale), every product and sum rounded to float32
+ *   jitter      clip(noise + (double)x, 0, 255) in float64, rounded once to float32 (noise already holds std * 255)
+ *   hue / sat   rgb_to_hsv, np.remainder(hue_val + h + 1, 1), clip(sat_ratio * s, 0, 1), hsv_to_rgb in float64, truncated
+ *               to uint8 (defined for values in [0, 256); a NaN gives 0)
+ *   height      z - np.percentile(z, 0.99): the float32 interpolation of two order statistics found by radix select
+ *   sunrgbd     + 0.5 (float32), * brightness, + shift, + jitter (float64 each, rounded to float32 after each), clip to [0, 1],
+ *               * keep, - 0.5 (float32)
+ * ---------------------------------------------------------------------------------------------- */
+#define VDETR_COLOR_AUG_TILE 256
+#define VDETR_HEIGHT_TILE 1024    /* rows per workgroup of the radix select's histogram kernel */
+#define VDETR_COLOR_AUG_PARAMS 8  /* doubles per scene.  vdetr_color_augment_f32: contrast fired (0 / 1), 1 - blend, blend,
+                                     first row of the scene's noise (-1: the jitter did not fire), hue / saturation fired
+                                     (0 / 1), hue_val, sat_ratio, drop given (0 / 1).
+                                     vdetr_sunrgbd_color_f32: brightness rgb, shift rgb, 0, 0 */
+#define VDETR_HEIGHT_SELECT 4     /* int32 per scene: index of the lower and of the upper order statistic, bits of the float32
+                                     interpolation weight, 0 */
+typedef struct vdetr_color_aug_desc {
+  int32_t B;           /* scenes (<= 4096) */
+  int32_t W;           /* floats per row of `points` (xyz first, rgb in columns 3:6) */
+  int32_t noise_rows;  /* rows of `noise` */
+  int32_t reserved;
+  const float* points;     /* [offsets[B], W] */
+  const int32_t* offsets;  /* [B+1] DEVICE copy of offsets_host */
+  float* out;              /* colour augment: [offsets[B], W]; height: [offsets[B], W+1]; sunrgbd: may be `points` (in place) */
+  const double* params;    /* [B, VDETR_COLOR_AUG_PARAMS] */
+  const uint8_t* keep;     /* [offsets[B]] 0: the row's colour is dropped; NULL if no scene drops (colour augment only) */
+  const double* noise;     /* colour augment: [noise_rows, 3] the fired scenes' jitter; sunrgbd: [noise_rows] per-row jitter */
+  const int32_t* select;   /* height: [B, VDETR_HEIGHT_SELECT] */
+} vdetr_color_aug_desc;
+/* offsets_host as for the scene preparation.  The workspaces hold per-tile partials (9 floats per tile of 256 rows and per
+ * scene; 3 x 256 counts per tile of VDETR_HEIGHT_TILE rows and 6 words per scene) and only live for the call.  Three, nine
+ * and one launch, whatever B, the data and the gates. */
+size_t vdetr_color_aug_workspace_bytes(const int32_t* offsets_host, int B);
+size_t vdetr_append_height_workspace_bytes(const int32_t* offsets_host, int B);
+int vdetr_color_augment_f32(const vdetr_color_aug_desc* desc, const int32_t* offsets_host, void* workspace, size_t workspace_bytes,
+                            vdetr_stream_t stream);
+int vdetr_append_height_f32(const vdetr_color_aug_desc* desc, const int32_t* offsets_host, void* workspace, size_t workspace_bytes,
+                            vdetr_stream_t stream);
+int vdetr_sunrgbd_color_f32(const vdetr_color_aug_desc* desc, const int32_t* offsets_host, vdetr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Greedy 3-D NMS of a scene's predictions (reference utils/nms.py:78-162 nms_3d_faster /
  * nms_3d_faster_samecls as called from utils/ap_calculator.py:165-220 on the min / max extents of the 8 box corners).
  * corners (B,K,8,3) f32, score (B,K) f32, cls (B,K) i32 or NULL (class-agnostic nms_3d_faster), valid (B,K) u8 or NULL

@@ -10,7 +10,8 @@ its tensors are not on the GPU or when the HIP library is missing.
 __version__ = "0.1.0"
 
 _SCENE_PREP = ("AugmentParams", "draw_augment_params", "prepare_scenes", "nyu40_to_class", "crop_and_sample", "draw_cuboid_trials",
-               "CuboidTrials")
+               "CuboidTrials", "ColorAugmentParams", "draw_color_augment", "augment_colors", "append_height", "percentile_plan",
+               "SunrgbdColorParams", "draw_sunrgbd_color", "sunrgbd_color_augment")
 
 
 def __getattr__(name):

@@ -299,6 +299,16 @@ class CuboidDesc(ctypes.Structure):
                                 "out_classes", "result", "kept_rows", "drawn", "choices")]
 
 
+VDETR_COLOR_AUG_TILE, VDETR_HEIGHT_TILE, VDETR_COLOR_AUG_PARAMS, VDETR_HEIGHT_SELECT = 256, 1024, 8, 4
+
+
+class ColorAugDesc(ctypes.Structure):
+    """Mirror of ``vdetr_color_aug_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "W", "noise_rows", "reserved")] + [
+        (n, c_void_p) for n in ("points", "offsets", "out", "params", "keep", "noise", "select")]
+
+
 class SpBnDesc(ctypes.Structure):
     """Mirror of ``vdetr_spbn_desc``."""
 
@@ -407,6 +417,11 @@ _SIGNATURES = {
     "vdetr_cuboid_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "vdetr_cuboid_crop_f32": (c_int, [ctypes.POINTER(CuboidDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
     "vdetr_cuboid_compose_i32": (c_int, [ctypes.POINTER(CuboidDesc), c_void_p, c_void_p]),
+    "vdetr_color_aug_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "vdetr_append_height_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "vdetr_color_augment_f32": (c_int, [ctypes.POINTER(ColorAugDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vdetr_append_height_f32": (c_int, [ctypes.POINTER(ColorAugDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vdetr_sunrgbd_color_f32": (c_int, [ctypes.POINTER(ColorAugDesc), c_void_p, c_void_p]),
     "vdetr_sp_kernel_map_i32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vdetr_sp_inverse_map_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_sp_gather_cols_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

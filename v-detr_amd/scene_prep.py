@@ -7,8 +7,12 @@ own augmentation; ``AugmentParams.identity`` is the evaluation split).  ``prepar
 scales clouds and boxes, takes ``point_cloud_dims_min/max`` and builds the ``gt_*`` tensors in two launches on the current
 stream (csrc/scene_prep.hip), with no host round trip.  ``crop_and_sample`` is the step before it in the training split, the
 cuboid crop and the sampling (scannet.py:476-498, csrc/cuboid.hip): it replays the random stream attempt by attempt and returns
-the ``choices`` that ``prepare_scenes`` takes.  File reading, the split lists, the colour augmentations and ``use_height`` stay
-with the loader.  No CPU path.
+the ``choices`` that ``prepare_scenes`` takes.  Before the crop come the per-point steps of scannet.py:436-464 (DESIGN.md 6.5,
+csrc/color_aug.hip): ``draw_color_augment`` + ``augment_colors`` are the four ``--use_color`` augmentations, ``append_height`` is
+``use_height``; after ``prepare_scenes`` comes ``draw_sunrgbd_color`` + ``sunrgbd_color_augment`` (``--coloraug_sunrgbd``,
+:544-560).  One generator per scene, used in that order, is left where the reference leaves ``np.random``, so a raw
+``_vert.npy`` array goes to the device once.  File reading, the split lists, ``use_normals`` and ``use_superpoint`` stay with the
+loader.  No CPU path.
 """
 import ctypes
 from dataclasses import dataclass
@@ -348,3 +352,229 @@ def _launch_crop(d, host_offsets, ws, nbytes, alive):
 
 def _launch_compose(d, host_offsets, alive):
     L.check(L.lib().vdetr_cuboid_compose_i32(ctypes.byref(d), host_offsets, L.stream_ptr()), "cuboid_compose")
+
+
+# ---- the colour augmentations, the height channel, the SUN RGB-D colour step (csrc/color_aug.hip) ----------------------
+@dataclass
+class ColorAugmentParams:
+    """One scene's draws of scannet.py:436-451.  ``keep`` bool [N] (False: the row's colour is dropped) or None when
+    ``color_drop`` is 0; ``blend`` the contrast's blend factor or None (gate not fired); ``noise`` float64 [N,3], already times
+    ``std * 255``, or None; ``hue_val`` / ``sat_ratio`` or None."""
+    n_points: int
+    keep: object = None
+    blend: object = None
+    noise: object = None
+    hue_val: object = None
+    sat_ratio: object = None
+
+
+def _hue_sat_fields(hue_sat):
+    hue, sat, p = hue_sat.split("_") if isinstance(hue_sat, str) else hue_sat
+    return float(hue), float(sat), float(p)
+
+
+def draw_color_augment(n_points, random=np.random, *, color_drop=0.0, color_contrastp=0.0, color_jitterp=0.0, hue_sat="0_0_0",
+                       jitter_std=0.005):
+    """Draws one scene's colour parameters from ``random`` (``np.random`` or a ``RandomState``) as scannet.py:436-451 consumes
+    the stream: ``random(N)`` only if color_drop > 0; the contrast's gate only if color_contrastp > 0 and its blend only if the
+    gate fires; the jitter's gate, then ``randn(N, 3)`` only if it fires; the hue / saturation gate only if the last field of
+    ``hue_sat`` ("hue_sat_p", the reference's option string, or the three numbers) is > 0, then the two draws only if it fires.
+    The Gaussian stays on the host: the legacy generator's polar rejection loop runs log and sqrt in libm's float64, and only
+    the same code gives the same bits.  Host only."""
+    n = int(n_points)
+    p = ColorAugmentParams(n)
+    if color_drop > 0:
+        p.keep = random.random(n) > color_drop
+    if color_contrastp > 0 and random.random() < color_contrastp:
+        p.blend = random.random()
+    if color_jitterp > 0 and random.random() < color_jitterp:
+        p.noise = random.randn(n, 3)
+        p.noise *= jitter_std * 255
+    hue_max, sat_max, hue_p = _hue_sat_fields(hue_sat)
+    if hue_p > 0 and random.random() < hue_p:
+        p.hue_val = (random.random() - 0.5) * 2 * hue_max
+        p.sat_ratio = 1 + (random.random() - 0.5) * 2 * sat_max
+    return p
+
+
+@dataclass
+class SunrgbdColorParams:
+    """One scene's draws of scannet.py:546-558: ``brightness`` [3], ``shift`` [3], ``jitter`` [n] float64, ``keep`` bool [n]."""
+    brightness: np.ndarray
+    shift: np.ndarray
+    jitter: np.ndarray
+    keep: np.ndarray
+
+
+def draw_sunrgbd_color(n_rows, random=np.random):
+    """``random(3)``, ``random(3)``, ``random(n)``, ``random(n)`` put through the expressions of scannet.py:546-558; called after
+    ``draw_augment_params`` for the same scene.  Host only."""
+    n = int(n_rows)
+    brightness = 1 + 0.4 * random.random(3) - 0.2
+    shift = 0.1 * random.random(3) - 0.05
+    jitter = 0.05 * random.random(n) - 0.025
+    return SunrgbdColorParams(brightness, shift, jitter, random.random(n) > 0.3)
+
+
+def _packed_scenes(points, offsets, min_width, what):
+    L.require_gpu(points, "points")
+    L.require_float(points, "points")
+    off = _host_i32(offsets, "offsets")
+    if points.dim() != 2 or points.shape[1] < min_width:
+        raise ValueError(f"{what}: points must be [N, {min_width} or more columns], got {tuple(points.shape)}")
+    N = points.shape[0]
+    if off[0] != 0 or off[-1] != N or N >= 2 ** 31:
+        raise ValueError(f"offsets run from {off[0]} to {off[-1]}, points has {N} rows")
+    sizes = np.diff(off)
+    if (sizes <= 0).any():
+        raise ValueError(f"scene {int(np.argmax(sizes <= 0))} has no points")
+    return off, sizes
+
+
+def _color_desc(points, out, off32, dev):
+    d = L.ColorAugDesc()
+    d.B, d.W = len(off32) - 1, points.shape[1]
+    off_dev = torch.from_numpy(off32).to(dev, non_blocking=True)
+    d.points, d.offsets, d.out = points.data_ptr(), off_dev.data_ptr(), out.data_ptr()
+    return d, off_dev
+
+
+def augment_colors(points, offsets, params):
+    """The four ``--use_color`` augmentations (scannet.py:436-451) on a packed batch: points [N,3+C] f32 with rgb (0 .. 255) in
+    columns 3:6, offsets [B+1] as in ``prepare_scenes``, params: B ``ColorAugmentParams`` (``draw_color_augment``) -> a new
+    [N,3+C] tensor; columns 3:6 are augmented, every other column is copied, the input is left alone.  Three launches on the
+    current stream whatever B and whichever gates fired; the result equals the reference's bit for bit.  No CPU path."""
+    off, sizes = _packed_scenes(points, offsets, 6, "augment_colors")
+    params = list(params)
+    B = len(off) - 1
+    if len(params) != B or any(p.n_points != n for p, n in zip(params, sizes)):
+        raise ValueError(f"params must hold one ColorAugmentParams per scene, drawn for its row count ({B} scenes)")
+    dev = points.device
+    points = points.detach().contiguous()
+    out = torch.empty_like(points)
+    if B == 0:
+        return out
+    N = points.shape[0]
+    table = np.zeros((B, L.VDETR_COLOR_AUG_PARAMS))
+    table[:, 3] = -1
+    noise, noise_rows = [], 0
+    keep = np.ones(N, bool) if any(p.keep is not None for p in params) else None
+    for b, p in enumerate(params):
+        if p.keep is not None:
+            table[b, 7] = 1
+            keep[off[b]:off[b + 1]] = p.keep
+        if p.blend is not None:
+            table[b, :3] = 1, 1 - p.blend, p.blend
+        if p.noise is not None:
+            table[b, 3] = noise_rows
+            noise.append(np.asarray(p.noise, np.float64).reshape(-1, 3))
+            noise_rows += len(noise[-1])
+        if p.hue_val is not None:
+            table[b, 4:7] = 1, p.hue_val, p.sat_ratio
+    off32 = np.ascontiguousarray(off, dtype=np.int32)
+    d, off_dev = _color_desc(points, out, off32, dev)
+    table_dev = torch.from_numpy(table).to(dev, non_blocking=True)
+    keep_dev = torch.from_numpy(keep.view(np.uint8)).to(dev, non_blocking=True) if keep is not None else None
+    noise_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate(noise))).to(dev, non_blocking=True) if noise else None
+    d.params, d.noise_rows = table_dev.data_ptr(), noise_rows
+    d.keep = keep_dev.data_ptr() if keep_dev is not None else None
+    d.noise = noise_dev.data_ptr() if noise_dev is not None else None
+    host = off32.ctypes.data_as(ctypes.c_void_p)
+    nbytes = L.lib().vdetr_color_aug_workspace_bytes(host, B)
+    ws = L.workspace(nbytes, dev)
+    _launch_colors(d, host, ws, nbytes, (points, out, off_dev, table_dev, keep_dev, noise_dev))
+    return out
+
+
+def _launch_colors(d, host_offsets, ws, nbytes, alive):
+    """the three launches on the current stream (tools/color_aug_bench.py times exactly these)"""
+    L.check(L.lib().vdetr_color_augment_f32(ctypes.byref(d), host_offsets, L.ptr(ws), nbytes, L.stream_ptr()), "color_augment")
+
+
+def percentile_plan(n, percent=0.99):
+    """What ``np.percentile(z, percent)`` (method "linear", numpy 2.2) takes from a float32 column of n values: the indices of the
+    two order statistics and the float32 weight between them.  All of it is float32 arithmetic on n alone:
+    q = float32(percent) / float32(100); the virtual index (n - 1) * q in float32; its floor and the floor + 1, both n - 1 once
+    the virtual index reaches n - 1; the weight is the virtual index minus its floor."""
+    q = np.float32(percent) / np.float32(100)
+    virtual = np.float32(n - 1) * q
+    lower = int(np.floor(virtual))
+    upper = lower + 1
+    if virtual >= n - 1:
+        lower = upper = n - 1
+    gamma = np.float32(np.float64(virtual) - (-1 if virtual >= n - 1 else lower))
+    return lower, upper, gamma
+
+
+def append_height(points, offsets):
+    """``use_height`` (scannet.py:461-464) on a packed batch: -> [N,3+C+1], the last column ``z - np.percentile(z, 0.99)`` of the
+    row's scene (a NaN in the column makes the floor NaN); it comes before ``crop_and_sample`` and then travels as an ordinary
+    extra channel.  The two order statistics are found by a radix select, not a sort: nine launches whatever B and the data,
+    two runs give the same bits.  No CPU path."""
+    off, sizes = _packed_scenes(points, offsets, 3, "append_height")
+    B = len(off) - 1
+    dev = points.device
+    points = points.detach().contiguous()
+    out = torch.empty((points.shape[0], points.shape[1] + 1), dtype=torch.float32, device=dev)
+    if B == 0:
+        return out
+    select = np.zeros((B, L.VDETR_HEIGHT_SELECT), np.int32)
+    for b, n in enumerate(sizes):
+        lower, upper, gamma = percentile_plan(int(n))
+        select[b, :3] = lower, upper, np.array(gamma, np.float32).view(np.int32)
+    off32 = np.ascontiguousarray(off, dtype=np.int32)
+    d, off_dev = _color_desc(points, out, off32, dev)
+    select_dev = torch.from_numpy(select).to(dev, non_blocking=True)
+    d.select = select_dev.data_ptr()
+    host = off32.ctypes.data_as(ctypes.c_void_p)
+    nbytes = L.lib().vdetr_append_height_workspace_bytes(host, B)
+    ws = L.workspace(nbytes, dev)
+    _launch_height(d, host, ws, nbytes, (points, out, off_dev, select_dev))
+    return out
+
+
+def _launch_height(d, host_offsets, ws, nbytes, alive):
+    L.check(L.lib().vdetr_append_height_f32(ctypes.byref(d), host_offsets, L.ptr(ws), nbytes, L.stream_ptr()), "append_height")
+
+
+def sunrgbd_color_augment(point_clouds, offsets, params):
+    """``--coloraug_sunrgbd`` (scannet.py:544-560), in place on the packed tensor behind ``prepare_scenes``' ``point_clouds`` (the
+    list of views, or the packed [rows,3+C] tensor itself), whose colours are already normalised; offsets [B+1]: the scenes' rows
+    in it; params: B ``SunrgbdColorParams`` (``draw_sunrgbd_color``).  One launch; returns ``point_clouds``.  No CPU path."""
+    packed = point_clouds
+    if not torch.is_tensor(point_clouds):
+        views = list(point_clouds)
+        if not views:
+            return point_clouds
+        packed = views[0]._base if views[0]._base is not None else views[0]
+        L.require_gpu(packed, "point_clouds")
+        at = packed.data_ptr()
+        for v in views:
+            if v.dim() != 2 or v.shape[1] != packed.shape[1] or not v.is_contiguous() or v.data_ptr() != at:
+                raise ValueError("point_clouds must be consecutive row blocks of one packed tensor (prepare_scenes' list)")
+            at += v.numel() * 4
+    off, sizes = _packed_scenes(packed, offsets, 6, "sunrgbd_color_augment")
+    if not packed.is_contiguous():
+        raise ValueError("point_clouds must be contiguous: the step runs in place")
+    params = list(params)
+    B = len(off) - 1
+    if len(params) != B or any(len(p.jitter) != n or len(p.keep) != n for p, n in zip(params, sizes)):
+        raise ValueError(f"params must hold one SunrgbdColorParams per scene, drawn for its row count ({B} scenes)")
+    if B == 0:
+        return point_clouds
+    dev = packed.device
+    table = np.zeros((B, L.VDETR_COLOR_AUG_PARAMS))
+    for b, p in enumerate(params):
+        table[b, :3], table[b, 3:6] = p.brightness, p.shift
+    off32 = np.ascontiguousarray(off, dtype=np.int32)
+    d, off_dev = _color_desc(packed, packed, off32, dev)
+    table_dev = torch.from_numpy(table).to(dev, non_blocking=True)
+    jitter_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(p.jitter, np.float64) for p in params]))).to(dev, non_blocking=True)
+    keep_dev = torch.from_numpy(np.concatenate([np.asarray(p.keep, bool) for p in params]).view(np.uint8)).to(dev, non_blocking=True)
+    d.params, d.noise, d.keep, d.noise_rows = table_dev.data_ptr(), jitter_dev.data_ptr(), keep_dev.data_ptr(), packed.shape[0]
+    _launch_sunrgbd(d, off32.ctypes.data_as(ctypes.c_void_p), (packed, off_dev, table_dev, jitter_dev, keep_dev))
+    return point_clouds
+
+
+def _launch_sunrgbd(d, host_offsets, alive):
+    L.check(L.lib().vdetr_sunrgbd_color_f32(ctypes.byref(d), host_offsets, L.stream_ptr()), "sunrgbd_color")
