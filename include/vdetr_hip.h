@@ -705,6 +705,35 @@ typedef struct vdetr_adamw_desc {
   double lr, beta1, beta2, eps, weight_decay;
 } vdetr_adamw_desc;
 int vdetr_adamw_clip_f32(const vdetr_adamw_desc* d, vdetr_stream_t stream);
+/* The same launch with a per-step learning rate and a no-decay mask (engine.py:24-56: a new rate before every iteration;
+ * optimizer.py:4-26: --filter_biases_wd).  The fields of vdetr_adamw_desc, then:
+ *   lr_table [n_lr] doubles on the DEVICE: the step uses lr_table[clamp((long)*step + lr_offset, 0, n_lr - 1)], *step read before its
+ *     increment (entry 0 for the first step).  NULL (with n_lr <= 0): the rate is `lr`.  The entries are the host's: not checked here.
+ *   decay_mask [(n + 31) / 32] words on the device: element i is decayed (`p -= lr wd p`) iff bit i & 31 of word i >> 5 is set; a clear
+ *     bit skips the decay altogether.  NULL: every element is decayed.
+ *   lr_out (optional, device): the rate this step used.
+ * A captured graph replays the pointers and lr_offset, not the rate. */
+typedef struct vdetr_adamw_sched_desc {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t n;
+  float* step;
+  uint32_t* ticket;
+  const float* sumsq;
+  int32_t nsumsq;
+  float max_norm;
+  float norm_eps;
+  float* norm_out;
+  double lr, beta1, beta2, eps, weight_decay;
+  const double* lr_table;
+  int64_t n_lr;
+  int64_t lr_offset;
+  const uint32_t* decay_mask;
+  double* lr_out;
+} vdetr_adamw_sched_desc;
+int vdetr_adamw_sched_f32(const vdetr_adamw_sched_desc* d, vdetr_stream_t stream);
 /* partial[b] = sum of squares of slice b of g [n] (npartial = vdetr_sumsq_blocks(n)): the norm's first half where the flat gradient
  * changed after the pack (all-reduce, N > 1). */
 int vdetr_sumsq_blocks(long n);

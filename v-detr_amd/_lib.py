@@ -205,6 +205,13 @@ class AdamWDesc(ctypes.Structure):
         (n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
 
 
+class AdamWSchedDesc(ctypes.Structure):
+    """Mirror of ``vdetr_adamw_sched_desc``."""
+
+    _fields_ = AdamWDesc._fields_ + [("lr_table", c_void_p), ("n_lr", ctypes.c_int64), ("lr_offset", ctypes.c_int64),
+                                     ("decay_mask", c_void_p), ("lr_out", c_void_p)]
+
+
 class PosMlpDesc(ctypes.Structure):
     """Mirror of ``vdetr_posmlp_desc``."""
 
@@ -399,6 +406,7 @@ _SIGNATURES = {
     "vdetr_pack_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "vdetr_pack_sumsq_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vdetr_adamw_clip_f32": (c_int, [ctypes.POINTER(AdamWDesc), c_void_p]),
+    "vdetr_adamw_sched_f32": (c_int, [ctypes.POINTER(AdamWSchedDesc), c_void_p]),
     "vdetr_cpb_tables_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3),
     "vdetr_sumsq_blocks": (c_int, [ctypes.c_long]),
     "vdetr_sumsq_f32": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_int, c_void_p]),

@@ -130,6 +130,95 @@ __global__ __launch_bounds__(kOptThreads) void adamw_clip_kernel(AdamArgs A) {
   }
 }
 
+// ---- the same launch with a per-step learning rate and a no-decay mask (vdetr_adamw_sched_f32) ------------------------------------
+// Reference: engine.py:24-56 (a new rate before every iteration) and optimizer.py:4-26 (--filter_biases_wd: no decay for 1-D
+// parameters and *.bias).  A kernel of its own rather than two more branches in adamw_clip_kernel: the launch bench.py measures keeps
+// its code.  Two differences from the body above:
+//   * the rate is lr_table[clamp(*step + lr_offset, 0, n_lr - 1)] (*step before the increment; every workgroup reads the same entry
+//     out of L2).  The table holds the host's doubles: a captured graph replays the POINTER and the offset, the rate moves with the
+//     device-resident count.  Workgroup 0 leaves the rate it used in lr_out.
+//   * element i is decayed only where bit i & 31 of decay_mask[i >> 5] is set; a clear bit skips `p -= lr wd p` (no multiply by
+//     zero: what torch does for a group with weight_decay == 0).  The four bits of a float4 are one nibble of one word, which the
+//     eight lanes that share it load as the same dword (one 32-B piece of a cache line per wave and float4 row).
+struct AdamSchedArgs {
+  AdamArgs a;
+  const double* lr_table;    // nullptr: a.lr
+  long n_lr, lr_offset;
+  const unsigned* mask;      // nullptr: every element is decayed
+  double* lr_out;            // optional
+};
+
+__global__ __launch_bounds__(kOptThreads) void adamw_sched_kernel(AdamSchedArgs S) {
+  __shared__ double red[4];
+  const AdamArgs& A = S.a;
+  const float step0 = *A.step, step = step0 + 1.f;
+  double lr = A.lr;
+  if (S.lr_table) {
+    long k = (long)step0 + S.lr_offset;
+    k = k < 0 ? 0 : (k > S.n_lr - 1 ? S.n_lr - 1 : k);
+    lr = S.lr_table[k];
+  }
+  if (S.lr_out && blockIdx.x == 0 && threadIdx.x == 0) *S.lr_out = lr;
+  float scale = 1.f;
+  if (A.partial) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < A.npartial; i += kOptThreads) s += (double)A.partial[i];
+    const float norm = (float)sqrt(opt_block_sum(s, red));
+    scale = fmaxf((norm + A.norm_eps) / A.max_norm, 1.f);
+    if (A.norm_out && blockIdx.x == 0 && threadIdx.x == 0) *A.norm_out = norm;
+  }
+  const float bias1 = (float)(1.0 - pow(A.beta1, (double)step));
+  const float bias2 = (float)(1.0 - pow(A.beta2, (double)step));
+  const float step_size = (float)(lr / (double)bias1);
+  const float bias2_sqrt = sqrtf(bias2);
+  const float decay = (float)(lr * A.weight_decay);
+  const float w1 = (float)(1.0 - A.beta1), b2 = (float)A.beta2, w2 = (float)(1.0 - A.beta2), eps = (float)A.eps;
+  const bool clip = A.partial != nullptr;
+  const long n4 = A.n >> 2;
+  f32x4* p4 = reinterpret_cast<f32x4*>(A.p);
+  f32x4* m4 = reinterpret_cast<f32x4*>(A.m);
+  f32x4* v4 = reinterpret_cast<f32x4*>(A.v);
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(A.g);
+  const long stride = (long)gridDim.x * kOptThreads;
+  auto update = [&](float& p, float g, float& m, float& v, bool decayed) {
+    if (clip) g = g / scale;
+    if (decayed) p -= decay * p;
+    m = fmaf(w1, g - m, m);
+    v = b2 * v + w2 * g * g;
+    const float denom = sqrtf(v) / bias2_sqrt + eps;
+    p -= step_size * m / denom;
+  };
+  for (long i = (long)blockIdx.x * kOptThreads + threadIdx.x; i < n4; i += stride) {
+    // float4 i = elements 4 i .. 4 i + 3 = bits 4 (i & 7) .. of word i >> 3
+    const unsigned bits = S.mask ? S.mask[i >> 3] >> (((unsigned)i & 7u) * 4u) : 15u;
+    f32x4 p = p4[i], m = m4[i], v = v4[i];
+    const f32x4 g = g4[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = p[e], me = m[e], ve = v[e];
+      update(pe, g[e], me, ve, (bits >> e) & 1u);
+      p[e] = pe; m[e] = me; v[e] = ve;
+    }
+    p4[i] = p; m4[i] = m; v4[i] = v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(A.n & 3)) {
+    const long i = (n4 << 2) + threadIdx.x;
+    const bool decayed = S.mask ? (S.mask[i >> 5] >> ((unsigned)i & 31u)) & 1u : true;
+    float p = A.p[i], m = A.m[i], v = A.v[i];
+    update(p, A.g[i], m, v, decayed);
+    A.p[i] = p; A.m[i] = m; A.v[i] = v;
+  }
+  // the step count goes back as in adamw_clip_kernel: by the workgroup that draws the last ticket
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = atomicAdd(A.ticket, 1u);
+    if (t == gridDim.x - 1) {
+      *A.step = step;
+      atomicExch(A.ticket, 0u);
+    }
+  }
+}
+
 }  // namespace vdetr
 
 using namespace vdetr;
@@ -169,4 +258,34 @@ extern "C" int vdetr_adamw_clip_f32(const vdetr_adamw_desc* d, vdetr_stream_t st
   blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
   hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)blocks), dim3(kOptThreads), 0, (hipStream_t)stream, A);
   return check_launch("adamw_clip");
+}
+
+extern "C" int vdetr_adamw_sched_f32(const vdetr_adamw_sched_desc* d, vdetr_stream_t stream) {
+  VDETR_REQUIRE(d != nullptr, "adamw_sched: null descriptor");
+  VDETR_REQUIRE(d->param && d->grad && d->exp_avg && d->exp_avg_sq && d->step && d->ticket && d->n > 0, "adamw_sched: null pointer or empty buffer");
+  VDETR_REQUIRE((((uintptr_t)d->param | (uintptr_t)d->grad | (uintptr_t)d->exp_avg | (uintptr_t)d->exp_avg_sq) & 15) == 0,
+                "adamw_sched: the four buffers must be 16-B aligned");
+  VDETR_REQUIRE(d->lr >= 0.0 && d->beta1 >= 0.0 && d->beta1 < 1.0 && d->beta2 >= 0.0 && d->beta2 < 1.0 && d->eps >= 0.0 && d->weight_decay >= 0.0,
+                "adamw_sched: lr %g betas (%g, %g) eps %g weight_decay %g", d->lr, d->beta1, d->beta2, d->eps, d->weight_decay);
+  VDETR_REQUIRE(!d->sumsq || (d->nsumsq > 0 && d->max_norm > 0.f), "adamw_sched: %d partial sums, max_norm %g", d->nsumsq, d->max_norm);
+  VDETR_REQUIRE(d->lr_table ? d->n_lr > 0 : d->n_lr <= 0, "adamw_sched: lr_table %s with n_lr %ld", d->lr_table ? "given" : "null", (long)d->n_lr);
+  VDETR_REQUIRE(((uintptr_t)d->lr_table & 7) == 0 && ((uintptr_t)d->lr_out & 7) == 0, "adamw_sched: lr_table and lr_out must be 8-B aligned");
+  VDETR_REQUIRE(((uintptr_t)d->decay_mask & 3) == 0, "adamw_sched: decay_mask must be 4-B aligned");
+  AdamSchedArgs S;
+  AdamArgs& A = S.a;
+  A.p = d->param; A.g = d->grad; A.m = d->exp_avg; A.v = d->exp_avg_sq;
+  A.n = (long)d->n;
+  A.step = d->step; A.ticket = d->ticket;
+  A.partial = d->sumsq; A.npartial = d->nsumsq;
+  A.max_norm = d->max_norm; A.norm_eps = d->norm_eps;
+  A.norm_out = d->norm_out;
+  A.lr = d->lr; A.beta1 = d->beta1; A.beta2 = d->beta2; A.eps = d->eps; A.weight_decay = d->weight_decay;
+  S.lr_table = d->lr_table; S.n_lr = (long)d->n_lr; S.lr_offset = (long)d->lr_offset;
+  S.mask = d->decay_mask; S.lr_out = d->lr_out;
+  const long n4 = A.n / 4;
+  long blocks = (n4 + kOptThreads * 4 - 1) / (kOptThreads * 4);  // the launch shape of vdetr_adamw_clip_f32
+  const long cap = (long)device_cu_count() * 16;
+  blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
+  hipLaunchKernelGGL(adamw_sched_kernel, dim3((unsigned)blocks), dim3(kOptThreads), 0, (hipStream_t)stream, S);
+  return check_launch("adamw_sched");
 }

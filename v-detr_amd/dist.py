@@ -72,7 +72,7 @@ class FlatParams:
         bucket_views=True), whose buckets then complete roughly back to front while the backward pass is still running;
         "first" groups the shapes of the ``first`` part only (a captured decoder in front of an eager backbone).
         (A flat optimizer state saved under one layout does not line up with the other: persist it per parameter —
-        ``state_dict_per_parameter`` — not as the flat tensor.)"""
+        ``per_param_optimizer_state`` / ``load_per_param_optimizer_state`` — not as the flat tensor.)"""
         plist = [p for p in params if p.requires_grad]
         first_ids = {id(p) for p in (first or [])}
         assert plist, "no trainable parameters"
@@ -247,6 +247,22 @@ class FlatParams:
                 vec[o:o + p.numel()] = 1.0 - lr * weight_decay
         return vec
 
+    def decay_mask(self, named_params, filter_biases_wd=True):
+        """The same rule as one BIT per element of the flat buffer, for ``optim.ClipAdamW(decay_mask=...)``: int32 words on the
+        buffer's device, bit ``i & 31`` of word ``i >> 5`` set = element i gets weight decay ((n + 31) // 32 words).  Alignment and
+        slot padding are 0 (they stay zero anyway); ``filter_biases_wd=False`` marks every parameter's elements."""
+        import numpy as np
+        n = self.data.numel()
+        bits = np.zeros((n + 31) // 32 * 32, dtype=np.uint8)
+        names = {id(p): name for name, p in named_params}
+        for p in self.params:
+            exempt = filter_biases_wd and (p.ndim == 1 or names.get(id(p), "").endswith("bias"))
+            if not exempt:
+                o = self.offsets[id(p)]
+                bits[o:o + p.numel()] = 1
+        words = np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)  # byte k = bits 8 k .. 8 k + 7
+        return torch.from_numpy(words.astype(np.uint32).view(np.int32)).to(self.data.device)
+
     def per_param_optimizer_state(self, opt, params=None):
         """The one-tensor AdamW state (``exp_avg`` / ``exp_avg_sq`` of the flat buffer) as the per-parameter state
         dictionaries a per-parameter ``torch.optim.AdamW`` over ``params`` (default: this buffer's parameters, e.g. in
@@ -274,7 +290,9 @@ class FlatParams:
         for k in ("exp_avg", "exp_avg_sq"):
             st.setdefault(k, torch.zeros_like(self.data))
         if steps:
-            step = torch.tensor(steps.pop(), dtype=torch.float32, device=self.data.device if opt.defaults.get("capturable") else "cpu")
+            # on the device where the optimizer's kernel reads it (torch's capturable ones, optim.ClipAdamW), else torch's host scalar
+            on_device = opt.defaults.get("capturable") or getattr(opt, "step_on_device", False)
+            step = torch.tensor(steps.pop(), dtype=torch.float32, device=self.data.device if on_device else "cpu")
             st["step"] = step
         with torch.no_grad():
             for p, d in zip(plist, states):
@@ -282,6 +300,8 @@ class FlatParams:
                 for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"):
                     if k in d:
                         st.setdefault(k, torch.zeros_like(self.data))[o:o + n].copy_(d[k].reshape(-1))
+        if hasattr(opt, "_check_state"):  # optim.ClipAdamW: what its kernel is about to read
+            opt._check_state()
 
     def clip_scale(self, max_norm, eps=1e-6):
         """1 / clip coefficient of ``clip_grad_norm_(params, max_norm)`` as a device scalar: max(||g|| / max_norm, 1).
