@@ -1040,6 +1040,43 @@ int vdetr_append_height_f32(const vdetr_color_aug_desc* desc, const int32_t* off
 int vdetr_sunrgbd_color_f32(const vdetr_color_aug_desc* desc, const int32_t* offsets_host, vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Area-weighted vertex normals of a scan's mesh, --use_normals (reference datasets/scannet.py:394-420).  The
+ * reference adds every face's weighted normal to its three vertices in a serial loop over the faces; the result depends on
+ * the order of additions PER VERTEX only, so adding each vertex's incident faces in ascending face index gives the loop's
+ * bits.  All float32, every operation one IEEE operation (no fma, correctly rounded / and sqrt, subnormals kept):
+ *   u = p1 - p0, v = p2 - p0;  c = (u1*v2 - u2*v1, u2*v0 - u0*v2, u0*v1 - u1*v0)
+ *   len = sqrt((c0*c0 + c1*c1) + c2*c2) + 1e-8f;  w = (c / len) * (len * 0.5f)
+ *   n[v] = 0 + w[f_1] + w[f_2] + ... over the corners that name v, ascending f (a face that names v twice is added twice: its
+ *   weight is +-0 for finite coordinates);  out = n / (sqrt((n0*n0 + n1*n1) + n2*n2) + 1e-8f)
+ * Seven launches whatever B: clear the counts; one lane per face: w and the corners per vertex (integer atomics); the
+ * exclusive scan of the counts (tile sums, their scan, the starts); one lane per face: the vertex -> faces lists, slots
+ * drawn by integer atomics in any order; one lane per vertex: the list put in ascending order and summed (a list longer than
+ * VDETR_NORMALS_SHORT is sorted and summed by the vertex's whole workgroup).  No float atomics: two runs give the same bits.
+ * A face that names a vertex outside [0, vertices of its scene) is never followed: its in-range vertices get NaN normals.
+ * A vertex no face names gets 0, 0, 0; a scene without faces is legal, a scene without vertices is an argument error.
+ * ---------------------------------------------------------------------------------------------- */
+#define VDETR_NORMALS_TILE 256       /* faces / vertices per workgroup */
+#define VDETR_NORMALS_SCAN_TILE 1024 /* vertices per workgroup of the scan's kernels */
+#define VDETR_NORMALS_SHORT 32       /* longest list that one lane orders by itself */
+typedef struct vdetr_normals_desc {
+  int32_t B;            /* scenes (<= 4096) */
+  int32_t vert_stride;  /* floats per row of `vertices` (>= 3; xyz first) */
+  int32_t out_stride;   /* floats per row of `out` (>= 3) */
+  int32_t faces_i64;    /* faces hold int64 (1) or int32 (0) */
+  const float* vertices;        /* [vert_offsets[B], vert_stride] */
+  const void* faces;            /* [face_offsets[B], 3] indices local to the face's scene */
+  const int32_t* vert_offsets;  /* [B+1] DEVICE copy of vert_offsets_host */
+  const int32_t* face_offsets;  /* [B+1] DEVICE copy of face_offsets_host */
+  float* out;                   /* row r of the packed batch: out[r * out_stride + 0 .. 2]; nothing else is written */
+} vdetr_normals_desc;
+/* Both offset arrays are HOST arrays read at call time.  With N vertices, F faces and T = ceil(N / VDETR_NORMALS_SCAN_TILE)
+ * the workspace holds, each rounded up to 256 B: w [F,3] f32, counts / starts / cursors [N] i32 each, tile sums [T] i32 and
+ * the lists [3F] i32, plus 256 B; it only lives for the call.  N and 3F must stay below 2^31. */
+size_t vdetr_vertex_normals_workspace_bytes(const int32_t* vert_offsets_host, const int32_t* face_offsets_host, int B);
+int vdetr_vertex_normals_f32(const vdetr_normals_desc* desc, const int32_t* vert_offsets_host, const int32_t* face_offsets_host,
+                             void* workspace, size_t workspace_bytes, vdetr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Greedy 3-D NMS of a scene's predictions (reference utils/nms.py:78-162 nms_3d_faster /
  * nms_3d_faster_samecls as called from utils/ap_calculator.py:165-220 on the min / max extents of the 8 box corners).
  * corners (B,K,8,3) f32, score (B,K) f32, cls (B,K) i32 or NULL (class-agnostic nms_3d_faster), valid (B,K) u8 or NULL

@@ -316,6 +316,16 @@ class ColorAugDesc(ctypes.Structure):
         (n, c_void_p) for n in ("points", "offsets", "out", "params", "keep", "noise", "select")]
 
 
+VDETR_NORMALS_TILE, VDETR_NORMALS_SCAN_TILE, VDETR_NORMALS_SHORT = 256, 1024, 32
+
+
+class NormalsDesc(ctypes.Structure):
+    """Mirror of ``vdetr_normals_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "vert_stride", "out_stride", "faces_i64")] + [
+        (n, c_void_p) for n in ("vertices", "faces", "vert_offsets", "face_offsets", "out")]
+
+
 class SpBnDesc(ctypes.Structure):
     """Mirror of ``vdetr_spbn_desc``."""
 
@@ -430,6 +440,8 @@ _SIGNATURES = {
     "vdetr_color_augment_f32": (c_int, [ctypes.POINTER(ColorAugDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
     "vdetr_append_height_f32": (c_int, [ctypes.POINTER(ColorAugDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
     "vdetr_sunrgbd_color_f32": (c_int, [ctypes.POINTER(ColorAugDesc), c_void_p, c_void_p]),
+    "vdetr_vertex_normals_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int]),
+    "vdetr_vertex_normals_f32": (c_int, [ctypes.POINTER(NormalsDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vdetr_sp_kernel_map_i32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vdetr_sp_inverse_map_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_sp_gather_cols_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

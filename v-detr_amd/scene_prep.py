@@ -11,8 +11,13 @@ the ``choices`` that ``prepare_scenes`` takes.  Before the crop come the per-poi
 csrc/color_aug.hip): ``draw_color_augment`` + ``augment_colors`` are the four ``--use_color`` augmentations, ``append_height`` is
 ``use_height``; after ``prepare_scenes`` comes ``draw_sunrgbd_color`` + ``sunrgbd_color_augment`` (``--coloraug_sunrgbd``,
 :544-560).  One generator per scene, used in that order, is left where the reference leaves ``np.random``, so a raw
-``_vert.npy`` array goes to the device once.  File reading, the split lists, ``use_normals`` and ``use_superpoint`` stay with the
-loader.  No CPU path.
+``_vert.npy`` array goes to the device once.  ``vertex_normals`` + ``with_normals`` are ``--use_normals`` (scannet.py:394-420 and
+:457-458, DESIGN.md 6.6, csrc/normals.hip): the area-weighted vertex normals of the scan's mesh become columns 6:9 of a
+``use_color`` cloud.  The call order is ``augment_colors`` -> normals -> ``append_height`` -> ``crop_and_sample`` ->
+``prepare_scenes`` -> ``sunrgbd_color_augment``; flips and the rotation touch columns 0:3 only, so the normals are not turned,
+as in the reference.  Normals depend on the raw mesh alone and draw nothing from the generator, so a caller may compute them
+once per scan and keep them (no such cache is built here).  File reading (the ``.ply``, the split lists) and ``use_superpoint``
+stay with the loader.  No CPU path.
 """
 import ctypes
 from dataclasses import dataclass
@@ -578,3 +583,87 @@ def sunrgbd_color_augment(point_clouds, offsets, params):
 
 def _launch_sunrgbd(d, host_offsets, alive):
     L.check(L.lib().vdetr_sunrgbd_color_f32(ctypes.byref(d), host_offsets, L.stream_ptr()), "sunrgbd_color")
+
+
+# ---- --use_normals: area-weighted vertex normals of the scan's mesh (csrc/normals.hip) ------------------------------
+def vertex_normals(vertices, vert_offsets, faces, face_offsets, *, out=None):
+    """``vertex_normal(coords, faces)`` of scannet.py:398-420 for a packed batch of meshes: vertices [N,3+] f32 (xyz first; any
+    row stride, e.g. the seven columns ``read_plymesh`` returns), vert_offsets [B+1] as in ``prepare_scenes``, faces [F,3] int32 /
+    int64 with indices local to their scene (a host array or a device tensor), face_offsets [B+1] (a scene without faces is
+    legal) -> [N,3] f32 on the device, bit for bit the reference's serial loop: every vertex adds its incident faces' weights
+    in ascending face index.  A vertex that no face names gets 0, 0, 0.  With ``out`` ([N,3] f32 on the device, rows strided at
+    will, e.g. ``cloud9[:, 6:9]``) the normals are written there and ``out`` is returned; nothing else of its storage is touched.
+
+    A host ``faces`` array is range-checked here; a device tensor cannot be without a synchronisation: the kernels turn a face
+    with an index outside its scene into NaN normals for the face's in-range vertices and follow none of its indices.  Seven
+    launches on the current stream whatever B, no synchronisation, two runs give the same bits.  No CPU path."""
+    L.require_float(vertices, "vertices")
+    dev = vertices.device
+    voff = _host_i32(vert_offsets, "vert_offsets")
+    foff = _host_i32(face_offsets, "face_offsets")
+    B = len(voff) - 1
+    if len(foff) != B + 1:
+        raise ValueError(f"face_offsets must hold {B + 1} offsets like vert_offsets, got {len(foff)}")
+    if vertices.dim() != 2 or vertices.shape[1] < 3 or vertices.stride(1) != 1 or vertices.stride(0) < 3:
+        raise ValueError(f"vertices must be [N, 3 or more columns] with unit column stride, got {tuple(vertices.shape)}")
+    N = vertices.shape[0]
+    if voff[0] != 0 or voff[-1] != N or N >= 2 ** 31:
+        raise ValueError(f"vert_offsets run from {voff[0]} to {voff[-1]}, vertices has {N} rows")
+    sizes = np.diff(voff)
+    if (sizes <= 0).any():
+        raise ValueError(f"scene {int(np.argmax(sizes <= 0))} has no vertices")
+    if not torch.is_tensor(faces):
+        faces = torch.from_numpy(np.ascontiguousarray(faces))
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"faces must be int32 / int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+    F = faces.shape[0]
+    if foff[0] != 0 or foff[-1] != F or (np.diff(foff) < 0).any() or 3 * F >= 2 ** 31:
+        raise ValueError(f"face_offsets run from {foff[0]} to {foff[-1]} (they may not decrease), faces has {F} rows")
+    if not faces.is_cuda:
+        f = faces.numpy()
+        if (f < 0).any() or (f >= np.repeat(sizes, np.diff(foff))[:, None]).any():
+            raise ValueError("faces name a vertex outside their scene")
+    L.require_gpu(vertices, "vertices")                                # after the host checks, which need no device
+    if not faces.is_cuda:
+        faces = faces.to(dev, non_blocking=True)
+    faces = faces.detach().contiguous()
+    vertices = vertices.detach()
+    if out is None:
+        out = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    else:
+        L.require_gpu(out, "out")
+        L.require_float(out, "out")
+        if tuple(out.shape) != (N, 3) or (N and (out.stride(1) != 1 or out.stride(0) < 3)) or out.device != dev:
+            raise ValueError(f"out must be a [{N}, 3] view with unit column stride on {dev}, got {tuple(out.shape)}")
+    if B == 0:
+        return out
+    voff32, foff32 = np.ascontiguousarray(voff, dtype=np.int32), np.ascontiguousarray(foff, dtype=np.int32)
+    voff_dev = torch.from_numpy(voff32).to(dev, non_blocking=True)
+    foff_dev = torch.from_numpy(foff32).to(dev, non_blocking=True)
+    d = L.NormalsDesc()
+    d.B, d.vert_stride, d.out_stride, d.faces_i64 = B, vertices.stride(0), out.stride(0), int(faces.dtype == torch.int64)
+    d.vertices, d.faces, d.out = vertices.data_ptr(), faces.data_ptr(), out.data_ptr()
+    d.vert_offsets, d.face_offsets = voff_dev.data_ptr(), foff_dev.data_ptr()
+    vhost, fhost = voff32.ctypes.data_as(ctypes.c_void_p), foff32.ctypes.data_as(ctypes.c_void_p)
+    nbytes = L.lib().vdetr_vertex_normals_workspace_bytes(vhost, fhost, B)
+    ws = L.workspace(nbytes, dev)
+    _launch_normals(d, vhost, fhost, ws, nbytes, (vertices, faces, out, voff_dev, foff_dev, voff32, foff32))
+    return out
+
+
+def _launch_normals(d, vert_host, face_host, ws, nbytes, alive):
+    """the seven launches on the current stream (tools/normals_bench.py times exactly these)"""
+    L.check(L.lib().vdetr_vertex_normals_f32(ctypes.byref(d), vert_host, face_host, L.ptr(ws), nbytes, L.stream_ptr()), "vertex_normals")
+
+
+def with_normals(points6, normals):
+    """scannet.py:457-458: points6 [N,6] f32 (xyz, rgb: the reference appends normals under ``use_color`` only) and normals [N,3]
+    -> the [N,9] cloud.  To skip this copy, allocate the [N,9] cloud first and pass ``cloud9[:, 6:9]`` as ``vertex_normals``' out."""
+    if points6.dim() != 2 or points6.shape[1] != 6:
+        raise ValueError(f"with_normals: points6 must be [N, 6] (normals are appended to a use_color cloud), got {tuple(points6.shape)}")
+    if tuple(normals.shape) != (points6.shape[0], 3):
+        raise ValueError(f"with_normals: normals must be [{points6.shape[0]}, 3], got {tuple(normals.shape)}")
+    for t, name in ((points6, "points6"), (normals, "normals")):
+        L.require_gpu(t, name)
+        L.require_float(t, name)
+    return torch.cat((points6, normals), 1)
