@@ -119,3 +119,20 @@ def fixed_salts(monkeypatch, base=0x7E570000):
     monkeypatch.setattr(add_ln, "_salts", itertools.count(base + 0x1000))
     monkeypatch.setattr(bn_act, "_salts", itertools.count(base + 0x2000))
     monkeypatch.setattr(vdetr_transformer, "_salt_counter", itertools.count(base + 0x3000))
+
+
+# ---- the scene preparation's GPU tests (test_gpu_scene_prep / cuboid / color_aug / normals) -------------------------------------------
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+
+
+def cfg():
+    from vdetr_amd.dataset_config import ScannetDatasetConfig
+    return ScannetDatasetConfig()
+
+
+def same_bits(got, want):
+    """torch.equal on the int32 views: got a device / host tensor, want a numpy float32 array"""
+    got = got.detach().cpu().contiguous()
+    want = torch.from_numpy(np.ascontiguousarray(want, dtype=np.float32))
+    return got.dtype == torch.float32 and got.shape == want.shape and torch.equal(got.view(torch.int32), want.view(torch.int32))

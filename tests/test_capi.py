@@ -113,6 +113,61 @@ def test_round5_operand_image_entry_points():
     assert b"attn_pack_kv" in lib.vdetr_last_error()
 
 
+def test_scene_preparation_entry_points_keep_their_messages():
+    """The eight launch entry points of scene_prep.hip, cuboid.hip, color_aug.hip and normals.hip: an empty scene and a missing
+    workspace (the six that take one) are refused on the host, before any launch, with exactly these texts.  They were recorded
+    from the library as it was before the four files came to share csrc/scene_tiles.h."""
+    import numpy as np
+    from vdetr_amd import _lib
+    lib = _lib.lib()
+    spare = np.zeros(64, np.uint8)                                       # an address for the pointer checks; nothing follows it
+
+    def filled(d, **fields):
+        for name, kind in d._fields_:
+            if kind is ctypes.c_void_p:
+                setattr(d, name, spare.ctypes.data)
+        for name, value in fields.items():
+            setattr(d, name, value)
+        return ctypes.byref(d)
+
+    prep = filled(_lib.ScenePrepDesc(), B=2, C=3, G=4, max_obj=64)
+    crop = filled(_lib.CuboidDesc(), B=2, W=3, G=4, T=100, min_points=10, num_points=16)
+    color = filled(_lib.ColorAugDesc(), B=2, W=6, noise_rows=813, out=spare.ctypes.data + 32)
+    mesh = filled(_lib.NormalsDesc(), B=2, vert_stride=3, out_stride=3)
+    faces = np.array([0, 10, 20], np.int32).ctypes.data_as(ctypes.c_void_p)
+    calls = {"scene_prep_points": lambda off: lib.vdetr_scene_prep_points_f32(prep, off, None, 0, None),
+             "scene_prep_targets": lambda off: lib.vdetr_scene_prep_targets_f32(prep, off, None, 0, None),
+             "cuboid_crop": lambda off: lib.vdetr_cuboid_crop_f32(crop, off, None, 0, None),
+             "cuboid_compose": lambda off: lib.vdetr_cuboid_compose_i32(crop, off, None),
+             "color_augment": lambda off: lib.vdetr_color_augment_f32(color, off, None, 0, None),
+             "append_height": lambda off: lib.vdetr_append_height_f32(color, off, None, 0, None),
+             "sunrgbd_color": lambda off: lib.vdetr_sunrgbd_color_f32(color, off, None),
+             "vertex_normals": lambda off: lib.vdetr_vertex_normals_f32(mesh, off, faces, None, 0, None)}
+    empty = np.array([0, 300, 300], np.int32)
+    no_rows = {"scene_prep_points": b"scene_prep: scene 1 has no points (offsets 300 .. 300)",
+               "scene_prep_targets": b"scene_prep: scene 1 has no points (offsets 300 .. 300)",
+               "cuboid_crop": b"cuboid: scene 1 has no points (offsets 300 .. 300)",
+               "cuboid_compose": b"cuboid: scene 1 has no points (offsets 300 .. 300)",
+               "color_augment": b"color_augment: scene 1 has no points (offsets 300 .. 300)",
+               "append_height": b"append_height: scene 1 has no points (offsets 300 .. 300)",
+               "sunrgbd_color": b"sunrgbd_color: scene 1 has no points (offsets 300 .. 300)",
+               "vertex_normals": b"vertex_normals: scene 1 has no vertices (offsets 300 .. 300)"}
+    assert sorted(no_rows) == sorted(calls)
+    for name, text in no_rows.items():
+        assert calls[name](empty.ctypes.data_as(ctypes.c_void_p)) == 1, name
+        assert lib.vdetr_last_error() == text, name
+    good = np.array([0, 300, 813], np.int32)
+    no_workspace = {"scene_prep_points": b"scene_prep: workspace 0 B < required 376 B",
+                    "scene_prep_targets": b"scene_prep: workspace 0 B < required 376 B",
+                    "cuboid_crop": b"cuboid_crop: workspace 0 B < required 24576 B",
+                    "color_augment": b"color_augment: workspace 0 B < required 768 B",
+                    "append_height": b"append_height: workspace 0 B < required 6656 B",
+                    "vertex_normals": b"vertex_normals: workspace 0 B < required 11008 B"}
+    for name, text in no_workspace.items():                              # cuboid_compose and sunrgbd_color take no workspace
+        assert calls[name](good.ctypes.data_as(ctypes.c_void_p)) == 3, name
+        assert lib.vdetr_last_error() == text, name
+
+
 def test_ops_refuse_cpu_tensors():
     """No CPU fallback: the reference asserts "CPU not supported" (sampling.cpp:36,62,84)."""
     from vdetr_amd import pointnet2_utils as PU

@@ -10,21 +10,13 @@ import pytest
 import torch
 
 import color_aug_restatement as CA
+from helpers import cfg, dev
 import scene_prep_restatement as SR
 from test_color_aug_restatement import CASES, COLOR_CASES, golden, settings_of, state_is
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 G = 64
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def cfg():
-    from vdetr_amd.dataset_config import ScannetDatasetConfig
-    return ScannetDatasetConfig()
 
 
 def same(got, want):

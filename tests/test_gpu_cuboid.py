@@ -10,21 +10,12 @@ import pytest
 import torch
 
 import cuboid_restatement as CR
+from helpers import cfg, dev
 import scene_prep_restatement as SR
 from test_cuboid_restatement import CASES, batch_of, golden, state_is
 from test_scene_prep_restatement import same_bits
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def cfg():
-    from vdetr_amd.dataset_config import ScannetDatasetConfig
-    return ScannetDatasetConfig()
 
 
 def run(a, randoms, num_points, min_points, **kw):

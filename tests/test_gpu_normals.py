@@ -9,23 +9,13 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import dev, same_bits
 import normals_restatement as NR
 from test_normals_restatement import PLAIN_CASES, fan_hub, golden, settings_of, state_is
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 G = 64
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def same_bits(got, want):
-    """torch.equal on the int32 views: got a device / host tensor, want a numpy float32 array"""
-    got = got.detach().cpu().contiguous()
-    want = torch.from_numpy(np.ascontiguousarray(want, dtype=np.float32))
-    return got.dtype == torch.float32 and got.shape == want.shape and torch.equal(got.view(torch.int32), want.view(torch.int32))
 
 
 def one(c, faces=None, **kw):

@@ -11,21 +11,13 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import cfg, dev
 import scene_prep_restatement as SR
 from test_scene_prep_restatement import CASES, golden, params_of, same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 FLOATS, EXACT = SR.FLOAT_KEYS, SR.EXACT_KEYS
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def cfg():
-    from vdetr_amd.dataset_config import ScannetDatasetConfig
-    return ScannetDatasetConfig()
 
 
 def run(c, params=None, **kw):

@@ -13,7 +13,7 @@
 // Partials go out with ordinary stores: no global atomics, no ticket (README "Two findings about the chip"); the LDS
 // histograms count integers, so two runs give the same bits.  -ffp-contract=off as everywhere: every product and sum below
 // is one IEEE operation, in the dtype numpy uses for it (include/vdetr_hip.h).
-#include "wave.h"
+#include "scene_tiles.h"
 
 namespace vdetr {
 namespace {
@@ -23,28 +23,7 @@ constexpr int kSelTile = VDETR_HEIGHT_TILE;
 constexpr int kSelRows = kSelTile / 256;     // rows per lane of the histogram kernel
 constexpr int kSel = 3;                      // order statistics selected at once
 constexpr int kBins = 256;
-constexpr int kMaxScenes = 4096;
 constexpr int kBound = 9;                    // floats per tile / scene: min rgb, max rgb, then "holds a NaN" rgb or the scale rgb
-
-__device__ __forceinline__ int tiles_of(int rows, int tile) { return (rows + tile - 1) / tile; }
-
-// scene and tile within it of tile t (tiles never straddle scenes); uniform over the workgroup
-__device__ __forceinline__ bool locate_tile(const int32_t* offsets, int B, int tile, int t, int& b, int& local_tile) {
-  int acc = 0;
-  for (b = 0; b < B; ++b) {
-    const int nt = tiles_of(offsets[b + 1] - offsets[b], tile);
-    if (t < acc + nt) break;
-    acc += nt;
-  }
-  local_tile = t - acc;
-  return b < B;
-}
-
-__device__ __forceinline__ int first_tile(const int32_t* offsets, int b, int tile) {
-  int first = 0;
-  for (int i = 0; i < b; ++i) first += tiles_of(offsets[i + 1] - offsets[i], tile);
-  return first;
-}
 
 __device__ __forceinline__ bool drops(const vdetr_color_aug_desc& d, int b) {
   return d.keep != nullptr && d.params[(size_t)b * VDETR_COLOR_AUG_PARAMS + 7] != 0.0;
@@ -73,18 +52,7 @@ __global__ __launch_bounds__(kTile) void color_bounds_kernel(vdetr_color_aug_des
       }
     }
   }
-  const int wave = tid / kWave;
-#pragma unroll
-  for (int k = 0; k < kBound; ++k) {
-    const float r = k < 3 ? wave_allmin_f32(v[k]) : wave_allmax_f32(v[k]);
-    if ((tid & (kWave - 1)) == 0) red[wave][k] = r;
-  }
-  __syncthreads();
-  if (tid < kBound) {
-    float r = red[0][tid];
-    for (int w = 1; w < kTile / kWave; ++w) r = tid < 3 ? fminf(r, red[w][tid]) : fmaxf(r, red[w][tid]);
-    bounds[(size_t)t * kBound + tid] = r;
-  }
+  store_tile_partial(v, red, bounds, t);
 }
 
 __global__ __launch_bounds__(kWave) void color_scale_kernel(vdetr_color_aug_desc d, int num_tiles, const float* bounds, float* scene) {
@@ -343,24 +311,29 @@ __global__ __launch_bounds__(kTile) void sunrgbd_color_kernel(vdetr_color_aug_de
   }
 }
 
-long count_tiles(const int32_t* offsets_host, int B, int tile, const char* op) {
-  long tiles = 0;
-  for (int b = 0; b < B; ++b) {
-    const long n = (long)offsets_host[b + 1] - offsets_host[b];
-    if (n <= 0 || offsets_host[b] < 0) {
-      if (op) set_error("%s: scene %d has no points (offsets %d .. %d)", op, b, offsets_host[b], offsets_host[b + 1]);
-      return -1;
-    }
-    tiles += (n + tile - 1) / tile;
-  }
-  return tiles;
+// the two workspaces
+struct ColorWork {
+  float* bounds;      // [tiles, kBound]
+  float* scene;       // [B, kBound] lo, hi, scale
+};
+
+ColorWork lay_out_color(Carver& c, long tiles, int B) {
+  ColorWork w;
+  w.bounds = c.take<float>((size_t)tiles * kBound);
+  w.scene = c.take<float>((size_t)B * kBound);
+  return w;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct HeightWork {
+  unsigned* partial;  // [tiles, kSel, kBins] a pass's histograms
+  unsigned* state;    // [B, kSel, 2]
+};
 
-size_t color_bytes(long tiles, int B) { return align256((size_t)tiles * kBound * sizeof(float)) + align256((size_t)B * kBound * sizeof(float)); }
-size_t height_bytes(long tiles, int B) {
-  return align256((size_t)tiles * kSel * kBins * sizeof(unsigned)) + align256((size_t)B * kSel * 2 * sizeof(unsigned));
+HeightWork lay_out_height(Carver& c, long tiles, int B) {
+  HeightWork w;
+  w.partial = c.take<unsigned>((size_t)tiles * kSel * kBins);
+  w.state = c.take<unsigned>((size_t)B * kSel * 2);
+  return w;
 }
 
 int check_desc(const vdetr_color_aug_desc* d, const int32_t* offsets_host, const char* op) {
@@ -377,13 +350,19 @@ using namespace vdetr;
 extern "C" size_t vdetr_color_aug_workspace_bytes(const int32_t* offsets_host, int B) {
   if (!offsets_host || B <= 0) return 0;
   const long tiles = count_tiles(offsets_host, B, kTile, nullptr);
-  return tiles <= 0 ? 0 : color_bytes(tiles, B) + 256;
+  if (tiles <= 0) return 0;
+  Carver c(nullptr);
+  lay_out_color(c, tiles, B);
+  return c.bytes() + 256;
 }
 
 extern "C" size_t vdetr_append_height_workspace_bytes(const int32_t* offsets_host, int B) {
   if (!offsets_host || B <= 0) return 0;
   const long tiles = count_tiles(offsets_host, B, kSelTile, nullptr);
-  return tiles <= 0 ? 0 : height_bytes(tiles, B) + 256;
+  if (tiles <= 0) return 0;
+  Carver c(nullptr);
+  lay_out_height(c, tiles, B);
+  return c.bytes() + 256;
 }
 
 extern "C" int vdetr_color_augment_f32(const vdetr_color_aug_desc* desc, const int32_t* offsets_host, void* workspace, size_t workspace_bytes,
@@ -398,19 +377,14 @@ extern "C" int vdetr_color_augment_f32(const vdetr_color_aug_desc* desc, const i
   VDETR_REQUIRE(d.points && d.offsets && d.out && d.params, "color_augment: null pointer");
   VDETR_REQUIRE(d.points != d.out, "color_augment: out is the input");
   VDETR_REQUIRE(d.noise_rows >= 0 && (d.noise_rows == 0 || d.noise), "color_augment: %d noise rows without noise", d.noise_rows);
-  const size_t need = vdetr_color_aug_workspace_bytes(offsets_host, d.B);
-  if (!workspace || workspace_bytes < need) {
-    set_error("color_augment: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
-  const size_t at = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-  float* bounds = reinterpret_cast<float*>(at);
-  float* scene = reinterpret_cast<float*>(at + align256((size_t)tiles * kBound * sizeof(float)));
+  if (int e = require_workspace("color_augment", workspace, workspace_bytes, vdetr_color_aug_workspace_bytes(offsets_host, d.B))) return e;
+  Carver c(workspace);
+  const ColorWork w = lay_out_color(c, tiles, d.B);
   const int total = (int)offsets_host[d.B];
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(color_bounds_kernel, dim3((unsigned)tiles), dim3(kTile), 0, s, d, total, bounds);
-  hipLaunchKernelGGL(color_scale_kernel, dim3(d.B), dim3(kWave), 0, s, d, (int)tiles, (const float*)bounds, scene);
-  hipLaunchKernelGGL(color_apply_kernel, dim3((unsigned)tiles), dim3(kTile), 0, s, d, total, (const float*)scene);
+  hipLaunchKernelGGL(color_bounds_kernel, dim3((unsigned)tiles), dim3(kTile), 0, s, d, total, w.bounds);
+  hipLaunchKernelGGL(color_scale_kernel, dim3(d.B), dim3(kWave), 0, s, d, (int)tiles, (const float*)w.bounds, w.scene);
+  hipLaunchKernelGGL(color_apply_kernel, dim3((unsigned)tiles), dim3(kTile), 0, s, d, total, (const float*)w.scene);
   return check_launch("color_augment");
 }
 
@@ -425,22 +399,17 @@ extern "C" int vdetr_append_height_f32(const vdetr_color_aug_desc* desc, const i
   VDETR_REQUIRE(tiles <= 0x7fffffffL / (kSel * kBins), "append_height: %ld tiles", tiles);
   VDETR_REQUIRE(d.points && d.offsets && d.out && d.select, "append_height: null pointer");
   VDETR_REQUIRE(d.points != d.out, "append_height: out is the input");
-  const size_t need = vdetr_append_height_workspace_bytes(offsets_host, d.B);
-  if (!workspace || workspace_bytes < need) {
-    set_error("append_height: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
-  const size_t at = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-  unsigned* partial = reinterpret_cast<unsigned*>(at);
-  unsigned* state = reinterpret_cast<unsigned*>(at + align256((size_t)tiles * kSel * kBins * sizeof(unsigned)));
+  if (int e = require_workspace("append_height", workspace, workspace_bytes, vdetr_append_height_workspace_bytes(offsets_host, d.B))) return e;
+  Carver c(workspace);
+  const HeightWork w = lay_out_height(c, tiles, d.B);
   const int total = (int)offsets_host[d.B];
   const long write_tiles = count_tiles(offsets_host, d.B, 256, nullptr);
   hipStream_t s = (hipStream_t)stream;
   for (int shift = 24; shift >= 0; shift -= 8) {
-    hipLaunchKernelGGL(height_hist_kernel, dim3((unsigned)tiles), dim3(256), 0, s, d, total, shift, (const unsigned*)state, partial);
-    hipLaunchKernelGGL(height_pick_kernel, dim3(d.B), dim3(256), 0, s, d, (int)tiles, shift, (const unsigned*)partial, state);
+    hipLaunchKernelGGL(height_hist_kernel, dim3((unsigned)tiles), dim3(256), 0, s, d, total, shift, (const unsigned*)w.state, w.partial);
+    hipLaunchKernelGGL(height_pick_kernel, dim3(d.B), dim3(256), 0, s, d, (int)tiles, shift, (const unsigned*)w.partial, w.state);
   }
-  hipLaunchKernelGGL(height_write_kernel, dim3((unsigned)write_tiles), dim3(256), 0, s, d, total, (const unsigned*)state);
+  hipLaunchKernelGGL(height_write_kernel, dim3((unsigned)write_tiles), dim3(256), 0, s, d, total, (const unsigned*)w.state);
   return check_launch("append_height");
 }
 

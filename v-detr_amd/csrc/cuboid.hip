@@ -12,68 +12,37 @@
 // and vdetr_cuboid_compose_i32 one: choices[b, j] = kept_rows[b][drawn[b, j]].  Partials go out with ordinary stores: no
 // atomics, no ticket, nothing that depends on scheduling (README "Two findings about the chip"), so two runs give the same
 // bits.  Every decision is a comparison of exactly defined values (include/vdetr_hip.h), -ffp-contract=off as everywhere.
-#include "wave.h"
+#include "scene_tiles.h"
 
 namespace vdetr {
 namespace {
 
 constexpr int kTile = VDETR_CUBOID_TILE;
-constexpr int kMaxScenes = 4096;
 constexpr int kStat = 7;          // words per (tile, attempt): count, min xyz, max xyz
 constexpr int kBound = 9;         // floats per tile of the raw bounds: min xyz, max xyz, "holds a NaN" xyz
 
-__device__ __forceinline__ int tiles_of(int rows) { return (rows + kTile - 1) / kTile; }
-
-// scene and tile within it of tile t (tiles never straddle scenes); uniform over the workgroup
-__device__ __forceinline__ bool locate_tile(const int32_t* offsets, int B, int t, int& b, int& local_tile) {
-  int acc = 0;
-  for (b = 0; b < B; ++b) {
-    const int nt = tiles_of(offsets[b + 1] - offsets[b]);
-    if (t < acc + nt) break;
-    acc += nt;
-  }
-  local_tile = t - acc;
-  return b < B;
-}
-
-__device__ __forceinline__ int first_tile(const int32_t* offsets, int b) {
-  int first = 0;
-  for (int i = 0; i < b; ++i) first += tiles_of(offsets[i + 1] - offsets[i]);
-  return first;
-}
-
-// the workspace, carved the same way on both sides
-struct Carve {
+// the workspace
+struct Work {
   float* bounds;      // [tiles, kBound]
   double* crop;       // [B, T, 6] max xyz, min xyz of every attempt (NaN: the attempt is not valid)
   int32_t* stats;     // [tiles, T, kStat]
   int32_t* tile_base; // [tiles] rows the winning attempt keeps in the scene's earlier tiles
 };
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-size_t carve(const void* workspace, long tiles, int B, int T, Carve* c) {
-  size_t at = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-  const size_t start = (uintptr_t)workspace;
-  auto take = [&](size_t bytes) { const size_t p = at; at += align256(bytes); return p; };
-  const size_t bounds = take((size_t)tiles * kBound * sizeof(float));
-  const size_t crop = take((size_t)B * T * 6 * sizeof(double));
-  const size_t stats = take((size_t)tiles * T * kStat * sizeof(int32_t));
-  const size_t base = take((size_t)tiles * sizeof(int32_t));
-  if (c) {
-    c->bounds = reinterpret_cast<float*>(bounds);
-    c->crop = reinterpret_cast<double*>(crop);
-    c->stats = reinterpret_cast<int32_t*>(stats);
-    c->tile_base = reinterpret_cast<int32_t*>(base);
-  }
-  return at - start;
+Work lay_out(Carver& c, long tiles, int B, int T) {
+  Work w;
+  w.bounds = c.take<float>((size_t)tiles * kBound);
+  w.crop = c.take<double>((size_t)B * T * 6);
+  w.stats = c.take<int32_t>((size_t)tiles * T * kStat);
+  w.tile_base = c.take<int32_t>((size_t)tiles);
+  return w;
 }
 
 __global__ __launch_bounds__(kTile) void cuboid_bounds_kernel(vdetr_cuboid_desc d, int total_rows, float* bounds) {
   __shared__ float red[kTile / kWave][kBound];
   const int t = blockIdx.x, tid = threadIdx.x;
   int b, local_tile;
-  const bool found = locate_tile(d.offsets, d.B, t, b, local_tile);
+  const bool found = locate_tile(d.offsets, d.B, kTile, t, b, local_tile);
   const float inf = __builtin_huge_valf();
   float v[kBound] = {inf, inf, inf, -inf, -inf, -inf, 0.f, 0.f, 0.f};
   if (found) {
@@ -89,25 +58,14 @@ __global__ __launch_bounds__(kTile) void cuboid_bounds_kernel(vdetr_cuboid_desc 
       }
     }
   }
-  const int wave = tid / kWave;
-#pragma unroll
-  for (int k = 0; k < kBound; ++k) {
-    const float r = k < 3 ? wave_allmin_f32(v[k]) : wave_allmax_f32(v[k]);
-    if ((tid & (kWave - 1)) == 0) red[wave][k] = r;
-  }
-  __syncthreads();
-  if (tid < kBound) {
-    float r = red[0][tid];
-    for (int w = 1; w < kTile / kWave; ++w) r = tid < 3 ? fminf(r, red[w][tid]) : fmaxf(r, red[w][tid]);
-    bounds[(size_t)t * kBound + tid] = r;
-  }
+  store_tile_partial(v, red, bounds, t);
 }
 
 __global__ __launch_bounds__(kWave) void cuboid_boxes_kernel(vdetr_cuboid_desc d, int num_tiles, int total_rows, const float* bounds,
                                                              double* crop) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int begin = d.offsets[b], rows = d.offsets[b + 1] - begin;
-  const int first = first_tile(d.offsets, b), nt = tiles_of(rows);
+  const int first = first_tile(d.offsets, b, kTile), nt = tiles_of(rows, kTile);
   const float inf = __builtin_huge_valf();
   float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf}, bad[3] = {0.f, 0.f, 0.f};
   for (int i = lane; i < nt && first + i < num_tiles; i += kWave) {
@@ -144,7 +102,7 @@ __global__ __launch_bounds__(VDETR_CUBOID_ATTEMPT_LANES) void cuboid_count_kerne
   __shared__ float xyz[kTile][3];
   const int t = blockIdx.x, tid = threadIdx.x;
   int b, local_tile;
-  if (!locate_tile(d.offsets, d.B, t, b, local_tile)) return;          // uniform
+  if (!locate_tile(d.offsets, d.B, kTile, t, b, local_tile)) return;          // uniform
   const int begin = d.offsets[b], rows = d.offsets[b + 1] - begin;
   const int base = local_tile * kTile;
   int here = rows - base;
@@ -199,7 +157,7 @@ __global__ __launch_bounds__(VDETR_CUBOID_ATTEMPT_LANES) void cuboid_select_kern
   __shared__ int win_count;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int rows = d.offsets[b + 1] - d.offsets[b];
-  const int first = first_tile(d.offsets, b), nt = tiles_of(rows);
+  const int first = first_tile(d.offsets, b, kTile), nt = tiles_of(rows, kTile);
   long nbox = d.box_counts[b];
   nbox = nbox < 0 ? 0 : nbox > d.G ? d.G : nbox;
   const bool filter = d.trials[((size_t)b * (d.T + 1) + d.T) * VDETR_CUBOID_TRIAL] != 0.0;
@@ -302,7 +260,7 @@ __global__ __launch_bounds__(kTile) void cuboid_compact_kernel(vdetr_cuboid_desc
   __shared__ int wave_count[kTile / kWave];
   const int t = blockIdx.x, tid = threadIdx.x;
   int b, local_tile;
-  if (!locate_tile(d.offsets, d.B, t, b, local_tile)) return;          // uniform
+  if (!locate_tile(d.offsets, d.B, kTile, t, b, local_tile)) return;          // uniform
   const int begin = d.offsets[b], rows = d.offsets[b + 1] - begin;
   const int trial = d.result[b * VDETR_CUBOID_RESULT], kept_rows = d.result[b * VDETR_CUBOID_RESULT + 1];
   const int j = local_tile * kTile + tid;
@@ -333,19 +291,6 @@ __global__ __launch_bounds__(256) void cuboid_compose_kernel(vdetr_cuboid_desc d
   d.choices[i] = ok ? d.kept_rows[begin + pick] : -1;                  // prepare_scenes turns a row outside its scene into NaN
 }
 
-long count_tiles(const int32_t* offsets_host, int B, bool report) {
-  long tiles = 0;
-  for (int b = 0; b < B; ++b) {
-    const long n = (long)offsets_host[b + 1] - offsets_host[b];
-    if (n <= 0 || offsets_host[b] < 0) {
-      if (report) set_error("cuboid: scene %d has no points (offsets %d .. %d)", b, offsets_host[b], offsets_host[b + 1]);
-      return -1;
-    }
-    tiles += (n + kTile - 1) / kTile;
-  }
-  return tiles;
-}
-
 int check_desc(const vdetr_cuboid_desc* d, const int32_t* offsets_host, const char* op) {
   VDETR_REQUIRE(d && offsets_host, "%s: null descriptor or offsets", op);
   VDETR_REQUIRE(d->B >= 0 && d->W >= 3 && d->G >= 0 && d->num_points >= 0, "%s: bad dimension (B %d, W %d, G %d, num_points %d)", op,
@@ -363,8 +308,11 @@ using namespace vdetr;
 
 extern "C" size_t vdetr_cuboid_workspace_bytes(const int32_t* offsets_host, int B, int T) {
   if (!offsets_host || B <= 0 || T <= 0) return 0;
-  const long tiles = count_tiles(offsets_host, B, false);
-  return tiles <= 0 ? 0 : carve(nullptr, tiles, B, T, nullptr) + 256;
+  const long tiles = count_tiles(offsets_host, B, kTile, nullptr);
+  if (tiles <= 0) return 0;
+  Carver c(nullptr);
+  lay_out(c, tiles, B, T);
+  return c.bytes() + 256;
 }
 
 extern "C" int vdetr_cuboid_crop_f32(const vdetr_cuboid_desc* desc, const int32_t* offsets_host, void* workspace, size_t workspace_bytes,
@@ -372,19 +320,15 @@ extern "C" int vdetr_cuboid_crop_f32(const vdetr_cuboid_desc* desc, const int32_
   if (int e = check_desc(desc, offsets_host, "cuboid_crop")) return e;
   if (desc->B == 0) return VDETR_OK;
   const vdetr_cuboid_desc& d = *desc;
-  const long tiles = count_tiles(offsets_host, d.B, true);
+  const long tiles = count_tiles(offsets_host, d.B, kTile, "cuboid");
   if (tiles < 0) return VDETR_ERR_ARG;
   VDETR_REQUIRE(tiles <= 0x7fffffffL / (d.T * kStat), "cuboid_crop: %ld tiles x %d attempts", tiles, d.T);
   VDETR_REQUIRE(d.points && d.offsets && d.trials && d.box_counts && d.out_counts && d.result && d.kept_rows, "cuboid_crop: null pointer");
   VDETR_REQUIRE(d.G == 0 || (d.boxes && d.box_classes && d.out_boxes && d.out_classes), "cuboid_crop: %d box slots without boxes or classes",
                 d.G);
-  const size_t need = vdetr_cuboid_workspace_bytes(offsets_host, d.B, d.T);
-  if (!workspace || workspace_bytes < need) {
-    set_error("cuboid_crop: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
-  Carve c;
-  carve(workspace, tiles, d.B, d.T, &c);
+  if (int e = require_workspace("cuboid_crop", workspace, workspace_bytes, vdetr_cuboid_workspace_bytes(offsets_host, d.B, d.T))) return e;
+  Carver carver(workspace);
+  const Work c = lay_out(carver, tiles, d.B, d.T);
   const int total = (int)offsets_host[d.B];
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(cuboid_bounds_kernel, dim3((unsigned)tiles), dim3(kTile), 0, s, d, total, c.bounds);
@@ -402,7 +346,7 @@ extern "C" int vdetr_cuboid_compose_i32(const vdetr_cuboid_desc* desc, const int
   if (int e = check_desc(desc, offsets_host, "cuboid_compose")) return e;
   if (desc->B == 0) return VDETR_OK;
   const vdetr_cuboid_desc& d = *desc;
-  if (count_tiles(offsets_host, d.B, true) < 0) return VDETR_ERR_ARG;
+  if (count_tiles(offsets_host, d.B, kTile, "cuboid") < 0) return VDETR_ERR_ARG;
   VDETR_REQUIRE(d.num_points >= 1, "cuboid_compose: num_points %d < 1", d.num_points);
   VDETR_REQUIRE(d.offsets && d.result && d.kept_rows && d.drawn && d.choices, "cuboid_compose: null pointer");
   const long n = (long)d.B * d.num_points;

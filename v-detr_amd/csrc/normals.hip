@@ -17,7 +17,7 @@
 // scene is never followed: the face's weight is NaN and only its in-range corners are listed.  -ffp-contract=off as everywhere:
 // every product, difference and sum below is one IEEE float32 operation; `/` and sqrtf are the correctly rounded forms (no
 // fast-math, not the native sqrt), float32 subnormals are kept (the compiler's default mode for kernels).
-#include "common.h"
+#include "scene_tiles.h"
 
 namespace vdetr {
 namespace {
@@ -26,7 +26,6 @@ constexpr int kTile = VDETR_NORMALS_TILE;
 constexpr int kScanTile = VDETR_NORMALS_SCAN_TILE;
 constexpr int kScanRows = kScanTile / 256;   // consecutive vertices per lane of the scan kernels
 constexpr int kShort = VDETR_NORMALS_SHORT;
-constexpr int kMaxScenes = 4096;
 constexpr float kEps = 1.0e-8f;              // the reference's 1.0e-8, rounded to float32 when it meets a float32 array
 
 struct Work {
@@ -282,8 +281,6 @@ __global__ __launch_bounds__(kTile) void normals_vertex_kernel(vdetr_normals_des
   }
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // N, F of the packed batch, or -1 (with a message if `op` is given)
 int batch_sizes(const int32_t* vert, const int32_t* face, int B, const char* op, long& N, long& F) {
   if (vert[0] != 0 || face[0] != 0) {
@@ -309,9 +306,25 @@ int batch_sizes(const int32_t* vert, const int32_t* face, int B, const char* op,
   return 0;
 }
 
+// the workspace of a packed batch of N vertices and F faces
+Work lay_out(Carver& c, long N, long F) {
+  Work k;
+  k.N = (int)N;
+  k.F = (int)F;
+  k.tiles = (int)((N + kScanTile - 1) / kScanTile);
+  k.w = c.take<float>((size_t)F * 3);
+  k.count = c.take<int>((size_t)N);
+  k.start = c.take<int>((size_t)N);
+  k.cursor = c.take<int>((size_t)N);
+  k.tile_sum = c.take<int>((size_t)k.tiles);
+  k.adj = c.take<int>((size_t)F * 3);
+  return k;
+}
+
 size_t workspace_need(long N, long F) {
-  const long tiles = (N + kScanTile - 1) / kScanTile;
-  return 2 * align256((size_t)F * 3 * 4) + 3 * align256((size_t)N * 4) + align256((size_t)tiles * 4) + 256;
+  Carver c(nullptr);
+  lay_out(c, N, F);
+  return c.bytes() + 256;
 }
 
 }  // namespace
@@ -337,27 +350,9 @@ extern "C" int vdetr_vertex_normals_f32(const vdetr_normals_desc* desc, const in
   long N, F;
   if (batch_sizes(vert_offsets_host, face_offsets_host, d.B, "vertex_normals", N, F)) return VDETR_ERR_ARG;
   VDETR_REQUIRE(d.vertices && d.vert_offsets && d.face_offsets && d.out && (d.faces || F == 0), "vertex_normals: null pointer");
-  const size_t need = workspace_need(N, F);
-  if (!workspace || workspace_bytes < need) {
-    set_error("vertex_normals: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
-  Work k;
-  k.N = (int)N;
-  k.F = (int)F;
-  k.tiles = (int)((N + kScanTile - 1) / kScanTile);
-  size_t at = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-  k.w = reinterpret_cast<float*>(at);
-  at += align256((size_t)F * 3 * 4);
-  k.count = reinterpret_cast<int*>(at);
-  at += align256((size_t)N * 4);
-  k.start = reinterpret_cast<int*>(at);
-  at += align256((size_t)N * 4);
-  k.cursor = reinterpret_cast<int*>(at);
-  at += align256((size_t)N * 4);
-  k.tile_sum = reinterpret_cast<int*>(at);
-  at += align256((size_t)k.tiles * 4);
-  k.adj = reinterpret_cast<int*>(at);
+  if (int e = require_workspace("vertex_normals", workspace, workspace_bytes, workspace_need(N, F))) return e;
+  Carver c(workspace);
+  const Work k = lay_out(c, N, F);
   const unsigned vert_tiles = (unsigned)((N + kTile - 1) / kTile);
   const unsigned face_tiles = (unsigned)((F + kTile - 1) / kTile > 0 ? (F + kTile - 1) / kTile : 1);   // no faces: one idle workgroup
   hipStream_t s = (hipStream_t)stream;

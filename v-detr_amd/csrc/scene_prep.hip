@@ -7,13 +7,12 @@
 //                              carries the boxes through the same augmentation in fp64 and writes every gt_* tensor.
 // The arithmetic follows numpy on the reference's dtypes step by step (include/vdetr_hip.h): the build's -ffp-contract=off
 // keeps every product and sum a separate IEEE operation.
-#include "wave.h"
+#include "scene_tiles.h"
 
 namespace vdetr {
 namespace {
 
 constexpr int kTile = VDETR_SCENE_PREP_TILE;
-constexpr int kPrepMaxScenes = 4096;
 
 struct ScenePose {
   bool flip_x, flip_y;
@@ -36,19 +35,19 @@ __device__ __forceinline__ void rotate_z(const ScenePose& p, double x, double y,
   oz = (x * 0.0 + y * 0.0) + z * 1.0;
 }
 
-// scene and first tile of tile t / of scene b: tiles never straddle scenes
-__device__ __forceinline__ int tiles_of(int rows) { return (rows + kTile - 1) / kTile; }
-
-__device__ __forceinline__ bool locate_tile(const vdetr_scene_prep_desc& d, int t, int& b, int& local_tile) {
+// locate_tile for the kept rows: with num_points every scene keeps that many, the same number of tiles each.  The ragged case
+// is locate_tile's / first_tile's loop written out, here and in scene_prep_targets_kernel: called as functions they leave both
+// kernels with other instructions
+__device__ __forceinline__ bool locate_kept_tile(const vdetr_scene_prep_desc& d, int t, int& b, int& local_tile) {
   if (d.num_points > 0) {
-    const int per = tiles_of(d.num_points);
+    const int per = tiles_of(d.num_points, kTile);
     b = t / per;
     local_tile = t - b * per;
     return b < d.B;
   }
   int acc = 0;
   for (b = 0; b < d.B; ++b) {
-    const int nt = tiles_of(d.offsets[b + 1] - d.offsets[b]);
+    const int nt = tiles_of(d.offsets[b + 1] - d.offsets[b], kTile);
     if (t < acc + nt) break;
     acc += nt;
   }
@@ -60,7 +59,7 @@ __global__ __launch_bounds__(kTile) void scene_prep_points_kernel(vdetr_scene_pr
   __shared__ float red[kTile / kWave][6];
   const int t = blockIdx.x, tid = threadIdx.x;
   int b, local_tile;
-  const bool found = locate_tile(d, t, b, local_tile);  // uniform over the workgroup
+  const bool found = locate_kept_tile(d, t, b, local_tile);  // uniform over the workgroup
   const float inf = __builtin_huge_valf();
   float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
   if (found) {
@@ -104,7 +103,8 @@ __global__ __launch_bounds__(kTile) void scene_prep_points_kernel(vdetr_scene_pr
       }
     }
   }
-  // every lane is active here (idle ones carry +-inf)
+  // every lane is active here (idle ones carry +-inf).  store_tile_partial's body, kept in this form: through the template
+  // the compiler orders this kernel's instructions differently
   const int wave = tid / kWave;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -123,11 +123,11 @@ __global__ __launch_bounds__(kWave) void scene_prep_targets_kernel(vdetr_scene_p
   const int b = blockIdx.x, lane = threadIdx.x;
   int first = 0, nt;
   if (d.num_points > 0) {
-    nt = tiles_of(d.num_points);
+    nt = tiles_of(d.num_points, kTile);
     first = b * nt;
   } else {
-    for (int i = 0; i < b; ++i) first += tiles_of(d.offsets[i + 1] - d.offsets[i]);
-    nt = tiles_of(d.offsets[b + 1] - d.offsets[b]);
+    for (int i = 0; i < b; ++i) first += tiles_of(d.offsets[i + 1] - d.offsets[i], kTile);
+    nt = tiles_of(d.offsets[b + 1] - d.offsets[b], kTile);
   }
   const float inf = __builtin_huge_valf();
   float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
@@ -214,37 +214,28 @@ __global__ __launch_bounds__(kWave) void scene_prep_targets_kernel(vdetr_scene_p
   }
 }
 
-// number of tiles, or -1 (with the error set) if the host offsets are unusable
-long count_tiles(const int32_t* offsets_host, int B, int num_points, bool report) {
-  long tiles = 0;
-  for (int b = 0; b < B; ++b) {
-    const long n = (long)offsets_host[b + 1] - offsets_host[b];
-    if (n <= 0 || offsets_host[b] < 0) {
-      if (report) set_error("scene_prep: scene %d has no points (offsets %d .. %d)", b, offsets_host[b], offsets_host[b + 1]);
-      return -1;
-    }
-    tiles += ((num_points > 0 ? num_points : n) + kTile - 1) / kTile;
-  }
-  return tiles;
+// count_tiles for the kept rows: num_points per scene where it is given; the offsets are checked either way
+long count_kept_tiles(const int32_t* offsets_host, int B, int num_points, const char* op) {
+  const long tiles = count_tiles(offsets_host, B, kTile, op);
+  return tiles < 0 || num_points <= 0 ? tiles : (long)B * ((num_points + kTile - 1) / kTile);
 }
+
+// the workspace: 6 floats per tile
+float* lay_out(Carver& c, long tiles) { return c.take_unpadded<float>((size_t)tiles * 6); }
 
 int check_desc(const vdetr_scene_prep_desc* d, const int32_t* offsets_host, const void* workspace, size_t workspace_bytes,
                long* tiles) {
   VDETR_REQUIRE(d && offsets_host, "scene_prep: null descriptor or offsets");
   VDETR_REQUIRE(d->B >= 0 && d->C >= 0 && d->G >= 0 && d->max_obj >= 0 && d->num_points >= 0, "scene_prep: negative dimension");
-  VDETR_REQUIRE(d->B <= kPrepMaxScenes, "scene_prep: %d scenes > %d", d->B, kPrepMaxScenes);
+  VDETR_REQUIRE(d->B <= kMaxScenes, "scene_prep: %d scenes > %d", d->B, kMaxScenes);
   VDETR_REQUIRE(d->G <= d->max_obj, "scene_prep: %d box slots > max_obj %d", d->G, d->max_obj);
   VDETR_REQUIRE(d->color_mode == VDETR_COLOR_KEEP || ((d->color_mode == VDETR_COLOR_MEAN || d->color_mode == VDETR_COLOR_UNIT) && d->C >= 3),
                 "scene_prep: color_mode %d with %d feature columns", d->color_mode, d->C);
-  *tiles = count_tiles(offsets_host, d->B, d->num_points, true);
+  *tiles = count_kept_tiles(offsets_host, d->B, d->num_points, "scene_prep");
   if (*tiles < 0) return VDETR_ERR_ARG;
   VDETR_REQUIRE(*tiles <= 0x7fffffffL, "scene_prep: %ld tiles", *tiles);
   const size_t need = vdetr_scene_prep_workspace_bytes(offsets_host, d->B, d->num_points);
-  if (d->B > 0 && (!workspace || workspace_bytes < need)) {
-    set_error("scene_prep: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
-  return VDETR_OK;
+  return d->B > 0 ? require_workspace("scene_prep", workspace, workspace_bytes, need) : VDETR_OK;
 }
 
 }  // namespace
@@ -254,12 +245,11 @@ using namespace vdetr;
 
 extern "C" size_t vdetr_scene_prep_workspace_bytes(const int32_t* offsets_host, int B, int num_points) {
   if (!offsets_host || B <= 0 || num_points < 0) return 0;
-  const long tiles = count_tiles(offsets_host, B, num_points, false);
-  return tiles <= 0 ? 0 : (size_t)tiles * 6 * sizeof(float) + 256;
-}
-
-static float* prep_partials(const void* workspace) {
-  return reinterpret_cast<float*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  const long tiles = count_kept_tiles(offsets_host, B, num_points, nullptr);
+  if (tiles <= 0) return 0;
+  Carver c(nullptr);
+  lay_out(c, tiles);
+  return c.bytes() + 256;
 }
 
 extern "C" int vdetr_scene_prep_points_f32(const vdetr_scene_prep_desc* desc, const int32_t* offsets_host, void* workspace,
@@ -269,8 +259,9 @@ extern "C" int vdetr_scene_prep_points_f32(const vdetr_scene_prep_desc* desc, co
   if (desc->B == 0) return VDETR_OK;
   VDETR_REQUIRE(desc->points && desc->offsets && desc->params && desc->out_points, "scene_prep_points: null pointer");
   VDETR_REQUIRE(desc->num_points == 0 || desc->choices, "scene_prep_points: num_points %d without choices", desc->num_points);
+  Carver c(workspace);
   hipLaunchKernelGGL(scene_prep_points_kernel, dim3((unsigned)tiles), dim3(kTile), 0, (hipStream_t)stream, *desc,
-                     (int)offsets_host[desc->B], prep_partials(workspace));
+                     (int)offsets_host[desc->B], lay_out(c, tiles));
   return check_launch("scene_prep_points");
 }
 
@@ -285,7 +276,8 @@ extern "C" int vdetr_scene_prep_targets_f32(const vdetr_scene_prep_desc* desc, c
                     d.angle_residual && d.angles && d.present,
                 "scene_prep_targets: null pointer");
   VDETR_REQUIRE(d.G == 0 || (d.boxes && d.box_classes), "scene_prep_targets: %d box slots without boxes or classes", d.G);
+  Carver c(workspace);
   hipLaunchKernelGGL(scene_prep_targets_kernel, dim3(d.B), dim3(kWave), 0, (hipStream_t)stream, d, (int)tiles,
-                     (const float*)prep_partials(workspace));
+                     (const float*)lay_out(c, tiles));
   return check_launch("scene_prep_targets");
 }

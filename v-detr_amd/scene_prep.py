@@ -88,6 +88,48 @@ def _host_i32(a, name):
     return a
 
 
+def _packed_scenes(points, offsets, min_width, what, *, name="points", strided=False, gpu=True):
+    """The one place that holds a packed float32 [N, columns] tensor against its B + 1 host offsets -> (offsets int64, rows per
+    scene).  ``name``: "points" or "vertices", the wording of the messages; ``strided``: the rows may be strided (unit column
+    stride); ``gpu=False`` leaves ``require_gpu`` to the caller, after its own host checks."""
+    if gpu:
+        L.require_gpu(points, name)
+    L.require_float(points, name)
+    off_name = "offsets" if name == "points" else "vert_offsets"
+    off = _host_i32(offsets, off_name)
+    if points.dim() != 2 or points.shape[1] < min_width or (strided and (points.stride(1) != 1 or points.stride(0) < min_width)):
+        layout = " with unit column stride" if strided else ""
+        raise ValueError(f"{what}: {name} must be [N, {min_width} or more columns]{layout}, got {tuple(points.shape)}")
+    N = points.shape[0]
+    if off[0] != 0 or off[-1] != N or N >= 2 ** 31:
+        raise ValueError(f"{off_name} run from {off[0]} to {off[-1]}, {name} has {N} rows")
+    sizes = np.diff(off)
+    if (sizes <= 0).any():
+        raise ValueError(f"scene {int(np.argmax(sizes <= 0))} has no {name}")
+    return off, sizes
+
+
+def _box_tables(boxes, box_counts, box_classes, B, dtypes=(torch.float32,)):
+    """boxes [B,G,6] of one of ``dtypes``, box_counts [B], box_classes [B,G] on the device -> the three detached and contiguous,
+    counts and classes as int64"""
+    for t, name in ((boxes, "boxes"), (box_counts, "box_counts"), (box_classes, "box_classes")):
+        L.require_gpu(t, name)
+    if boxes.dtype not in dtypes:
+        raise RuntimeError("boxes must be a float tensor" if len(dtypes) == 1 else "boxes must be a float or double tensor")
+    if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 6:
+        raise ValueError(f"boxes must be [{B}, G, 6], got {tuple(boxes.shape)}")
+    if tuple(box_counts.shape) != (B,) or tuple(box_classes.shape) != (B, boxes.shape[1]):
+        raise ValueError("box_counts [B] and box_classes [B,G] must describe the B scenes of offsets")
+    return boxes.detach().contiguous(), box_counts.detach().to(torch.int64).contiguous(), box_classes.detach().to(torch.int64).contiguous()
+
+
+def _upload_offsets(off, dev):
+    """-> (the offsets as int32 on the host, their device copy, the host array's address for the C ABI); the caller keeps the
+    first alive while the address is in use"""
+    off32 = np.ascontiguousarray(off, dtype=np.int32)
+    return off32, torch.from_numpy(off32).to(dev, non_blocking=True), off32.ctypes.data_as(ctypes.c_void_p)
+
+
 def prepare_scenes(points, offsets, boxes, box_counts, box_classes, params, dataset_config, *, choices=None, color_mean=None,
                    max_num_obj=None):
     """points [N,3+C] f32 (packed scenes), offsets [B+1] (host array / CPU tensor; a device tensor is read back once), boxes
@@ -99,29 +141,17 @@ def prepare_scenes(points, offsets, boxes, box_counts, box_classes, params, data
     ``pc[choices]``, repeats allowed) and the bounds cover the kept rows; a host array is range-checked here, a device tensor
     cannot be without a synchronisation (the kernel turns an index outside the scene into a row of NaN).  ``color_mean``: None
     leaves columns 3:6, negative is ``(rgb - MEAN_COLOR_RGB) / 256.0``, otherwise ``rgb / 255.0 - 0.5`` (scannet.py:453-456)."""
-    for t, name in ((points, "points"), (boxes, "boxes"), (box_counts, "box_counts"), (box_classes, "box_classes")):
-        L.require_gpu(t, name)
-    L.require_float(points, "points")
-    L.require_float(boxes, "boxes")
+    off, sizes = _packed_scenes(points, offsets, 3, "prepare_scenes")
     dev = points.device
-    off = _host_i32(offsets, "offsets")
     B = len(off) - 1
-    if points.dim() != 2 or points.shape[1] < 3:
-        raise ValueError(f"points must be [N, 3+C], got {tuple(points.shape)}")
-    if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 6:
-        raise ValueError(f"boxes must be [{B}, G, 6], got {tuple(boxes.shape)}")
+    boxes, counts, classes = _box_tables(boxes, box_counts, box_classes, B)
     N, W = points.shape
     G = boxes.shape[1]
     M = int(dataset_config.max_num_obj if max_num_obj is None else max_num_obj)
     if G > M:
         raise ValueError(f"{G} box slots > max_num_obj {M}")
-    if tuple(box_counts.shape) != (B,) or tuple(box_classes.shape) != (B, G) or len(params) != B:
-        raise ValueError("box_counts [B], box_classes [B,G] and params must describe the B scenes of offsets")
-    if off[0] != 0 or off[-1] != N or N >= 2 ** 31:
-        raise ValueError(f"offsets run from {off[0]} to {off[-1]}, points has {N} rows")
-    sizes = np.diff(off)
-    if (sizes <= 0).any():
-        raise ValueError(f"scene {int(np.argmax(sizes <= 0))} has no points (point_cloud.min would fail, scannet.py:563)")
+    if len(params) != B:
+        raise ValueError(f"params describe {len(params)} scenes, offsets {B}")
     mode = L.VDETR_COLOR_KEEP if color_mean is None else L.VDETR_COLOR_MEAN if color_mean < 0 else L.VDETR_COLOR_UNIT
     if mode != L.VDETR_COLOR_KEEP and W < 6:
         raise ValueError(f"color_mean needs rgb in columns 3:6, points has {W} columns")
@@ -142,11 +172,8 @@ def prepare_scenes(points, offsets, boxes, box_counts, box_classes, params, data
     keep_rows = [num_points] * B if num_points else sizes.tolist()
     rows = int(sum(keep_rows))
 
-    points, boxes = points.detach().contiguous(), boxes.detach().contiguous()
-    counts = box_counts.detach().to(torch.int64).contiguous()
-    classes = box_classes.detach().to(torch.int64).contiguous()
-    off32 = np.ascontiguousarray(off, dtype=np.int32)
-    off_dev = torch.from_numpy(off32).to(dev, non_blocking=True)
+    points = points.detach().contiguous()
+    off32, off_dev, host = _upload_offsets(off, dev)
     table = torch.from_numpy(params.table()).to(dev, non_blocking=True)
     mean = torch.from_numpy(np.ascontiguousarray(dataset_config.mean_size_arr, dtype=np.float64)).to(dev, non_blocking=True)
 
@@ -177,7 +204,6 @@ def prepare_scenes(points, offsets, boxes, box_counts, box_classes, params, data
                        ("sem_cls", "gt_box_sem_cls_label"), ("angle_residual", "gt_angle_residual_label"),
                        ("angles", "gt_box_angles"), ("present", "gt_box_present")):
         setattr(d, field, ret[key].data_ptr())
-    host = off32.ctypes.data_as(ctypes.c_void_p)
     nbytes = L.lib().vdetr_scene_prep_workspace_bytes(host, B, num_points)
     ws = L.workspace(nbytes, dev)
     _launch_pair(d, host, ws, nbytes)
@@ -249,27 +275,12 @@ def crop_and_sample(points, offsets, boxes, box_counts, box_classes, randoms, nu
     Six launches whatever B and the number of attempts (csrc/cuboid.hip) and ONE read-back of (trial, kept points, kept
     boxes) per scene, the call's only synchronisation.  It is inherent: ``np.random.choice(n_kept, num_points, replace=n_kept <
     num_points)`` consumes the stream differently for every ``n_kept``.  No CPU path."""
-    for t, name in ((points, "points"), (boxes, "boxes"), (box_counts, "box_counts"), (box_classes, "box_classes")):
-        L.require_gpu(t, name)
-    L.require_float(points, "points")
-    if boxes.dtype not in (torch.float32, torch.float64):
-        raise RuntimeError("boxes must be a float or double tensor")
+    off, sizes = _packed_scenes(points, offsets, 3, "crop_and_sample")
     dev = points.device
-    off = _host_i32(offsets, "offsets")
     B = len(off) - 1
-    if points.dim() != 2 or points.shape[1] < 3:
-        raise ValueError(f"points must be [N, 3+C], got {tuple(points.shape)}")
-    if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 6:
-        raise ValueError(f"boxes must be [{B}, G, 6], got {tuple(boxes.shape)}")
+    boxes, counts, classes = _box_tables(boxes, box_counts, box_classes, B, (torch.float32, torch.float64))
     N, W = points.shape
     G = boxes.shape[1]
-    if tuple(box_counts.shape) != (B,) or tuple(box_classes.shape) != (B, G):
-        raise ValueError("box_counts [B] and box_classes [B,G] must describe the B scenes of offsets")
-    if off[0] != 0 or off[-1] != N or N >= 2 ** 31:
-        raise ValueError(f"offsets run from {off[0]} to {off[-1]}, points has {N} rows")
-    sizes = np.diff(off)
-    if (sizes <= 0).any():
-        raise ValueError(f"scene {int(np.argmax(sizes <= 0))} has no points")
     num_points, min_points, max_trials = int(num_points), int(min_points), int(max_trials)
     if num_points < 1:
         raise ValueError(f"num_points {num_points} < 1")
@@ -288,9 +299,7 @@ def crop_and_sample(points, offsets, boxes, box_counts, box_classes, randoms, nu
         if filter_boxes.shape != (B,):
             raise ValueError(f"filter_boxes must be a host bool array [{B}]")
 
-    counts = box_counts.detach().to(torch.int64).contiguous()
-    classes = box_classes.detach().to(torch.int64).contiguous()
-    points, boxes = points.detach().contiguous(), boxes.detach().contiguous()
+    points = points.detach().contiguous()
     ret = {"boxes": torch.empty_like(boxes), "box_counts": torch.empty_like(counts), "box_classes": torch.empty_like(classes),
            "choices": torch.empty((B, num_points), dtype=torch.int32, device=dev), "trial": np.zeros(B, np.int64),
            "kept_points": np.zeros(B, np.int64), "kept_rows": []}
@@ -311,8 +320,7 @@ def crop_and_sample(points, offsets, boxes, box_counts, box_classes, randoms, nu
     table = torch.from_numpy(table).to(dev, non_blocking=True)
     if filter_dev is not None:
         table[:, max_trials, 0] = filter_dev
-    off32 = np.ascontiguousarray(off, dtype=np.int32)
-    off_dev = torch.from_numpy(off32).to(dev, non_blocking=True)
+    off32, off_dev, host = _upload_offsets(off, dev)
     result = torch.empty((B, L.VDETR_CUBOID_RESULT), dtype=torch.int32, device=dev)
     kept_rows = torch.empty(N, dtype=torch.int32, device=dev)
 
@@ -324,7 +332,6 @@ def crop_and_sample(points, offsets, boxes, box_counts, box_classes, randoms, nu
     d.boxes, d.box_counts, d.box_classes = boxes.data_ptr(), counts.data_ptr(), classes.data_ptr()
     d.out_boxes, d.out_counts, d.out_classes = ret["boxes"].data_ptr(), ret["box_counts"].data_ptr(), ret["box_classes"].data_ptr()
     d.result, d.kept_rows, d.choices = result.data_ptr(), kept_rows.data_ptr(), ret["choices"].data_ptr()
-    host = off32.ctypes.data_as(ctypes.c_void_p)
     nbytes = L.lib().vdetr_cuboid_workspace_bytes(host, B, max_trials)
     ws = L.workspace(nbytes, dev)
     alive = (points, boxes, counts, classes, table, off_dev, result, kept_rows, ret)
@@ -421,27 +428,11 @@ def draw_sunrgbd_color(n_rows, random=np.random):
     return SunrgbdColorParams(brightness, shift, jitter, random.random(n) > 0.3)
 
 
-def _packed_scenes(points, offsets, min_width, what):
-    L.require_gpu(points, "points")
-    L.require_float(points, "points")
-    off = _host_i32(offsets, "offsets")
-    if points.dim() != 2 or points.shape[1] < min_width:
-        raise ValueError(f"{what}: points must be [N, {min_width} or more columns], got {tuple(points.shape)}")
-    N = points.shape[0]
-    if off[0] != 0 or off[-1] != N or N >= 2 ** 31:
-        raise ValueError(f"offsets run from {off[0]} to {off[-1]}, points has {N} rows")
-    sizes = np.diff(off)
-    if (sizes <= 0).any():
-        raise ValueError(f"scene {int(np.argmax(sizes <= 0))} has no points")
-    return off, sizes
-
-
-def _color_desc(points, out, off32, dev):
+def _color_desc(points, out, off_dev):
     d = L.ColorAugDesc()
-    d.B, d.W = len(off32) - 1, points.shape[1]
-    off_dev = torch.from_numpy(off32).to(dev, non_blocking=True)
+    d.B, d.W = len(off_dev) - 1, points.shape[1]
     d.points, d.offsets, d.out = points.data_ptr(), off_dev.data_ptr(), out.data_ptr()
-    return d, off_dev
+    return d
 
 
 def augment_colors(points, offsets, params):
@@ -476,15 +467,14 @@ def augment_colors(points, offsets, params):
             noise_rows += len(noise[-1])
         if p.hue_val is not None:
             table[b, 4:7] = 1, p.hue_val, p.sat_ratio
-    off32 = np.ascontiguousarray(off, dtype=np.int32)
-    d, off_dev = _color_desc(points, out, off32, dev)
+    off32, off_dev, host = _upload_offsets(off, dev)
+    d = _color_desc(points, out, off_dev)
     table_dev = torch.from_numpy(table).to(dev, non_blocking=True)
     keep_dev = torch.from_numpy(keep.view(np.uint8)).to(dev, non_blocking=True) if keep is not None else None
     noise_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate(noise))).to(dev, non_blocking=True) if noise else None
     d.params, d.noise_rows = table_dev.data_ptr(), noise_rows
     d.keep = keep_dev.data_ptr() if keep_dev is not None else None
     d.noise = noise_dev.data_ptr() if noise_dev is not None else None
-    host = off32.ctypes.data_as(ctypes.c_void_p)
     nbytes = L.lib().vdetr_color_aug_workspace_bytes(host, B)
     ws = L.workspace(nbytes, dev)
     _launch_colors(d, host, ws, nbytes, (points, out, off_dev, table_dev, keep_dev, noise_dev))
@@ -527,11 +517,10 @@ def append_height(points, offsets):
     for b, n in enumerate(sizes):
         lower, upper, gamma = percentile_plan(int(n))
         select[b, :3] = lower, upper, np.array(gamma, np.float32).view(np.int32)
-    off32 = np.ascontiguousarray(off, dtype=np.int32)
-    d, off_dev = _color_desc(points, out, off32, dev)
+    off32, off_dev, host = _upload_offsets(off, dev)
+    d = _color_desc(points, out, off_dev)
     select_dev = torch.from_numpy(select).to(dev, non_blocking=True)
     d.select = select_dev.data_ptr()
-    host = off32.ctypes.data_as(ctypes.c_void_p)
     nbytes = L.lib().vdetr_append_height_workspace_bytes(host, B)
     ws = L.workspace(nbytes, dev)
     _launch_height(d, host, ws, nbytes, (points, out, off_dev, select_dev))
@@ -571,13 +560,13 @@ def sunrgbd_color_augment(point_clouds, offsets, params):
     table = np.zeros((B, L.VDETR_COLOR_AUG_PARAMS))
     for b, p in enumerate(params):
         table[b, :3], table[b, 3:6] = p.brightness, p.shift
-    off32 = np.ascontiguousarray(off, dtype=np.int32)
-    d, off_dev = _color_desc(packed, packed, off32, dev)
+    off32, off_dev, host = _upload_offsets(off, dev)
+    d = _color_desc(packed, packed, off_dev)
     table_dev = torch.from_numpy(table).to(dev, non_blocking=True)
     jitter_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(p.jitter, np.float64) for p in params]))).to(dev, non_blocking=True)
     keep_dev = torch.from_numpy(np.concatenate([np.asarray(p.keep, bool) for p in params]).view(np.uint8)).to(dev, non_blocking=True)
     d.params, d.noise, d.keep, d.noise_rows = table_dev.data_ptr(), jitter_dev.data_ptr(), keep_dev.data_ptr(), packed.shape[0]
-    _launch_sunrgbd(d, off32.ctypes.data_as(ctypes.c_void_p), (packed, off_dev, table_dev, jitter_dev, keep_dev))
+    _launch_sunrgbd(d, host, (packed, off_dev, table_dev, jitter_dev, keep_dev))
     return point_clouds
 
 
@@ -597,21 +586,12 @@ def vertex_normals(vertices, vert_offsets, faces, face_offsets, *, out=None):
     A host ``faces`` array is range-checked here; a device tensor cannot be without a synchronisation: the kernels turn a face
     with an index outside its scene into NaN normals for the face's in-range vertices and follow none of its indices.  Seven
     launches on the current stream whatever B, no synchronisation, two runs give the same bits.  No CPU path."""
-    L.require_float(vertices, "vertices")
+    voff, sizes = _packed_scenes(vertices, vert_offsets, 3, "vertex_normals", name="vertices", strided=True, gpu=False)
     dev = vertices.device
-    voff = _host_i32(vert_offsets, "vert_offsets")
     foff = _host_i32(face_offsets, "face_offsets")
-    B = len(voff) - 1
+    B, N = len(voff) - 1, vertices.shape[0]
     if len(foff) != B + 1:
         raise ValueError(f"face_offsets must hold {B + 1} offsets like vert_offsets, got {len(foff)}")
-    if vertices.dim() != 2 or vertices.shape[1] < 3 or vertices.stride(1) != 1 or vertices.stride(0) < 3:
-        raise ValueError(f"vertices must be [N, 3 or more columns] with unit column stride, got {tuple(vertices.shape)}")
-    N = vertices.shape[0]
-    if voff[0] != 0 or voff[-1] != N or N >= 2 ** 31:
-        raise ValueError(f"vert_offsets run from {voff[0]} to {voff[-1]}, vertices has {N} rows")
-    sizes = np.diff(voff)
-    if (sizes <= 0).any():
-        raise ValueError(f"scene {int(np.argmax(sizes <= 0))} has no vertices")
     if not torch.is_tensor(faces):
         faces = torch.from_numpy(np.ascontiguousarray(faces))
     if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
@@ -637,14 +617,11 @@ def vertex_normals(vertices, vert_offsets, faces, face_offsets, *, out=None):
             raise ValueError(f"out must be a [{N}, 3] view with unit column stride on {dev}, got {tuple(out.shape)}")
     if B == 0:
         return out
-    voff32, foff32 = np.ascontiguousarray(voff, dtype=np.int32), np.ascontiguousarray(foff, dtype=np.int32)
-    voff_dev = torch.from_numpy(voff32).to(dev, non_blocking=True)
-    foff_dev = torch.from_numpy(foff32).to(dev, non_blocking=True)
+    (voff32, voff_dev, vhost), (foff32, foff_dev, fhost) = _upload_offsets(voff, dev), _upload_offsets(foff, dev)
     d = L.NormalsDesc()
     d.B, d.vert_stride, d.out_stride, d.faces_i64 = B, vertices.stride(0), out.stride(0), int(faces.dtype == torch.int64)
     d.vertices, d.faces, d.out = vertices.data_ptr(), faces.data_ptr(), out.data_ptr()
     d.vert_offsets, d.face_offsets = voff_dev.data_ptr(), foff_dev.data_ptr()
-    vhost, fhost = voff32.ctypes.data_as(ctypes.c_void_p), foff32.ctypes.data_as(ctypes.c_void_p)
     nbytes = L.lib().vdetr_vertex_normals_workspace_bytes(vhost, fhost, B)
     ws = L.workspace(nbytes, dev)
     _launch_normals(d, vhost, fhost, ws, nbytes, (vertices, faces, out, voff_dev, foff_dev, voff32, foff32))
