@@ -133,6 +133,9 @@ int vdetr_three_interpolate_grad_f32(const float* grad_out, const int32_t* idx, 
 #define VDETR_MASK_BOOL 1  /* uint8 [B,nQ,nK]; non-zero -> score := -100 (vdetr_transformer.py:746-747) */
 #define VDETR_MASK_FLOAT 2 /* f32   [B,nQ,nK]; added to the score        (vdetr_transformer.py:748-749) */
 
+#define VDETR_RPE_BILINEAR 0 /* trilinear over the 2 x 2 x 2 cells around pix, zero padding (F.grid_sample mode="bilinear") */
+#define VDETR_RPE_NEAREST 1  /* the one cell rint(pix), zero padding                          (F.grid_sample mode="nearest") */
+
 typedef struct vdetr_attn_desc {
   int32_t kind;        /* VDETR_ATTN_* */
   int32_t B, H, nQ, nK;
@@ -142,6 +145,11 @@ typedef struct vdetr_attn_desc {
   int32_t table_size;    /* 10 for rpe_quant "bilinear_4_10" */
   float log_scale;       /* 512 */
   float inv_log_norm;    /* 1 / (log2(8) * max_value) = 1/12 */
+  int32_t rpe_interp;    /* VDETR_RPE_*: the interpolation of rpe_quant ("bilinear_4_10" / "nearest_4_10"), F.grid_sample's `mode`
+                            (vdetr_transformer.py:675,727).  0 = bilinear, so a zeroed descriptor behaves as before ABI 3 knew the
+                            field (it fills what was a 4-byte hole: no size or offset changed).  VDETR_RPE_NEAREST: per vertex and
+                            axis the one cell rint(pix) (ties to even), contributing 0 outside 0..T-1; forward, stand-alone bias
+                            and both table-gradient kernels follow it.  Any other value: VDETR_ERR_ARG. */
   const float* vertices; /* [B, nQ, 8, 3] reference_point */
   const float* xyz;      /* [B, nK, 3] */
   const float* cos_sin;  /* [B, nQ, 2] (cos, sin of reference_angle) or NULL (angle_type != object_coords) */

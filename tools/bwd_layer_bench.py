@@ -4,7 +4,8 @@ the library-GEMM path (dO V^T, element-wise + table kernel, three contractions) 
 (attn_bwd_kv.hip + table kernel on the given dS + the dQ GEMM).  HIP events around autograd's backward, and around the
 C entry points alone.
 
-    python tools/bwd_layer_bench.py [c2|c4]
+    python tools/bwd_layer_bench.py [c2|c4] [--interp bilinear|nearest]
+--interp: the look-up mode of the table (rpe_quant "bilinear_*" / "nearest_*"; default bilinear).
 """
 import ctypes
 import json
@@ -37,7 +38,8 @@ def main():
     from vdetr_amd import _lib as L
     from vdetr_amd import attention as A
     from vdetr_amd.pc_util import morton_argsort
-    cfg = sys.argv[1] if len(sys.argv) > 1 else "c2"
+    cfg = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else "c2"
+    interp = sys.argv[sys.argv.index("--interp") + 1] if "--interp" in sys.argv else "bilinear"
     _, bs, nK, nQ, *_ = bench.CONFIGS[cfg]
     dev = torch.device("cuda")
     B, H = bs, 4
@@ -55,8 +57,8 @@ def main():
     v = torch.randn((B, nK, 64), generator=g).to(dev).requires_grad_(True)
     table = torch.randn((8, 10, 10, 10, 4), generator=g).to(dev).requires_grad_(True)
     dout = torch.randn((B, nQ, 256), generator=g).to(dev) * 1e-3
-    kw = dict(num_heads=H, scale=0.125, shared_kv=True, rpe=A.RPEConfig(), vertices=verts, xyz=kxyz, dropout_p=0.1)
-    res = {}
+    kw = dict(num_heads=H, scale=0.125, shared_kv=True, rpe=A.RPEConfig(interp=interp), vertices=verts, xyz=kxyz, dropout_p=0.1)
+    res = {"config": cfg, "interp": interp}
     grads = {}
     rng_once = A.new_rng_state(dev, 1234)  # ONE dropout state for both paths: their gradients are then comparable
     for name, fused in (("gemm_path", False), ("fused_path", True)):
@@ -77,7 +79,7 @@ def main():
     lib = L.lib()
     st = L.stream_ptr()
     rng = A.begin_step(dev)
-    d = A._desc(L.VDETR_ATTN_SHARED_KV, B, H, nQ, nK, 0.125, table.detach(), A.RPEConfig(), verts, kxyz, None, None, 0.1, rng, 1)
+    d = A._desc(L.VDETR_ATTN_SHARED_KV, B, H, nQ, nK, 0.125, table.detach(), A.RPEConfig(interp=interp), verts, kxyz, None, None, 0.1, rng, 1)
     o = torch.empty((B, nQ, 256), device=dev)
     lse = torch.empty((B, nQ, H), device=dev)
     scores = torch.empty((B, nQ, H, nK), device=dev)

@@ -2,7 +2,8 @@
 """A/B of the two forward kernels of the 3DV-RPE attention (vdetr_attn_desc.fwd_kernel: 0 = persistent workgroups,
 attn_fwd_pipe.hip; 1 = one workgroup per (query quad, key chunk), attn_fwd.hip): same inputs, outputs compared, launches timed
 interleaved with HIP events in one process.
-    python tools/fwd_ab.py [c2|c5] [--reps N] [--with-fps] [--cases]
+    python tools/fwd_ab.py [c2|c5] [--reps N] [--with-fps] [--cases] [--interp bilinear|nearest]
+--interp: the look-up mode of the table (rpe_quant "bilinear_*" / "nearest_*"; default bilinear), all three kernels alike.
 --cases: small ragged shapes (nQ % 4 != 0, nK % 16 != 0, general vertices, no dropout / no stored scores) checked against the
 grid kernel as well."""
 import ctypes
@@ -17,6 +18,7 @@ import bench  # noqa: E402
 from vdetr_amd import _lib as L  # noqa: E402
 from vdetr_amd import attention as A  # noqa: E402
 
+INTERP = sys.argv[sys.argv.index("--interp") + 1] if "--interp" in sys.argv else "bilinear"
 SIGNS = [[1, 1, -1], [1, -1, -1], [-1, -1, -1], [-1, 1, -1], [1, 1, 1], [1, -1, 1], [-1, -1, 1], [-1, 1, 1]]
 
 
@@ -53,7 +55,7 @@ class Runner:
         c = case
         self.c = c
         dev = c["q"].device
-        self.d = A._desc(L.VDETR_ATTN_SHARED_KV, c["B"], 4, c["nQ"], c["nK"], 0.125, c["table"], A.RPEConfig(), c["verts"], c["kxyz"],
+        self.d = A._desc(L.VDETR_ATTN_SHARED_KV, c["B"], 4, c["nQ"], c["nK"], 0.125, c["table"], A.RPEConfig(interp=INTERP), c["verts"], c["kxyz"],
                          c["cos_sin"], None, dropout, rng if dropout > 0 else None, 1)
         self.d.fwd_kernel = kernel
         self.out = torch.empty_like(c["q"])
@@ -151,6 +153,6 @@ if __name__ == "__main__":
     t = time_pair(case, 0.1, reps, rng)
     torch.cuda.synchronize()
     ok &= compare(case, 0.1, True, rng, cfg + " (after the timed launches)")
-    t.update({"config": cfg, "with_fps": "--with-fps" in sys.argv, "all_ok": bool(ok)})
+    t.update({"config": cfg, "interp": INTERP, "with_fps": "--with-fps" in sys.argv, "all_ok": bool(ok)})
     print(json.dumps(t), flush=True)
     sys.exit(0 if ok else 1)

@@ -15,6 +15,7 @@ c_int, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void
 
 VDETR_ATTN_SHARED_KV, VDETR_ATTN_PER_HEAD = 0, 1
 VDETR_MASK_NONE, VDETR_MASK_BOOL, VDETR_MASK_FLOAT = 0, 1, 2
+VDETR_RPE_BILINEAR, VDETR_RPE_NEAREST = 0, 1
 
 
 class AttnDesc(ctypes.Structure):
@@ -24,6 +25,7 @@ class AttnDesc(ctypes.Structure):
         ("kind", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("nQ", ctypes.c_int32),
         ("nK", ctypes.c_int32), ("scale", c_float),
         ("table", c_void_p), ("table_size", ctypes.c_int32), ("log_scale", c_float), ("inv_log_norm", c_float),
+        ("rpe_interp", ctypes.c_int32),
         ("vertices", c_void_p), ("xyz", c_void_p), ("cos_sin", c_void_p),
         ("mask", c_void_p), ("mask_kind", ctypes.c_int32),
         ("dropout_p", c_float), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),

@@ -28,7 +28,12 @@ HEAD_DIM = 64
 class RPEConfig:
     """Static parameters of the 3DV-RPE lookup (vdetr_transformer.py:671-683,722-723)."""
 
-    def __init__(self, table_size=10, log_scale=512.0, max_value=4.0):
+    INTERP = {"bilinear": L.VDETR_RPE_BILINEAR, "nearest": L.VDETR_RPE_NEAREST}  # F.grid_sample modes that are built
+
+    def __init__(self, table_size=10, log_scale=512.0, max_value=4.0, interp="bilinear"):
+        if interp not in self.INTERP:
+            raise NotImplementedError(f"RPE interpolation '{interp}' (built: 'bilinear' and 'nearest')")
+        self.interp = interp
         self.table_size = int(table_size)
         self.log_scale = float(log_scale)
         self.max_value = float(max_value)
@@ -485,6 +490,7 @@ def _desc(kind, B, H, nQ, nK, scale, table, rpe, vertices, xyz, cos_sin, mask, d
     if table is not None:
         d.table = table.data_ptr()
         d.table_size, d.log_scale, d.inv_log_norm = rpe.table_size, rpe.log_scale, rpe.inv_log_norm
+        d.rpe_interp = RPEConfig.INTERP[rpe.interp]
         d.vertices, d.xyz = vertices.data_ptr(), xyz.data_ptr()
         d.cos_sin = cos_sin.data_ptr() if cos_sin is not None else None
     if mask is not None:

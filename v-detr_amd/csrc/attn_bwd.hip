@@ -95,7 +95,9 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // VLOOP: a wave takes every (VERTS*WPV)-th chunk and walks ALL the workgroup's vertices for it, so the element-wise
 // softmax backward (loads, exp, dropout hash, stores: ~85 of ~385 VALU instructions per (chunk, vertex)) is done once
 // per chunk and workgroup instead of once per vertex.
-template <bool FIXED, int VERTS, int WPV, bool SPLIT16, bool VLOOP>
+// NEAREST (rpe_interp "nearest"): the taps carry 0 / 1 indicator weights (attn_common.h: rpe_axis), so every product below is
+// dS x 1 or dS x 0 and the grouping, the matrix product and the histogram are the bilinear kernel's.
+template <bool FIXED, int VERTS, int WPV, bool SPLIT16, bool VLOOP, bool NEAREST = false>
 __global__ __launch_bounds__(VERTS * WPV * kWave) void attn_bwd_scores_rpe_mm_kernel(AttnParams P) {
   constexpr int kThreads = VERTS * WPV * kWave;
   constexpr int kChunkStride = VLOOP ? VERTS * WPV : WPV;
@@ -267,7 +269,7 @@ __global__ __launch_bounds__(VERTS * WPV * kWave) void attn_bwd_scores_rpe_mm_ke
       // ---- lookup geometry of (pair, vertex) ------------------------------------------------------------------------
       float dx = vxs[vl] - ops.kx, dy = vys[vl] - ops.ky, dz = vzs[vl] - ops.kz;
       if (rot) rpe_rotate(dx, dy, rc, rs);
-      const AxisTap ax = rpe_axis(dx, P), ay = rpe_axis(dy, P), az = rpe_axis(dz, P);
+      const AxisTap ax = rpe_axis<NEAREST>(dx, P), ay = rpe_axis<NEAREST>(dy, P), az = rpe_axis<NEAREST>(dz, P);
       const int cell = rpe_cell(ax, ay, az, T);
       const float w00 = az.wa * ay.wa, w01 = az.wa * ay.wb, w10 = az.wb * ay.wa, w11 = az.wb * ay.wb;
       const float wgt[8] = {w00 * ax.wa, w00 * ax.wb, w01 * ax.wa, w01 * ax.wb,
@@ -540,6 +542,12 @@ extern "C" size_t vdetr_attn_bwd_workspace_bytes(const vdetr_attn_desc* d) {
 
 template <bool FIXED, int VERTS, int WPV, bool SPLIT16, bool VLOOP>
 static int launch_mm(const AttnParams& P, int grid, size_t lds, hipStream_t st) {
+  if (P.rpe_nearest) {
+    if (int e = set_lds(attn_bwd_scores_rpe_mm_kernel<FIXED, VERTS, WPV, SPLIT16, VLOOP, true>, lds, "attn_bwd_scores")) return e;
+    hipLaunchKernelGGL((attn_bwd_scores_rpe_mm_kernel<FIXED, VERTS, WPV, SPLIT16, VLOOP, true>), dim3(grid),
+                       dim3(VERTS * WPV * kWave), lds, st, P);
+    return VDETR_OK;
+  }
   if (int e = set_lds(attn_bwd_scores_rpe_mm_kernel<FIXED, VERTS, WPV, SPLIT16, VLOOP>, lds, "attn_bwd_scores")) return e;
   hipLaunchKernelGGL((attn_bwd_scores_rpe_mm_kernel<FIXED, VERTS, WPV, SPLIT16, VLOOP>), dim3(grid),
                      dim3(VERTS * WPV * kWave), lds, st, P);

@@ -58,6 +58,9 @@ __device__ __forceinline__ int b4_round(float x) {  // floor(x + 0.5): one instr
   return r;
 }
 
+// NEAREST (rpe_interp "nearest"): 0 / 1 indicator weights in the five taps (attn_common.h: rpe_axis); signatures, sort, matrix
+// products and the histogram are unchanged — a group's sums are then sums of dS over the pairs that chose the cell.
+template <bool NEAREST>
 __global__ __launch_bounds__(kB4Threads) void attn_bwd_box4_kernel(AttnParams P) {
   constexpr int T = kB4T, T3 = T * T * T;
   if (P.bwd_aux[4] != 0 || P.bwd_aux[5] == 0) return;  // a query is not an axis-aligned box: the general kernel runs instead
@@ -162,9 +165,9 @@ __global__ __launch_bounds__(kB4Threads) void attn_bwd_box4_kernel(AttnParams P)
         rpe_rotate(dx0, dy0, rc, rs);
         dx1 = dx0 + X1; dy1 = dy0 + Y1;
       }
-      const AxisTap az = rpe_axis(Zp - ops.kz, P);
-      const AxisTap ay0 = rpe_axis(dy0, P), ay1 = rpe_axis(dy1, P);
-      const AxisTap ax0 = rpe_axis(dx0, P), ax1 = rpe_axis(dx1, P);
+      const AxisTap az = rpe_axis<NEAREST>(Zp - ops.kz, P);
+      const AxisTap ay0 = rpe_axis<NEAREST>(dy0, P), ay1 = rpe_axis<NEAREST>(dy1, P);
+      const AxisTap ax0 = rpe_axis<NEAREST>(dx0, P), ax1 = rpe_axis<NEAREST>(dx1, P);
       // signature = the cell numbers the flush needs: (z T + y0) T | (z T + y1) T << 10 | x0 << 20 | x1 << 24
       const int zrow = az.base * (T * T);
       const int J = (zrow + ay0.base * T) | ((zrow + ay1.base * T) << 10) | (ax0.base << 20) | (ax1.base << 24);
@@ -301,8 +304,13 @@ __global__ __launch_bounds__(kB4Threads) void attn_bwd_box4_kernel(AttnParams P)
 
 int launch_attn_bwd_box4(const AttnParams& P, int grid, hipStream_t st) {
   const size_t lds = attn_bwd_box4_lds_bytes();
-  if (int e = set_lds(attn_bwd_box4_kernel, lds, "attn_bwd_box4")) return e;
-  hipLaunchKernelGGL(attn_bwd_box4_kernel, dim3(grid), dim3(kB4Threads), lds, st, P);
+  if (P.rpe_nearest) {
+    if (int e = set_lds(attn_bwd_box4_kernel<true>, lds, "attn_bwd_box4")) return e;
+    hipLaunchKernelGGL(attn_bwd_box4_kernel<true>, dim3(grid), dim3(kB4Threads), lds, st, P);
+    return check_launch("attn_bwd_box4");
+  }
+  if (int e = set_lds(attn_bwd_box4_kernel<false>, lds, "attn_bwd_box4")) return e;
+  hipLaunchKernelGGL(attn_bwd_box4_kernel<false>, dim3(grid), dim3(kB4Threads), lds, st, P);
   return check_launch("attn_bwd_box4");
 }
 

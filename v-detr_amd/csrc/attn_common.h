@@ -31,6 +31,7 @@ struct AttnParams {
   const float* v;
   int k_stride, v_stride;  // floats between consecutive key rows
   int box_path;            // forward: the axis-aligned-box instantiation is launched too (see attn_fwd.hip)
+  int rpe_nearest;         // vdetr_attn_desc.rpe_interp == VDETR_RPE_NEAREST: read by the host dispatch only (it picks the NEAREST instantiations)
   const unsigned* bwd_aux; // {max |dO row|^2, max |V row|^2, query counter half 0, half 1} or NULL
   float* out;
   float* lse;
@@ -134,6 +135,10 @@ struct AxisTap {
 // v_med3_f32 clamps: __saturatef / fminf(fmaxf()) expand to compare+select pairs (4 instructions per weight, measured
 // 192 of the forward kernel's ~950 VALU instructions per 64 pairs)
 __device__ __forceinline__ float sat01(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, 1.f); }
+// NEAREST (grid_sample mode "nearest": the one cell r = rint(pix), ties to even as ATen's nearbyint, v_rndne_f32; 0 outside
+// 0..T-1): the same two cells carry the indicator weights wa = (r == base), wb = (r == base + 1) — both zero exactly where r is
+// out of range, on either side — so everything built on the taps (the table-gradient kernels) serves both modes.
+template <bool NEAREST = false>
 __device__ __forceinline__ AxisTap rpe_axis(float d, const AttnParams& P) {
   const float L = __log2f(__builtin_fmaf(fabsf(d), P.log_scale, 1.0f));
   const float pix = __builtin_fmaf(copysignf(L, d), P.pix_mul, P.pix_add);
@@ -143,7 +148,22 @@ __device__ __forceinline__ AxisTap rpe_axis(float d, const AttnParams& P) {
   a.base = (int)bf;
   a.wa = sat01(1.f - fabsf(t));
   a.wb = sat01(1.f - fabsf(t - 1.f));
+  if constexpr (NEAREST) {
+    const float r = rintf(pix);
+    a.wa = r == bf ? 1.f : 0.f;
+    a.wb = r == bf + 1.f ? 1.f : 0.f;
+  }
   return a;
+}
+// NEAREST, forward: the cell of one axis times its stride, or kRpeOut outside the table.  A vertex's three offsets are added and
+// the sum is clamped to the index of a zero float4 that the kernels keep behind their LDS table image (rpe_zero_cell): any
+// out-of-range axis lands there, without a branch and without a select per head.
+constexpr int kRpeOut = 1 << 20;  // above every cell index (8 T^3 <= 8000), three of them far below 2^31
+__device__ __forceinline__ int rpe_axis_nearest(float d, float log_scale, float pix_mul, float pix_add, int T, int stride) {
+  const float L = __log2f(__builtin_fmaf(fabsf(d), log_scale, 1.0f));
+  const float pix = __builtin_fmaf(copysignf(L, d), pix_mul, pix_add);
+  const int r = (int)rintf(pix);  // |pix| < 2^10: log2 of a finite float
+  return (unsigned)r < (unsigned)T ? r * stride : kRpeOut;
 }
 
 // x -> LAST table axis, y -> middle, z -> FIRST (grid_sample: x=W, y=H, z=D)
@@ -161,10 +181,26 @@ __device__ __forceinline__ void rpe_rotate(float& dx, float& dy, float c, float 
 }
 
 // bias of one (query, key) pair for the 4 heads; tab = LDS image [8][T^3] of float4 (heads)
+// NEAREST: one 16-byte read per vertex, no weights; `zero` = index of the zero cell behind the image
+template <bool NEAREST = false>
 __device__ __forceinline__ void rpe_pair_bias(const AttnParams& P, const f32x4* tab, const float (&vx)[8],
                                               const float (&vy)[8], const float (&vz)[8], float kx, float ky,
-                                              float kz, bool rot, float rc, float rs, float (&acc)[4]) {
+                                              float kz, bool rot, float rc, float rs, float (&acc)[4], int zero = 0) {
   const int T = P.T, TT = T * T, T3 = TT * T;
+  if constexpr (NEAREST) {
+#pragma unroll
+    for (int i = 0; i < kRpeVerts; ++i) {
+      float dx = vx[i] - kx, dy = vy[i] - ky, dz = vz[i] - kz;
+      if (rot) rpe_rotate(dx, dy, rc, rs);
+      const int cell = rpe_axis_nearest(dx, P.log_scale, P.pix_mul, P.pix_add, T, 1) +
+                       rpe_axis_nearest(dy, P.log_scale, P.pix_mul, P.pix_add, T, T) +
+                       rpe_axis_nearest(dz, P.log_scale, P.pix_mul, P.pix_add, T, TT);
+      const f32x4 cv = tab[min(i * T3 + cell, zero)];
+#pragma unroll
+      for (int h = 0; h < 4; ++h) acc[h] += cv[h];
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < kRpeVerts; ++i) {
     float dx = vx[i] - kx, dy = vy[i] - ky, dz = vz[i] - kz;
@@ -212,9 +248,27 @@ __device__ __forceinline__ bool rpe_box_pattern(const float (&vx)[8], const floa
   return ok;
 }
 // the two offsets per axis given directly (dx[a] = x value a of the box minus the key, in the frame the table is looked up in)
+// NEAREST: six axis cells, composed per vertex; one read per vertex
+template <bool NEAREST = false>
 __device__ __forceinline__ void rpe_pair_bias_box_d(const AttnParams& P, const f32x4* tab, const float (&dx)[2],
-                                                    const float (&dy)[2], const float (&dz)[2], float (&acc)[4]) {
+                                                    const float (&dy)[2], const float (&dz)[2], float (&acc)[4], int zero = 0) {
   const int T = P.T, TT = T * T, T3 = TT * T;
+  if constexpr (NEAREST) {
+    int cx[2], cy[2], cz[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      cx[a] = rpe_axis_nearest(dx[a], P.log_scale, P.pix_mul, P.pix_add, T, 1);
+      cy[a] = rpe_axis_nearest(dy[a], P.log_scale, P.pix_mul, P.pix_add, T, T);
+      cz[a] = rpe_axis_nearest(dz[a], P.log_scale, P.pix_mul, P.pix_add, T, TT);
+    }
+#pragma unroll
+    for (int i = 0; i < kRpeVerts; ++i) {
+      const f32x4 cv = tab[min(i * T3 + cz[rpe_box_zi(i)] + cy[rpe_box_yi(i)] + cx[rpe_box_xi(i)], zero)];
+#pragma unroll
+      for (int h = 0; h < 4; ++h) acc[h] += cv[h];
+    }
+    return;
+  }
   const AxisTap ax[2] = {rpe_axis(dx[0], P), rpe_axis(dx[1], P)};
   const AxisTap ay[2] = {rpe_axis(dy[0], P), rpe_axis(dy[1], P)};
   const AxisTap az[2] = {rpe_axis(dz[0], P), rpe_axis(dz[1], P)};
@@ -259,11 +313,12 @@ __device__ __forceinline__ void rpe_pair_bias_box_d(const AttnParams& P, const f
   }
 }
 
+template <bool NEAREST = false>
 __device__ __forceinline__ void rpe_pair_bias_box(const AttnParams& P, const f32x4* tab, const float (&X)[2],
                                                   const float (&Y)[2], const float (&Z)[2], float kx, float ky, float kz,
-                                                  float (&acc)[4]) {
+                                                  float (&acc)[4], int zero = 0) {
   const float dx[2] = {X[0] - kx, X[1] - kx}, dy[2] = {Y[0] - ky, Y[1] - ky}, dz[2] = {Z[0] - kz, Z[1] - kz};
-  rpe_pair_bias_box_d(P, tab, dx, dy, dz, acc);
+  rpe_pair_bias_box_d<NEAREST>(P, tab, dx, dy, dz, acc, zero);
 }
 // angle_type "object_coords": in the frame the offsets are turned into (rpe_rotate by the query's angle) the corners of a ROTATED
 // box are an axis-aligned box: R (P_i - P_0) = (xi EX, yi EY, zi EZ) with the edges of vertices 3, 1 and 4 — the test of

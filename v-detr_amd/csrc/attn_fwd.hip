@@ -61,8 +61,11 @@ __device__ __forceinline__ void fwd_split4(const f32x4& x, bf16x4& hi, bf16x4& l
   }
 }
 
-template <bool PERHEAD, bool RPE, bool BOX = false, bool BF16 = false, int WAVES = kFwdWaves>
+// NEAREST (RPE only): rpe_interp "nearest" — one table cell per vertex (attn_common.h); a zero float4 behind the P pads is the
+// cell of every out-of-range vertex (the host reserves 16 more bytes).
+template <bool PERHEAD, bool RPE, bool BOX = false, bool BF16 = false, int WAVES = kFwdWaves, bool NEAREST = false>
 __device__ __forceinline__ void attn_fwd_body(AttnParams P) {
+  static_assert(RPE || !NEAREST, "NEAREST is a mode of the RPE look-up");
   static_assert(WAVES == 8 || WAVES == 4, "the merge of the wave states is written for 8 or 4 waves");
   static_assert(!(BF16 && PERHEAD), "the bf16 path is built for the shared-KV kinds");
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -96,6 +99,8 @@ __device__ __forceinline__ void attn_fwd_body(AttnParams P) {
   }
   const float bX[2] = {vx[0], vx[2]}, bY[2] = {vy[0], vy[1]}, bZ[2] = {vz[0], vz[4]};
   if (RPE) rpe_stage_table(P, tab, tid, WAVES * kWave);
+  const int zero_cell = NEAREST ? (table_floats + WAVES * 16 * kPPad) / 4 : 0;
+  if (NEAREST && tid == 0) tab[zero_cell] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- A operand of QK^T: row i = c ---------------------------------------------------------------
   float qa[BF16 ? 1 : 16];
@@ -214,12 +219,12 @@ __device__ __forceinline__ void attn_fwd_body(AttnParams P) {
           const float d0z = vz[0] - ops.kz;
           rpe_rotate(d0x, d0y, rc, rs);
           const float dx[2] = {d0x, d0x + eX}, dy[2] = {d0y, d0y + eY}, dz[2] = {d0z, d0z + eZ};
-          rpe_pair_bias_box_d(P, tab, dx, dy, dz, sc);
+          rpe_pair_bias_box_d<NEAREST>(P, tab, dx, dy, dz, sc, zero_cell);
         } else {
-          rpe_pair_bias_box(P, tab, bX, bY, bZ, ops.kx, ops.ky, ops.kz, sc);
+          rpe_pair_bias_box<NEAREST>(P, tab, bX, bY, bZ, ops.kx, ops.ky, ops.kz, sc, zero_cell);
         }
       } else {
-        rpe_pair_bias(P, tab, vx, vy, vz, ops.kx, ops.ky, ops.kz, rot, rc, rs, sc);
+        rpe_pair_bias<NEAREST>(P, tab, vx, vy, vz, ops.kx, ops.ky, ops.kz, rot, rc, rs, sc, zero_cell);
       }
     }
     // ---- mask, tail ------------------------------------------------------------------------------
@@ -380,7 +385,8 @@ __global__ __launch_bounds__(4 * kWave) void attn_fwd_perhead4_kernel(AttnParams
 // immediate exits per layer (6 us with the 133 KB LDS reservation); both bodies use the same register budget.
 // Only BF16 = false is instantiated (with bf16 operands the merged kernel spills 11 registers: vdetr_attn_fwd_bf16 launches the
 // two instantiations side by side); the parameter stays so that the kernel keeps its symbol.
-template <bool BF16>
+// NEAREST: rpe_interp "nearest", the same launch shape around the one-cell look-up
+template <bool BF16, bool NEAREST = false>
 __global__ __launch_bounds__(kFwdThreads) void attn_fwd_rpe_auto_kernel(AttnParams P) {
   const int g = (threadIdx.x & 63) >> 4;
   const int q_pair = min((int)blockIdx.x * 4 + g, P.nQ - 1);
@@ -396,8 +402,13 @@ __global__ __launch_bounds__(kFwdThreads) void attn_fwd_rpe_auto_kernel(AttnPara
     float ex, ey, ez;
     box = P.box_path && __all(rpe_box_pattern_rot(vx, vy, vz, rc, rs, ex, ey, ez));
   }
-  if (box) attn_fwd_body<false, true, true, BF16>(P);
-  else attn_fwd_body<false, true, false, BF16>(P);
+  if (box) attn_fwd_body<false, true, true, BF16, kFwdWaves, NEAREST>(P);
+  else attn_fwd_body<false, true, false, BF16, kFwdWaves, NEAREST>(P);
+}
+// rpe_interp "nearest" with bf16 operands: the two instantiations side by side, as vdetr_attn_fwd_bf16 launches the bilinear ones
+template <bool BOX>
+__global__ __launch_bounds__(kFwdThreads) void attn_fwd_bf16_nearest_kernel(AttnParams P) {
+  attn_fwd_body<false, true, BOX, true, kFwdWaves, true>(P);
 }
 
 
@@ -429,10 +440,13 @@ __global__ __launch_bounds__(256) void attn_fwd_combine_kernel(AttnParams P) {
 }
 
 // ---- stand-alone RPE bias (parity hook for vdetr_transformer.py:710-731) ------------------------------
-__global__ __launch_bounds__(256) void rpe_bias_kernel(AttnParams P, float* rpe) {
+template <bool NEAREST>
+__device__ __forceinline__ void rpe_bias_body(const AttnParams& P, float* rpe) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   f32x4* tab = reinterpret_cast<f32x4*>(smem);
   rpe_stage_table(P, tab, threadIdx.x, 256);
+  const int zero_cell = NEAREST ? kRpeVerts * P.T * P.T * P.T : 0;  // NEAREST: the zero cell behind the image
+  if (NEAREST && threadIdx.x == 0) tab[zero_cell] = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
   const int b = blockIdx.z, q = blockIdx.y;
   const float* vp = P.vertices + ((size_t)b * P.nQ + q) * 24;
@@ -445,11 +459,13 @@ __global__ __launch_bounds__(256) void rpe_bias_kernel(AttnParams P, float* rpe)
   for (int key = blockIdx.x * 256 + threadIdx.x; key < P.nK; key += gridDim.x * 256) {
     const float* xp = P.xyz + ((size_t)b * P.nK + key) * 3;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    rpe_pair_bias(P, tab, vx, vy, vz, xp[0], xp[1], xp[2], rot, rc, rs, acc);
+    rpe_pair_bias<NEAREST>(P, tab, vx, vy, vz, xp[0], xp[1], xp[2], rot, rc, rs, acc, zero_cell);
 #pragma unroll
     for (int h = 0; h < 4; ++h) rpe[(((size_t)b * P.nQ + q) * 4 + h) * P.nK + key] = acc[h];
   }
 }
+__global__ __launch_bounds__(256) void rpe_bias_kernel(AttnParams P, float* rpe) { rpe_bias_body<false>(P, rpe); }
+__global__ __launch_bounds__(256) void rpe_bias_nearest_kernel(AttnParams P, float* rpe) { rpe_bias_body<true>(P, rpe); }
 
 // ---- MFMA layout self test: C[16][16] = A[16][64] * B[16][64]^T with the operand mapping used above ----
 __global__ void mfma_selftest_kernel(const float* a, const float* b, float* cmat) {
@@ -477,6 +493,8 @@ int attn_fill_params(const vdetr_attn_desc* d, AttnParams* P, const char* op) {
                 "%s: shared-KV attention is built for %d heads (got %d)", op, kRpeHeads, d->H);
   VDETR_REQUIRE(d->dropout_p >= 0.f && d->dropout_p < 1.f, "%s: dropout_p %f outside [0,1)", op, d->dropout_p);
   VDETR_REQUIRE(d->mask_kind == VDETR_MASK_NONE || d->mask != nullptr, "%s: mask_kind set but mask is null", op);
+  VDETR_REQUIRE(d->rpe_interp == VDETR_RPE_BILINEAR || d->rpe_interp == VDETR_RPE_NEAREST,
+                "%s: rpe_interp %d (VDETR_RPE_BILINEAR = 0 or VDETR_RPE_NEAREST = 1)", op, d->rpe_interp);
   *P = AttnParams{};
   P->kind = d->kind; P->B = d->B; P->H = d->H; P->nQ = d->nQ; P->nK = d->nK; P->scale = d->scale;
   const int dense = d->kind == VDETR_ATTN_PER_HEAD ? d->H * 64 : 64;
@@ -497,6 +515,7 @@ int attn_fill_params(const vdetr_attn_desc* d, AttnParams* P, const char* op) {
     P->pix_mul = d->inv_log_norm * 0.5f * (float)d->table_size;
     P->pix_add = 0.5f * (float)(d->table_size - 1);
     P->vertices = d->vertices; P->xyz = d->xyz; P->cos_sin = d->cos_sin;
+    P->rpe_nearest = d->rpe_interp == VDETR_RPE_NEAREST ? 1 : 0;
   }
   P->mask = d->mask; P->mask_kind = d->mask ? d->mask_kind : VDETR_MASK_NONE;
   if (d->dropout_p > 0.f) {
@@ -514,7 +533,7 @@ int attn_fill_params(const vdetr_attn_desc* d, AttnParams* P, const char* op) {
   return VDETR_OK;
 }
 
-int attn_fwd_pipe_launch(const AttnParams& P, unsigned* counter, int workgroups, char* kv_img, int split, bool packed, bool src_f32, hipStream_t st);  // attn_fwd_pipe.hip
+int attn_fwd_pipe_launch(const AttnParams& P, unsigned* counter, int workgroups, char* kv_img, int split, bool packed, bool src_f32, hipStream_t st);  // attn_fwd_pipe.hip (reads P.rpe_nearest)
 int attn_fwd_pack_launch(const void* k, const void* v, int B, int nK, int k_stride, int v_stride, int nlayers, long layer_stride, char* img,
                          int split, bool src_f32, hipStream_t st);
 size_t attn_fwd_pipe_img_bytes(int B, int nK, int split);
@@ -627,9 +646,10 @@ static int attn_fwd_run(const vdetr_attn_desc* d, const float* q, const float* k
   char* kv_img = pipe_split(d) ? (d->kv_img ? (char*)d->kv_img : (char*)((ws_top + 255) & ~(uintptr_t)255)) : nullptr;
   VDETR_REQUIRE(!d->kv_img || (((uintptr_t)d->kv_img) & 15) == 0, "attn_fwd: kv_img must be 16-B aligned");
   const size_t lds_table = rpe ? (size_t)kRpeVerts * P.T * P.T * P.T * 16 : 0;
-  const size_t lds = lds_table + (size_t)kFwdWaves * 16 * kPPad * 4 > (size_t)kFwdWaves * kWave * 24 * 4
-                         ? lds_table + (size_t)kFwdWaves * 16 * kPPad * 4
-                         : (size_t)kFwdWaves * kWave * 24 * 4;
+  const size_t lds_bilinear = lds_table + (size_t)kFwdWaves * 16 * kPPad * 4 > (size_t)kFwdWaves * kWave * 24 * 4
+                                  ? lds_table + (size_t)kFwdWaves * 16 * kPPad * 4
+                                  : (size_t)kFwdWaves * kWave * 24 * 4;
+  const size_t lds = lds_bilinear + (P.rpe_nearest ? 16 : 0);  // nearest: the zero cell behind the pads
   hipStream_t st = (hipStream_t)stream;
   if (pipe) {
     VDETR_REQUIRE((size_t)d->nK * P.k_stride < (1u << 30) && (size_t)d->nK * P.v_stride < (1u << 30) && (size_t)4 * d->nK < (1u << 30),
@@ -655,8 +675,13 @@ static int attn_fwd_run(const vdetr_attn_desc* d, const float* q, const float* k
       // one launch, the box / general body chosen per workgroup on the device; rotated boxes take the box body too
       // (docs/DESIGN_rounds1-4.md 4.3)
       P.box_path = true;
-      if (int e = set_lds(attn_fwd_rpe_auto_kernel<false>, lds, "attn_fwd")) return e;
-      hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<false>), grid, dim3(kFwdThreads), lds, st, P);
+      if (P.rpe_nearest) {
+        if (int e = set_lds(attn_fwd_rpe_auto_kernel<false, true>, lds, "attn_fwd")) return e;
+        hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<false, true>), grid, dim3(kFwdThreads), lds, st, P);
+      } else {
+        if (int e = set_lds(attn_fwd_rpe_auto_kernel<false>, lds, "attn_fwd")) return e;
+        hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<false>), grid, dim3(kFwdThreads), lds, st, P);
+      }
     } else {
       if (int e = set_lds(attn_fwd_kernel<false, false>, lds, "attn_fwd")) return e;
       hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, dim3(kFwdThreads), lds, st, P);
@@ -743,12 +768,19 @@ extern "C" int vdetr_attn_fwd_bf16(const vdetr_attn_desc* d, const void* q, cons
     return VDETR_OK;
   }
   const size_t lds_table = rpe ? (size_t)kRpeVerts * P.T * P.T * P.T * 16 : 0;
-  const size_t lds = lds_table + (size_t)kFwdWaves * 16 * kPPad * 4 > (size_t)kFwdWaves * kWave * 24 * 4
-                         ? lds_table + (size_t)kFwdWaves * 16 * kPPad * 4
-                         : (size_t)kFwdWaves * kWave * 24 * 4;
+  const size_t lds_bilinear = lds_table + (size_t)kFwdWaves * 16 * kPPad * 4 > (size_t)kFwdWaves * kWave * 24 * 4
+                                  ? lds_table + (size_t)kFwdWaves * 16 * kPPad * 4
+                                  : (size_t)kFwdWaves * kWave * 24 * 4;
+  const size_t lds = lds_bilinear + (P.rpe_nearest ? 16 : 0);  // nearest: the zero cell behind the pads
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((d->nQ + 3) / 4, ks, d->B);
-  if (rpe) {
+  if (rpe && P.rpe_nearest) {
+    P.box_path = true;
+    if (int e = set_lds(attn_fwd_bf16_nearest_kernel<false>, lds, "attn_fwd_bf16")) return e;
+    hipLaunchKernelGGL(attn_fwd_bf16_nearest_kernel<false>, grid, dim3(kFwdThreads), lds, st, P);
+    if (int e = set_lds(attn_fwd_bf16_nearest_kernel<true>, lds, "attn_fwd_bf16")) return e;
+    hipLaunchKernelGGL(attn_fwd_bf16_nearest_kernel<true>, grid, dim3(kFwdThreads), lds, st, P);
+  } else if (rpe) {
     // the general and the box instantiation side by side over the same grid (the merged kernel of the fp32 path spills 11
     // registers when built for bf16 operands)
     P.box_path = true;
@@ -774,10 +806,15 @@ extern "C" int vdetr_rpe_bias_f32(const vdetr_attn_desc* d, float* rpe, vdetr_st
   if (int e = attn_fill_params(d, &P, "rpe_bias")) return e;
   VDETR_REQUIRE(d->table && rpe, "rpe_bias: null pointer");
   VDETR_REQUIRE(d->nQ <= 65535, "rpe_bias: nQ=%d > 65535", d->nQ);
-  const size_t lds = (size_t)kRpeVerts * P.T * P.T * P.T * 16;
-  if (int e = set_lds(rpe_bias_kernel, lds, "rpe_bias")) return e;
+  const size_t lds = (size_t)kRpeVerts * P.T * P.T * P.T * 16 + (P.rpe_nearest ? 16 : 0);
   dim3 grid(min(ceil_div(d->nK, 256), 64), d->nQ, d->B);
-  hipLaunchKernelGGL(rpe_bias_kernel, grid, dim3(256), lds, (hipStream_t)stream, P, rpe);
+  if (P.rpe_nearest) {
+    if (int e = set_lds(rpe_bias_nearest_kernel, lds, "rpe_bias")) return e;
+    hipLaunchKernelGGL(rpe_bias_nearest_kernel, grid, dim3(256), lds, (hipStream_t)stream, P, rpe);
+  } else {
+    if (int e = set_lds(rpe_bias_kernel, lds, "rpe_bias")) return e;
+    hipLaunchKernelGGL(rpe_bias_kernel, grid, dim3(256), lds, (hipStream_t)stream, P, rpe);
+  }
   return check_launch("rpe_bias");
 }
 

@@ -40,6 +40,10 @@ constexpr int kLdsMl = kLdsPad + kPipeWaves * 16 * kPipePad * 4;   // 138,240: [
 constexpr int kLdsXch = kLdsMl + kPipeWaves * 4 * 8 * 4;           // 139,264: [8 waves][8 slots][64 lanes] floats (16 KB)
 constexpr int kLdsNext = kLdsXch + kPipeWaves * 8 * kWave * 4;     // 155,648: two item indices
 constexpr int kPipeLdsBytes = kLdsNext + 16;
+// NEAREST (rpe_interp "nearest"): one zero float4 behind everything else, the cell of every out-of-range vertex (attn_common.h)
+constexpr int kPipeZeroCell = kPipeLdsBytes / 16;
+constexpr int kPipeLdsBytesNearest = kPipeLdsBytes + 16;
+static_assert(kPipeLdsBytes % 16 == 0 && kPipeLdsBytesNearest <= 160 * 1024, "the zero cell is a 16-byte slot inside the 160 KB LDS");
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -90,7 +94,9 @@ struct PipeQuery {
 };
 
 // bias of the lane's role pair for the 4 heads, axis-aligned box (6 taps); ROT: one rotation of P_0 - X, then the edges
-template <bool ROT>
+// NEAREST: six axis cells (rint, range test: ~8 VALU each against ~11 of a tap), one 16-byte read and two v_pk_add_f32 per vertex
+// instead of eight reads, seven weight products and 16 v_pk_fma_f32; all eight reads are in flight before the first add
+template <bool ROT, bool NEAREST>
 __device__ __forceinline__ void pipe_bias_box(const AttnParams& P, const f32x4* tab, const PipeQuery& Q, float kx, float ky, float kz,
                                               f32x2& s01, f32x2& s23) {
   float dx[2], dy[2], dz[2];
@@ -104,6 +110,25 @@ __device__ __forceinline__ void pipe_bias_box(const AttnParams& P, const f32x4* 
     dx[0] = Q.x0 - kx; dx[1] = Q.x1 - kx;
     dy[0] = Q.y0 - ky; dy[1] = Q.y1 - ky;
     dz[0] = Q.z0 - kz; dz[1] = Q.z1 - kz;
+  }
+  if constexpr (NEAREST) {
+    int cx[2], cy[2], cz[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      cx[a] = rpe_axis_nearest(dx[a], P.log_scale, P.pix_mul, P.pix_add, kPT, 1);
+      cy[a] = rpe_axis_nearest(dy[a], P.log_scale, P.pix_mul, P.pix_add, kPT, kPT);
+      cz[a] = rpe_axis_nearest(dz[a], P.log_scale, P.pix_mul, P.pix_add, kPT, kPT * kPT);
+    }
+    f32x4 cv[kRpeVerts];
+#pragma unroll
+    for (int i = 0; i < kRpeVerts; ++i)
+      cv[i] = tab[min(i * kPCells + cz[rpe_box_zi(i)] + cy[rpe_box_yi(i)] + cx[rpe_box_xi(i)], kPipeZeroCell)];
+#pragma unroll
+    for (int i = 0; i < kRpeVerts; ++i) {
+      s01 += f32x2{cv[i][0], cv[i][1]};
+      s23 += f32x2{cv[i][2], cv[i][3]};
+    }
+    return;
   }
   const AxisTap ax[2] = {pipe_axis(dx[0], P.log_scale, P.pix_mul, P.pix_add), pipe_axis(dx[1], P.log_scale, P.pix_mul, P.pix_add)};
   const AxisTap ay[2] = {pipe_axis(dy[0], P.log_scale, P.pix_mul, P.pix_add), pipe_axis(dy[1], P.log_scale, P.pix_mul, P.pix_add)};
@@ -134,6 +159,7 @@ __device__ __forceinline__ void pipe_bias_box(const AttnParams& P, const f32x4* 
 }
 
 // any eight vertices (rolled: one vertex per trip, its coordinates re-read): the path of non-box `reference_point`s
+template <bool NEAREST>
 __device__ __forceinline__ void pipe_bias_general(const AttnParams& P, const f32x4* tab, const float* __restrict__ vp, bool rot, float rc,
                                                   float rs, float kx, float ky, float kz, f32x2& s01, f32x2& s23) {
 #pragma unroll 1
@@ -141,6 +167,15 @@ __device__ __forceinline__ void pipe_bias_general(const AttnParams& P, const f32
     float dx = vp[i * 3] - kx, dy = vp[i * 3 + 1] - ky;
     const float dz = vp[i * 3 + 2] - kz;
     if (rot) rpe_rotate(dx, dy, rc, rs);
+    if constexpr (NEAREST) {
+      const int cell = rpe_axis_nearest(dx, P.log_scale, P.pix_mul, P.pix_add, kPT, 1) +
+                       rpe_axis_nearest(dy, P.log_scale, P.pix_mul, P.pix_add, kPT, kPT) +
+                       rpe_axis_nearest(dz, P.log_scale, P.pix_mul, P.pix_add, kPT, kPT * kPT);
+      const f32x4 cv = tab[min(i * kPCells + cell, kPipeZeroCell)];
+      s01 += f32x2{cv[0], cv[1]};
+      s23 += f32x2{cv[2], cv[3]};
+      continue;
+    }
     const AxisTap ax = pipe_axis(dx, P.log_scale, P.pix_mul, P.pix_add), ay = pipe_axis(dy, P.log_scale, P.pix_mul, P.pix_add),
                   az = pipe_axis(dz, P.log_scale, P.pix_mul, P.pix_add);
     PipeCorners C;
@@ -252,7 +287,7 @@ struct PipeQT {
 };
 
 // one 16-key tile: scores, bias, online softmax, PV
-template <int MODE, bool TAIL, int SPLIT>
+template <int MODE, bool TAIL, int SPLIT, bool NEAREST>
 __device__ __forceinline__ void pipe_tile(const AttnParams& P, const f32x4* tab, float* ppad, const PipeLane& A, const PipeQuery& Q,
                                           const float* __restrict__ role_vp, const PipeQT<SPLIT>& QA, PipeTileT<SPLIT>& ops, int tile, int next, int b,
                                           int qrow, int g, int c, bool swapped, f32x4 (&o)[4], float (&m)[4], float (&l)[4]) {
@@ -282,8 +317,8 @@ __device__ __forceinline__ void pipe_tile(const AttnParams& P, const f32x4* tab,
   const float kx = ops.kx, ky = ops.ky, kz = ops.kz;
   pipe_fetch_x<SPLIT>(A, next, nK, c, ops);
   f32x2 s01 = {0.f, 0.f}, s23 = {0.f, 0.f};
-  if (MODE == kPipeGeneral) pipe_bias_general(P, tab, role_vp, P.cos_sin != nullptr, Q.rc, Q.rs, kx, ky, kz, s01, s23);
-  else pipe_bias_box<MODE == kPipeBoxRot>(P, tab, Q, kx, ky, kz, s01, s23);
+  if (MODE == kPipeGeneral) pipe_bias_general<NEAREST>(P, tab, role_vp, P.cos_sin != nullptr, Q.rc, Q.rs, kx, ky, kz, s01, s23);
+  else pipe_bias_box<MODE == kPipeBoxRot, NEAREST>(P, tab, Q, kx, ky, kz, s01, s23);
   if constexpr (SPLIT) {  // (24 registers: requested behind the lookups, whose eight vertices are where the registers run out)
     __builtin_amdgcn_sched_barrier(0);
     pipe_fetch_k<SPLIT>(P, A, next, nK, c, ops);
@@ -371,7 +406,7 @@ __device__ __forceinline__ void pipe_tile(const AttnParams& P, const f32x4* tab,
   pipe_fetch_v<SPLIT>(P, A, next, nK, g, ops);
 }
 
-template <int MODE, int SPLIT>
+template <int MODE, int SPLIT, bool NEAREST>
 __device__ __forceinline__ void pipe_tiles(const AttnParams& P, const f32x4* tab, float* ppad, const PipeLane& A, const PipeQuery& Q,
                                            const float* __restrict__ role_vp, const PipeQT<SPLIT>& qa, PipeTileT<SPLIT>& ops, int tile_begin,
                                            int tile_end, int w, int b, int qrow, int g, int c, bool swapped, f32x4 (&o)[4],
@@ -381,13 +416,13 @@ __device__ __forceinline__ void pipe_tiles(const AttnParams& P, const f32x4* tab
   int tile = tile_begin + w;
   for (; tile < full_end; tile += kPipeWaves) {
     const int next = tile + kPipeWaves < tile_end ? tile + kPipeWaves : tile;  // (the wave's last tile re-reads itself: no branch)
-    pipe_tile<MODE, false, SPLIT>(P, tab, ppad, A, Q, role_vp, qa, ops, tile, next, b, qrow, g, c, swapped, o, m, l);
+    pipe_tile<MODE, false, SPLIT, NEAREST>(P, tab, ppad, A, Q, role_vp, qa, ops, tile, next, b, qrow, g, c, swapped, o, m, l);
   }
   if (tile < tile_end)  // the last tile of the key range, cut short by nK
-    pipe_tile<MODE, true, SPLIT>(P, tab, ppad, A, Q, role_vp, qa, ops, tile, tile, b, qrow, g, c, swapped, o, m, l);
+    pipe_tile<MODE, true, SPLIT, NEAREST>(P, tab, ppad, A, Q, role_vp, qa, ops, tile, tile, b, qrow, g, c, swapped, o, m, l);
 }
 
-template <bool ROT, int SPLIT>
+template <bool ROT, int SPLIT, bool NEAREST = false>
 __global__ __launch_bounds__(kPipeThreads) void attn_fwd_rpe_pipe_kernel(PipeArgs K) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   AttnParams& P = K.P;
@@ -422,6 +457,7 @@ __global__ __launch_bounds__(kPipeThreads) void attn_fwd_rpe_pipe_kernel(PipeArg
     if (nextbuf[0] >= K.nitems) return;
   }
   rpe_stage_table(P, reinterpret_cast<f32x4*>(smem), tid, kPipeThreads);
+  if (NEAREST && tid == 0) reinterpret_cast<f32x4*>(smem)[kPipeZeroCell] = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
   int item = nextbuf[0];
   int parity = 0;
@@ -521,9 +557,9 @@ __global__ __launch_bounds__(kPipeThreads) void attn_fwd_rpe_pipe_kernel(PipeArg
       pipe_fetch_v<SPLIT>(P, A, t0, nK, g, ops);
     }
     if (box)
-      pipe_tiles<ROT ? kPipeBoxRot : kPipeBox, SPLIT>(P, tab, ppad, A, Q, role_vp, qa, ops, tile_begin, tile_end, w, b, qrow, g, c, swapped, o, m, l);
+      pipe_tiles<ROT ? kPipeBoxRot : kPipeBox, SPLIT, NEAREST>(P, tab, ppad, A, Q, role_vp, qa, ops, tile_begin, tile_end, w, b, qrow, g, c, swapped, o, m, l);
     else
-      pipe_tiles<kPipeGeneral, SPLIT>(P, tab, ppad, A, Q, role_vp, qa, ops, tile_begin, tile_end, w, b, qrow, g, c, swapped, o, m, l);
+      pipe_tiles<kPipeGeneral, SPLIT, NEAREST>(P, tab, ppad, A, Q, role_vp, qa, ops, tile_begin, tile_end, w, b, qrow, g, c, swapped, o, m, l);
 
     // ---- merge of the 8 waves' online-softmax states: m / l per row (1 KB), then the accumulators in two halves of 16 KB ----
     if (tid == 0) {
@@ -714,8 +750,13 @@ int attn_fwd_pipe_launch(const AttnParams& P, unsigned* counter, int workgroups,
   }
 #define VDETR_PIPE_LAUNCH(ROT, SPLIT)                                                                                       \
   do {                                                                                                                      \
-    if (int e = set_lds(attn_fwd_rpe_pipe_kernel<ROT, SPLIT>, kPipeLdsBytes, "attn_fwd")) return e;                        \
-    hipLaunchKernelGGL((attn_fwd_rpe_pipe_kernel<ROT, SPLIT>), dim3(grid), dim3(kPipeThreads), kPipeLdsBytes, st, K);      \
+    if (P.rpe_nearest) {                                                                                                    \
+      if (int e = set_lds(attn_fwd_rpe_pipe_kernel<ROT, SPLIT, true>, kPipeLdsBytesNearest, "attn_fwd")) return e;         \
+      hipLaunchKernelGGL((attn_fwd_rpe_pipe_kernel<ROT, SPLIT, true>), dim3(grid), dim3(kPipeThreads), kPipeLdsBytesNearest, st, K); \
+    } else {                                                                                                                \
+      if (int e = set_lds(attn_fwd_rpe_pipe_kernel<ROT, SPLIT>, kPipeLdsBytes, "attn_fwd")) return e;                      \
+      hipLaunchKernelGGL((attn_fwd_rpe_pipe_kernel<ROT, SPLIT>), dim3(grid), dim3(kPipeThreads), kPipeLdsBytes, st, K);    \
+    }                                                                                                                       \
   } while (0)
   if (P.cos_sin) {
     if (split == 1) VDETR_PIPE_LAUNCH(true, 1); else if (split) VDETR_PIPE_LAUNCH(true, 3); else VDETR_PIPE_LAUNCH(true, 0);

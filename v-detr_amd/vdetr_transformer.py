@@ -150,8 +150,8 @@ class GlobalShareCrossAttention(nn.Module):
         self.angle_type = args.angle_type
         self.interp_method, max_value, num_points = self.rpe_quant.split("_")
         max_value, num_points = float(max_value), int(num_points)
-        if self.interp_method != "bilinear":
-            raise NotImplementedError(f"rpe_quant interpolation '{self.interp_method}' (only 'bilinear' is built)")
+        if self.interp_method not in A.RPEConfig.INTERP:
+            raise NotImplementedError(f"rpe_quant interpolation '{self.interp_method}' ('bilinear' and 'nearest' are built)")
         lin = torch.linspace(-max_value, max_value, num_points, dtype=torch.float32)
         table = torch.stack(torch.meshgrid(lin, lin, lin, indexing="ij"), dim=-1).unsqueeze(0)
         self.register_buffer("relative_coords_table", table)  # [1,T,T,T,3]
@@ -163,7 +163,7 @@ class GlobalShareCrossAttention(nn.Module):
         self.attn_drop = nn.Dropout(attn_drop)  # p is read by the fused kernel
         self.proj = nn.Linear(dim, dim)
         self.proj_drop = nn.Dropout(proj_drop)
-        self.rpe_cfg = A.RPEConfig(num_points, self.log_scale, max_value)
+        self.rpe_cfg = A.RPEConfig(num_points, self.log_scale, max_value, self.interp_method)
         self.return_attn = False
         # set by a caller whose reference points are box corners out of its own box decode (TransformerDecoder): the table gradient
         # then launches the box kernel alone (attention.fused_attention: vertices_are_boxes)
