@@ -1085,6 +1085,62 @@ int vdetr_vertex_normals_f32(const vdetr_normals_desc* desc, const int32_t* vert
                              void* workspace, size_t workspace_bytes, vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * A raw ScanNet scan -> the arrays of its _vert / _sem_label / _ins_label / _bbox files (reference
+ * scannet/load_scannet_data.py:60-129 export and scannet/batch_load_scannet_data.py:25-50 export_one_scan).  The host has
+ * walked the aggregation into per-segment tables (v-detr_amd/scan_export.py:scan_tables); per vertex the device then does
+ *   aligned[r] = float32(((x * m[r][0] + y * m[r][1]) + z * m[r][2]) + m[r][3])   in float64, every operation separate
+ *   semantic = seg_label[seg], instance = seg_object[seg]                         pure gathers
+ * and per object k (1-based id k + 1) the min / max of the aligned float32 coordinates of its vertices,
+ *   centre = (min + max) / 2, size = max - min in float32, label = object_label[k]; an object without vertices is a row of zeros.
+ * Rows whose label has class_table[label] >= 0 go to `boxes` in ascending object id, zero rows after them.
+ * Two launches: one workgroup per scene-aligned tile of VDETR_EXPORT_TILE rows keeps a [K, 6] table of order-preserving
+ * integer keys in LDS (LDS integer min / max) and stores it as the tile's partial; one workgroup per scene merges the
+ * partials, forms, filters and compacts the boxes.  No float atomics: two runs give the same bits.  With a drop table
+ * (DONOTCARE_CLASS_IDS) a third launch moves the kept rows and labels up in their order and `kept_counts` holds the scenes'
+ * new row counts.  Inputs are finite.
+ * ---------------------------------------------------------------------------------------------- */
+#define VDETR_EXPORT_TILE 512           /* rows per workgroup, one lane per row */
+#define VDETR_EXPORT_MAX_INSTANCES 512  /* objects per scan: the [K, 6] table of 32-bit keys takes 12 KB of the workgroup's LDS */
+typedef struct vdetr_scan_export_desc {
+  int32_t B;                /* scenes (<= 4096) */
+  int32_t W;                /* floats per output row (>= 3): columns 0:3 aligned, the rest copied */
+  int32_t vert_stride;      /* floats per row of `vertices` (>= W) */
+  int32_t Kmax;             /* object slots per scene: rows of instance_bboxes and of boxes (0 .. VDETR_EXPORT_MAX_INSTANCES) */
+  int32_t num_segments;     /* entries of seg_label / seg_object over the whole batch */
+  int32_t class_table_len;  /* entries of class_table */
+  int32_t drop_table_len;   /* entries of drop_table; 0: nothing is dropped, two launches */
+  int32_t reserved;
+  const float* vertices;          /* [offsets[B], vert_stride] */
+  const int32_t* offsets;         /* [B+1] DEVICE copy of offsets_host */
+  const int32_t* seg_indices;     /* [offsets[B]] index into seg_label / seg_object (outside 0 .. num_segments - 1: unannotated) */
+  const int32_t* seg_label;       /* [num_segments] semantic label, 0 = unannotated */
+  const int32_t* seg_object;      /* [num_segments] 1-based object id within the scene, 0 = none */
+  const int32_t* num_instances;   /* [B] DEVICE copy of num_instances_host */
+  const int32_t* object_label;    /* [B, Kmax] */
+  const double* axis_align;       /* [B, 16] row-major 4 x 4 */
+  const int32_t* class_table;     /* [class_table_len] class index of a kept label, -1 otherwise */
+  const int32_t* drop_table;      /* [drop_table_len] nonzero: vertices with this semantic label are removed */
+  float* out_vertices;            /* [offsets[B], W] */
+  int32_t* semantic;              /* [offsets[B]] */
+  int32_t* instance;              /* [offsets[B]] */
+  float* instance_bboxes;         /* [B, Kmax, 7] centre, size, label: export's table before the class filter */
+  float* boxes;                   /* [B, Kmax, 6] */
+  int64_t* box_nyu40;             /* [B, Kmax] */
+  int64_t* box_classes;           /* [B, Kmax] */
+  int64_t* box_counts;            /* [B] */
+  float* kept_vertices;           /* drop table only: [offsets[B], W], the kept rows of all scenes packed */
+  int32_t* kept_semantic;         /* [offsets[B]] */
+  int32_t* kept_instance;         /* [offsets[B]] */
+  int32_t* kept_counts;           /* [B] kept rows per scene */
+} vdetr_scan_export_desc;
+/* offsets_host and num_instances_host are HOST arrays read at call time (num_instances_host[b] in 0 .. Kmax is checked before
+ * any launch).  With T tiles the workspace holds, each rounded up to 256 B: the partials [T, Kmax, 6] u32 and two [T] i32
+ * arrays (kept rows per tile, their exclusive scan within the scene), plus 256 B; it only lives for the call. */
+size_t vdetr_scan_export_workspace_bytes(const int32_t* offsets_host, int B, int Kmax);
+int vdetr_scan_export_f32(const vdetr_scan_export_desc* desc, const int32_t* offsets_host, const int32_t* num_instances_host,
+                          void* workspace, size_t workspace_bytes, vdetr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Greedy 3-D NMS of a scene's predictions (reference utils/nms.py:78-162 nms_3d_faster /
  * nms_3d_faster_samecls as called from utils/ap_calculator.py:165-220 on the min / max extents of the 8 box corners).
  * corners (B,K,8,3) f32, score (B,K) f32, cls (B,K) i32 or NULL (class-agnostic nms_3d_faster), valid (B,K) u8 or NULL

@@ -1,0 +1,167 @@
+"""GPU: the scan export on the device (v-detr_amd/scan_export.py ``export_scans`` -> csrc/scan_export.hip)
+against the fixture made by the reference's own ``export`` / ``export_one_scan`` (tests/golden/scan_export.npz) and against the
+numpy restatement for generated scans.
+
+The alignment is six float64 operations in a stated order and one rounding, the labels are gathers, min and max do not depend
+on the order of their operands, and centre and size are one float32 operation each: everything is compared with NO tolerance,
+``same_bits`` on floats and ``torch.equal`` on integers.  (Where +0 and -0 are both the extreme of an object's axis the box may
+carry either zero and ``==`` would decide; tests/test_scan_export_restatement.py asserts that no fixture case is one.)"""
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import cfg, dev, same_bits
+import scan_export_restatement as SR
+from test_scan_export_restatement import CASES, golden, inputs_of, make_scan
+
+pytestmark = pytest.mark.gpu
+FLOAT_KEYS = ("mesh_vertices", "instance_bboxes", "boxes")
+INT_KEYS = ("semantic_labels", "instance_labels", "box_nyu40", "box_classes", "box_counts")
+
+
+def tables_of(scan, identity=False):
+    from vdetr_amd.scan_export import scan_tables
+    return scan_tables(scan["seg_indices"], scan["groups"], scan["label_map"], None if identity else scan["axis_align"])
+
+
+def want_of(scans, donotcare=(), Kmax=None):
+    """the restatement's batch for generated scans"""
+    args = [(s["mesh"], s["seg_indices"], s["groups"], s["label_map"], s["axis_align"]) for s in scans]
+    return SR.batch_tensors([(SR.export(*a), SR.export_one_scan(*a, donotcare_ids=donotcare)) for a in args], cfg().nyu40id2class, Kmax)
+
+
+def export(scans, donotcare=(), vertices=None):
+    from vdetr_amd.scan_export import export_scans
+    vertices = dev(np.concatenate([s["mesh"] for s in scans])) if vertices is None else vertices
+    off = np.cumsum([0] + [len(s["mesh"]) for s in scans])
+    return export_scans(vertices, off, [tables_of(s) for s in scans], cfg(), donotcare_ids=donotcare)
+
+
+def assert_equal(got, want, what=""):
+    assert np.array_equal(got["offsets"], want["offsets"]), what
+    for k in FLOAT_KEYS:
+        assert same_bits(got[k], want[k]), (what, k)
+    for k in INT_KEYS:
+        assert got[k].dtype == (torch.int32 if k.endswith("labels") else torch.int64), k
+        assert torch.equal(got[k].cpu(), torch.from_numpy(want[k])), (what, k)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_fixture_cases_bit_for_bit(name):
+    from vdetr_amd.scan_export import export_scans
+    c = golden()[name]
+    mesh, seg, groups, label_map, matrix = inputs_of(c)
+    scan = {"mesh": mesh, "seg_indices": seg, "groups": groups, "label_map": label_map, "axis_align": matrix}
+    got = export_scans(dev(mesh), np.array([0, len(mesh)]), [tables_of(scan, identity=name == "identity")], cfg(),
+                       donotcare_ids=c["donotcare"].tolist())
+    full = (c["ex_vertices"], c["ex_labels"], c["ex_instances"], c["ex_bboxes"], None)
+    want = SR.batch_tensors([(full, tuple(c[k] for k in ("vert", "sem_label", "ins_label", "bbox")))], cfg().nyu40id2class)
+    assert_equal(got, want, name)
+    assert got["instance_bboxes"].shape == (1, len(c["ex_bboxes"]), 7) and int(got["box_counts"][0]) == len(c["bbox"])
+
+
+def test_one_object_and_the_most_objects():
+    from vdetr_amd import _lib
+    rng = np.random.default_rng(31)
+    K = _lib.VDETR_EXPORT_MAX_INSTANCES
+    for n, k in ((3, 1), (K + 300, K)):
+        s = make_scan(rng, n, k, seg_size=2)
+        got = export([s])
+        assert got["instance_bboxes"].shape == (1, k, 7)
+        assert_equal(got, want_of([s]), (n, k))
+
+
+def test_one_object_too_many_is_refused_before_any_launch():
+    from vdetr_amd import _lib
+    from vdetr_amd.scan_export import export_scans, scan_tables
+    K = _lib.VDETR_EXPORT_MAX_INSTANCES
+    s = make_scan(np.random.default_rng(32), K + 50, K + 1, seg_size=1)
+    with pytest.raises(ValueError, match="VDETR_EXPORT_MAX_INSTANCES"):
+        scan_tables(s["seg_indices"], s["groups"], s["label_map"], s["axis_align"])
+    t = tables_of(make_scan(np.random.default_rng(32), K + 50, K, seg_size=1))
+    t.num_instances, t.object_label = K + 1, np.zeros(K + 1, np.int32)
+    with pytest.raises(ValueError, match="VDETR_EXPORT_MAX_INSTANCES"):
+        export_scans(torch.zeros((K + 50, 6), device="cuda"), np.array([0, K + 50]), [t], cfg())
+
+
+@pytest.fixture(scope="module")
+def ragged():
+    """four scans: 5 tiles and a bit, one vertex, no groups at all, one tile and a bit with objects named by several groups"""
+    rng = np.random.default_rng(33)
+    scans = [make_scan(rng, 2700, 23), make_scan(rng, 1, 1), make_scan(rng, 333, 0, cover=0.0), make_scan(rng, 640, 7, cover=0.6)]
+    scans[3]["groups"][2]["segments"] = scans[3]["groups"][2]["segments"] + scans[3]["groups"][0]["segments"][:2]
+    return scans
+
+
+@pytest.mark.parametrize("donotcare", ((), (1, 2, 5, 7, 40)))
+def test_ragged_batch_equals_the_single_calls_and_the_restatement(ragged, donotcare):
+    got = export(ragged, donotcare)
+    Kmax = 23
+    assert_equal(got, want_of(ragged, donotcare, Kmax), "batch")
+    off = got["offsets"]
+    assert len(donotcare) == 0 or off[-1] < sum(len(s["mesh"]) for s in ragged)
+    for b, s in enumerate(ragged):
+        alone = export([s], donotcare)
+        k = alone["instance_bboxes"].shape[1]
+        for key in ("mesh_vertices", "semantic_labels", "instance_labels"):
+            assert torch.equal(got[key][off[b]:off[b + 1]], alone[key]), (b, key)
+        for key in ("instance_bboxes", "boxes", "box_nyu40", "box_classes"):
+            assert torch.equal(got[key][b, :k], alone[key][0]) and not got[key][b, k:].any(), (b, key)
+        assert got["box_counts"][b] == alone["box_counts"][0]
+    assert got["instance_bboxes"].shape == (4, Kmax, 7) and int(got["box_counts"][2]) == 0
+
+
+def test_two_runs_give_the_same_bits(ragged):
+    a, b = export(ragged, (1, 2)), export(ragged, (1, 2))
+    for k in FLOAT_KEYS:
+        assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), k
+    for k in INT_KEYS:
+        assert torch.equal(a[k], b[k]), k
+
+
+def test_strided_rows_are_accepted(ragged):
+    """seven-column ply rows (x y z r g b a): the first six columns as a view"""
+    s = ragged[3]
+    ply = dev(np.concatenate([s["mesh"], np.full((len(s["mesh"]), 1), 255, np.float32)], 1))
+    view = ply[:, :6]
+    assert not view.is_contiguous()
+    got = export([s], vertices=view)
+    assert_equal(got, want_of([s]))
+    wide = export([s], vertices=ply)                                    # the whole rows: column 6 is copied like the colours
+    assert same_bits(wide["mesh_vertices"][:, :6], want_of([s])["mesh_vertices"]) and same_bits(wide["mesh_vertices"][:, 6], ply[:, 6].cpu().numpy())
+
+
+def test_the_default_call_does_not_synchronise(ragged):
+    """with no DONOTCARE ids nothing is read back: torch's synchronisation check stays silent over the whole call"""
+    vertices = dev(np.concatenate([s["mesh"] for s in ragged]))
+    export(ragged, vertices=vertices)                                   # load the library, warm the allocator
+    torch.cuda.synchronize()
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)                    # "a prototype feature": it sees copies and synchronize calls
+        torch.cuda.set_sync_debug_mode("error")
+    try:
+        got = export(ragged, vertices=vertices)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert_equal(got, want_of(ragged, (), 23))
+
+
+def test_chain_into_prepare_scenes():
+    """export_scans -> prepare_scenes(identity) equals prepare_scenes fed with the reference-exported arrays from the host"""
+    from vdetr_amd import scene_prep as SP
+    from vdetr_amd.scan_export import export_scans
+    c = golden()["empty_object"]
+    mesh, seg, groups, label_map, matrix = inputs_of(c)
+    scan = {"mesh": mesh, "seg_indices": seg, "groups": groups, "label_map": label_map, "axis_align": matrix}
+    got = export_scans(dev(mesh), np.array([0, len(mesh)]), [tables_of(scan)], cfg())
+    mine = SP.prepare_scenes(got["mesh_vertices"], got["offsets"], got["boxes"], got["box_counts"], got["box_classes"], SP.AugmentParams.identity(1), cfg())
+    vert, bbox = c["vert"], c["bbox"]
+    boxes = dev(bbox[None, :, :6].astype(np.float32))
+    classes = dev(SP.nyu40_to_class(bbox[None, :, 6], cfg()))
+    ref = SP.prepare_scenes(dev(vert), np.array([0, len(vert)]), boxes, dev(np.array([len(bbox)])), classes, SP.AugmentParams.identity(1), cfg())
+    for key in SP.TARGET_KEYS + ("point_cloud_dims_min", "point_cloud_dims_max"):
+        assert torch.equal(mine[key], ref[key]), key
+    assert torch.equal(mine["point_clouds"][0], ref["point_clouds"][0])
+    assert float(ref["gt_box_present"].sum()) == len(bbox) >= 18

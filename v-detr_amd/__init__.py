@@ -12,6 +12,7 @@ __version__ = "0.1.0"
 _SCENE_PREP = ("AugmentParams", "draw_augment_params", "prepare_scenes", "nyu40_to_class", "crop_and_sample", "draw_cuboid_trials",
                "CuboidTrials", "ColorAugmentParams", "draw_color_augment", "augment_colors", "append_height", "percentile_plan",
                "SunrgbdColorParams", "draw_sunrgbd_color", "sunrgbd_color_augment")
+_SCAN_EXPORT = ("ScanTables", "scan_tables", "export_scans")
 _OPTIM = ("ClipAdamW", "build_optimizer", "compute_learning_rate", "lr_table")
 
 
@@ -21,6 +22,9 @@ def __getattr__(name):
     if name in _SCENE_PREP:
         from . import scene_prep
         return getattr(scene_prep, name)
+    if name in _SCAN_EXPORT:  # the step in front of it: a raw scan to the loader's arrays (scan_export.py)
+        from . import scan_export
+        return getattr(scan_export, name)
     if name in _OPTIM:  # the training loop's optimizer (optim.py), the same way
         from . import optim
         return getattr(optim, name)

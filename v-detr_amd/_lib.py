@@ -328,6 +328,20 @@ class NormalsDesc(ctypes.Structure):
         (n, c_void_p) for n in ("vertices", "faces", "vert_offsets", "face_offsets", "out")]
 
 
+VDETR_EXPORT_TILE, VDETR_EXPORT_MAX_INSTANCES = 512, 512
+
+
+class ScanExportDesc(ctypes.Structure):
+    """Mirror of ``vdetr_scan_export_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "W", "vert_stride", "Kmax", "num_segments", "class_table_len", "drop_table_len",
+                                              "reserved")] + [
+        (n, c_void_p) for n in ("vertices", "offsets", "seg_indices", "seg_label", "seg_object", "num_instances", "object_label",
+                                "axis_align", "class_table", "drop_table", "out_vertices", "semantic", "instance", "instance_bboxes",
+                                "boxes", "box_nyu40", "box_classes", "box_counts", "kept_vertices", "kept_semantic", "kept_instance",
+                                "kept_counts")]
+
+
 class SpBnDesc(ctypes.Structure):
     """Mirror of ``vdetr_spbn_desc``."""
 
@@ -444,6 +458,8 @@ _SIGNATURES = {
     "vdetr_sunrgbd_color_f32": (c_int, [ctypes.POINTER(ColorAugDesc), c_void_p, c_void_p]),
     "vdetr_vertex_normals_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int]),
     "vdetr_vertex_normals_f32": (c_int, [ctypes.POINTER(NormalsDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vdetr_scan_export_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "vdetr_scan_export_f32": (c_int, [ctypes.POINTER(ScanExportDesc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vdetr_sp_kernel_map_i32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vdetr_sp_inverse_map_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_sp_gather_cols_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

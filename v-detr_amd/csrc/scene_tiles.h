@@ -1,4 +1,4 @@
-// scene_tiles.h — what the loader chain's files share (scene_prep.hip, cuboid.hip, color_aug.hip, normals.hip; DESIGN.md
+// scene_tiles.h — what the loader chain's files share (scene_prep.hip, cuboid.hip, color_aug.hip, normals.hip, scan_export.hip; DESIGN.md
 // 6.4 "Scene-aligned tiles, partials and the workspace carver").  A packed batch is cut into tiles of `tile` rows that never
 // straddle scenes; a workgroup finds its scene by adding up the tile counts of the device offsets (B <= kMaxScenes).  A
 // per-scene min / max goes through ONE partial per tile, written with ordinary stores, which one wave per scene merges in a
