@@ -205,7 +205,8 @@ typedef struct vdetr_attn_desc {
                          rounds on the CUs left).  Same values either way up to the order of the row-tile sums. */
   const void* kv_img; /* vdetr_attn_fwd_f32 with fwd_kernel 0 / 3: the K / V operand images of this call, packed ahead by
                          vdetr_attn_pack_kv_f32 / vdetr_attn_pack_kv_parts_f32 with the matching part count (one launch for the K / V of all decoder layers); NULL: the call packs its own into
-                         `workspace` (one more launch) */
+                         `workspace` (one more launch).  vdetr_attn_fwd_bf16 reads no image of f32 parts and packs its own from its
+                         bf16 operands: it refuses a non-NULL kv_img (VDETR_ERR_ARG) */
   uint32_t* fwd_sched; /* persistent forward: ONE zero device word (the item counter), left zero by the call; a word must not be
                           shared by launches that may run concurrently.  NULL: the library clears a word at the head of
                           `workspace` with a memset node in front of the launch. */

@@ -232,3 +232,105 @@ def test_every_ctypes_mirror_has_the_headers_layout(tmp_path):
     assert len(got) == len(want)
     bad = [(what, int(g), w) for (what, w), g in zip(want, got) if int(g) != w]
     assert not bad, bad
+
+
+def _attn_desc(_lib, spare, kind=0, B=1, H=4, nQ=1024, nK=4096, T=10, **flags):
+    """a descriptor for the size functions and the host checks: they read fields only, so `spare` stands in for every pointer"""
+    d = _lib.AttnDesc()
+    d.kind, d.B, d.H, d.nQ, d.nK, d.scale = kind, B, H, nQ, nK, 0.125
+    if T:
+        d.table, d.table_size, d.vertices, d.xyz = spare, T, spare, spare
+    for name, value in flags.items():
+        setattr(d, name, spare if value is True else value)
+    return d
+
+
+def test_workspace_sizes_keep_their_byte_counts():
+    """What the *_workspace_bytes functions of nms.hip, fps.hip, attn_bwd.hip, attn_bwd_kv.hip and attn_fwd.hip answer.  Every
+    figure was recorded from the library as it was before these files came to write their layouts once, on a Carver
+    (csrc/workspace.h): callers have sized buffers by them, so they stay what they were, to the byte.  Without a device the
+    library counts 256 compute units."""
+    import numpy as np
+    from vdetr_amd import _lib
+    lib = _lib.lib()
+    spare = np.zeros(64, np.uint8).ctypes.data
+    per_head = _lib.VDETR_ATTN_PER_HEAD
+    small = dict(B=2, nQ=12, nK=272)                                     # key split 2, ragged last tile
+    fwd = {"T 10": (dict(), 6882048),                                    # counter, four key splits' partials, K/V image
+           "T 10, fwd_sched": (dict(fwd_sched=True), 6881792),
+           "T 10, kv_img": (dict(kv_img=True), 4260352),
+           "T 10, fwd_sched and kv_img": (dict(fwd_sched=True, kv_img=True), 4260096),
+           "T 10, fwd_kernel 1": (dict(fwd_kernel=1), 4260096),
+           "T 10, fwd_kernel 3": (dict(fwd_kernel=3), 6882048),
+           "T 6": (dict(T=6), 4260096),
+           "T 10, mask": (dict(mask=True, mask_kind=_lib.VDETR_MASK_BOOL), 4260096),
+           "small, T 10": (dict(small), 398848),
+           "small, T 10, kv_img": (dict(small, kv_img=True), 50432),
+           "small, T 10, fwd_kernel 2": (dict(small, fwd_kernel=2), 50432),
+           "small, no table": (dict(small, T=0), 50176),
+           "64 keys, T 10": (dict(nK=64), 41472),                        # no key split: counter and image
+           "64 keys, T 10, kv_img": (dict(nK=64, kv_img=True), 256),     # the counter alone
+           "per-head": (dict(kind=per_head, nQ=1024, nK=1024, T=0), 0)}
+    for name, (fields, want) in fwd.items():
+        assert lib.vdetr_attn_fwd_workspace_bytes(ctypes.byref(_attn_desc(_lib, spare, **fields))) == want, name
+    bwd = {"no table": (dict(T=0), 0), "T 10, 1024 queries": (dict(), 32768256), "T 10, 8 queries": (dict(nQ=8), 1024256),
+           "T 6": (dict(T=6), 7078144)}
+    for name, (fields, want) in bwd.items():
+        assert lib.vdetr_attn_bwd_workspace_bytes(ctypes.byref(_attn_desc(_lib, spare, **fields))) == want, name
+    bwd_kv = {"shared, H 4": (dict(T=0), 3145984), "per-head, B 2, H 4, nQ 100": (dict(kind=per_head, B=2, nQ=100, T=0), 786688),
+              "shared, H 8": (dict(H=8, T=0), 0)}
+    for name, (fields, want) in bwd_kv.items():
+        assert lib.vdetr_attn_bwd_kv_workspace_bytes(ctypes.byref(_attn_desc(_lib, spare, **fields))) == want, name
+    fps = {(1, 40000): 1682176, (2, 300): 189696, (1, 300000): 6000896, (0, 5): 0}
+    for (b, n), want in fps.items():
+        assert lib.vdetr_fps_workspace_bytes(b, n) == want, (b, n)
+    fps_varlen = {(300, 130): 184576, (40000,): 1682176, (20000,) * 4: 3533056}
+    for counts, want in fps_varlen.items():
+        arr = np.array(counts, np.int32)
+        assert lib.vdetr_fps_varlen_workspace_bytes(arr.ctypes.data, len(counts)) == want, counts
+    nms = {(1, 256): (15616, 34048), (2, 70): (6912, 16896), (4, 4096): (8847616, 10027264), (0, 5): (0, 0)}
+    for (B, K), (want, want_rot) in nms.items():
+        assert lib.vdetr_nms3d_workspace_bytes(B, K) == want, (B, K)
+        assert lib.vdetr_nms3d_rot_workspace_bytes(B, K) == want_rot, (B, K)
+
+
+def test_workspace_entry_points_keep_their_messages():
+    """A missing workspace (NULL, 0) is refused on the host, before any launch, with status 3 and exactly these texts: they were
+    recorded from the library as it was before nms.hip, fps.hip, attn_bwd.hip, attn_bwd_kv.hip and attn_fwd.hip came to share
+    require_workspace (csrc/workspace.h).  All eight entry points reach the check without a device.  Two more rows: the bf16
+    forward refuses a caller's K/V image (an image of f32 parts is not what it reads), and vdetr_attn_pack_kv_f32, now the
+    three-part form of vdetr_attn_pack_kv_parts_f32, still refuses short rows."""
+    import numpy as np
+    from vdetr_amd import _lib
+    lib = _lib.lib()
+    buf = np.zeros(4096, np.uint8)                                       # addresses for the pointer checks; nothing follows them
+    base = (buf.ctypes.data + 255) & ~255
+    p = [base + 256 * i for i in range(11)]
+
+    def desc(**fields):
+        return ctypes.byref(_attn_desc(_lib, p[0], B=2, nQ=12, nK=272, **fields))
+
+    counts = np.array([300, 130], np.int32)
+    scenes = ctypes.cast((ctypes.c_void_p * 2)(p[1], p[2]), ctypes.c_void_p)
+    nms_args = (p[0], p[1], p[2], p[3], p[4], 2, 70, 0.25, 0, p[5], None, 0, None)
+    no_workspace = [
+        (lambda: lib.vdetr_nms3d_f32(*nms_args), b"nms3d: workspace 0 B < required 6912 B"),
+        (lambda: lib.vdetr_nms3d_rot_f32(*nms_args), b"nms3d_rot: workspace 0 B < required 16896 B"),
+        (lambda: lib.vdetr_furthest_point_sampling_f32(p[0], 2, 300, 16, p[1], None, 0, None),
+         b"furthest_point_sampling: workspace 0 B < required 189696 B"),
+        (lambda: lib.vdetr_furthest_point_sampling_varlen_f32(scenes, counts.ctypes.data, 2, 16, p[3], None, 0, None),
+         b"furthest_point_sampling_varlen: workspace 0 B < required 184576 B"),
+        (lambda: lib.vdetr_attn_fwd_f32(desc(), p[1], p[2], p[3], p[4], p[5], None, None, 0, None),
+         b"attn_fwd: workspace 0 B < required 398848 B"),
+        (lambda: lib.vdetr_attn_fwd_bf16(desc(), p[1], p[2], p[3], p[4], p[5], None, None, 0, None),
+         b"attn_fwd_bf16: workspace 0 B < required 398848 B"),
+        (lambda: lib.vdetr_attn_bwd_kv_f32(desc(), *p[1:10], None, 0, None), b"attn_bwd_kv: workspace 0 B < required 98560 B"),
+        (lambda: lib.vdetr_attn_bwd_scores_f32(desc(), p[1], p[2], p[3], p[4], p[5], p[6], p[7], None, 0, None),
+         b"attn_bwd_scores: workspace 0 B < required 3072256 B")]
+    for call, text in no_workspace:
+        assert call() == 3, text
+        assert lib.vdetr_last_error() == text
+    assert lib.vdetr_attn_fwd_bf16(desc(kv_img=True), p[1], p[2], p[3], p[4], p[5], None, p[6], 1 << 20, None) == 1
+    assert lib.vdetr_last_error().startswith(b"attn_fwd_bf16:") and b"kv_img" in lib.vdetr_last_error()
+    assert lib.vdetr_attn_pack_kv_f32(p[1], p[2], 1, 4096, 62, 64, 1, 0, p[3], None) == 1
+    assert lib.vdetr_last_error() == b"attn_pack_kv: rows of >= 64 floats, strides multiples of 4, 16-B aligned"

@@ -14,6 +14,7 @@
 // ds_add_f32; the copies are written to a workspace and summed by a second, coalesced kernel —
 // no global atomics.
 #include "attn_common.h"
+#include "workspace.h"
 
 namespace vdetr {
 
@@ -532,12 +533,18 @@ static int bwd_table_grid(const vdetr_attn_desc* d, int* grid) {
   return VDETR_OK;
 }
 
+// one partial table per workgroup; sized for the default grid, one workgroup per CU (independent of d->table_grid, which only lowers it)
+static float* lay_out(Carver& c, const vdetr_attn_desc* d) {
+  const size_t table_floats = (size_t)kRpeVerts * d->table_size * d->table_size * d->table_size * 4;
+  const long wgs = (long)d->B * d->nQ, cus = device_cu_count();
+  return c.take_unpadded<float>((size_t)(wgs < cus ? wgs : cus) * table_floats);
+}
+
 extern "C" size_t vdetr_attn_bwd_workspace_bytes(const vdetr_attn_desc* d) {
   if (!d || !d->table) return 0;
-  const size_t table_floats = (size_t)kRpeVerts * d->table_size * d->table_size * d->table_size * 4;
-  const long wgs = (long)d->B * d->nQ;  // (sized for the default grid: independent of d->table_grid)
-  const long cus = device_cu_count();
-  return (size_t)(wgs < cus ? wgs : cus) * table_floats * sizeof(float) + 256;  // partial tables + alignment
+  Carver c(nullptr);
+  lay_out(c, d);
+  return c.bytes() + 256;
 }
 
 template <bool FIXED, int VERTS, int WPV, bool SPLIT16, bool VLOOP>
@@ -585,14 +592,9 @@ static int attn_bwd_scores_impl(const vdetr_attn_desc* d, const float* scores, c
   VDETR_REQUIRE(P.T * P.T * P.T <= kWave * 16, "attn_bwd_scores: table edge %d too large for the matrix-unit kernel", P.T);
   int grid = 0;
   if (int e = bwd_table_grid(d, &grid)) return e;
-  if (dtable) {
-    const size_t need = vdetr_attn_bwd_workspace_bytes(d);
-    if (!workspace || workspace_bytes < need) {
-      set_error("attn_bwd_scores: workspace %zu B < required %zu B", workspace_bytes, need);
-      return VDETR_ERR_WORKSPACE;
-    }
-    P.dtable_part = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  }
+  if (int e = require_workspace("attn_bwd_scores", workspace, workspace_bytes, vdetr_attn_bwd_workspace_bytes(d))) return e;
+  Carver carver(workspace);
+  P.dtable_part = lay_out(carver, d);
   // Two kernels over the same grid and partial-table layout; the DEVICE decides which of them works (bwd_aux words 4 / 5):
   //   attn_bwd_scores_rpe_mm_kernel: any eight vertices per query;
   //   attn_bwd_box4_kernel (dS given, table edge 10, dynamic distribution): every query's vertices are an axis-aligned box, or,
@@ -612,13 +614,10 @@ static int attn_bwd_scores_impl(const vdetr_attn_desc* d, const float* scores, c
       if (int e2 = launch_attn_bwd_box4(P, grid, st)) return e2;
   }
   if (int e = check_launch("attn_bwd_scores_rpe")) return e;
-  if (dtable) {
-    hipLaunchKernelGGL(attn_bwd_table_reduce_kernel,
-                       dim3((table_floats + 255) / 256, (grid / kBwdSplit + kRedSlice - 1) / kRedSlice), dim3(256), 0, st,
-                       P.dtable_part, grid, kBwdSplit, table_floats, dtable, box_only ? d->bwd_aux : (const unsigned*)nullptr);
-    return check_launch("attn_bwd_table_reduce");
-  }
-  return VDETR_OK;
+  hipLaunchKernelGGL(attn_bwd_table_reduce_kernel,  // (dtable is set: the element-wise form returned above)
+                     dim3((table_floats + 255) / 256, (grid / kBwdSplit + kRedSlice - 1) / kRedSlice), dim3(256), 0, st,
+                     P.dtable_part, grid, kBwdSplit, table_floats, dtable, box_only ? d->bwd_aux : (const unsigned*)nullptr);
+  return check_launch("attn_bwd_table_reduce");
 }
 
 extern "C" int vdetr_attn_bwd_scores_f32(const vdetr_attn_desc* d, const float* scores, const float* dprob,

@@ -16,6 +16,7 @@
 // Determinism: the 16 row slots of a key tile (2 workgroups x 8 waves) are reduced by a fixed tree in LDS, and the two
 // workgroups add their sums onto a zeroed output — two commutative float adds, the same bits in either order.
 #include "kv_pack.h"
+#include "workspace.h"
 
 #include <stdlib.h>
 
@@ -484,10 +485,17 @@ static bool kv_supported(const vdetr_attn_desc* d) {
 static size_t kv_rows(const vdetr_attn_desc* d) { return d->kind == VDETR_ATTN_PER_HEAD ? (size_t)d->nQ : (size_t)d->nQ * 4; }
 static size_t kv_problems(const vdetr_attn_desc* d) { return d->kind == VDETR_ATTN_PER_HEAD ? (size_t)d->B * d->H : (size_t)d->B; }
 
+// the packed operand images: kKvTileUnits 16-B units per 32-row tile of every score matrix
+static uint4* lay_out(Carver& c, const vdetr_attn_desc* d) {
+  const size_t nt = (kv_rows(d) + 31) / 32;
+  return c.take_unpadded<uint4>(kv_problems(d) * nt * kKvTileUnits);
+}
+
 extern "C" size_t vdetr_attn_bwd_kv_workspace_bytes(const vdetr_attn_desc* d) {
   if (!kv_supported(d) || d->B <= 0 || d->nQ <= 0 || d->H <= 0) return 0;
-  const size_t nt = (kv_rows(d) + 31) / 32;
-  return kv_problems(d) * nt * kKvTileUnits * sizeof(uint4) + 256;
+  Carver c(nullptr);
+  lay_out(c, d);
+  return c.bytes() + 256;
 }
 
 template <bool PERHEAD, int WAVES, int HALVES = 2>
@@ -517,15 +525,12 @@ static int kv_run(const vdetr_attn_desc* d, const float* q, const float* v, cons
   const size_t rows = kv_rows(d), nprob = kv_problems(d);
   VDETR_REQUIRE(rows * d->nK * 4 < ((size_t)1 << 31), "attn_bwd_kv: a score matrix (%zu x %d) must stay below 2 GB", rows, d->nK);
   VDETR_REQUIRE(nprob <= 65535, "attn_bwd_kv: %zu score matrices > 65535", nprob);
-  const size_t need = vdetr_attn_bwd_kv_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need) {
-    set_error("attn_bwd_kv: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
+  if (int e = require_workspace("attn_bwd_kv", workspace, workspace_bytes, vdetr_attn_bwd_kv_workspace_bytes(d))) return e;
   K.A.q = q; K.A.v = v;
   K.A.scores = const_cast<float*>(scores); K.A.lse = const_cast<float*>(lse); K.A.delta = delta; K.A.ds_out = ds_out;
   K.dout = dout; K.dk = dk; K.dv = dv;
-  K.pack = reinterpret_cast<uint4*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  Carver carver(workspace);
+  K.pack = lay_out(carver, d);
   K.R = (int)rows;
   K.NT = (K.R + 31) / 32;
   const long units = (long)nprob * K.NT * 12 * kWave;

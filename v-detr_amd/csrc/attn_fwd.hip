@@ -19,6 +19,8 @@
 // Contraction index order inside a tile is permuted (d = 16*(lane>>4)+s for QK^T, key = 4*(lane>>4)+s and
 // d = 4*(lane&15)+t for PV) so that every operand fetch is a contiguous float4 per lane.
 #include "attn_common.h"
+#include "workspace.h"
+#include <algorithm>
 
 namespace vdetr {
 
@@ -572,28 +574,40 @@ static int choose_ksplit(const vdetr_attn_desc* d) {
 }
 }  // namespace vdetr
 
+// The forward's workspace: the persistent kernel's item counter where the caller brings none (fwd_sched), the K/V operand
+// image where the caller brings none (kv_img), and the key splits' partial outputs.  Sized for the image of three f32 parts;
+// the bf16 entry's one-part image is smaller and takes the same region.
+struct FwdLayout {
+  unsigned* sched;
+  char* kv_img;
+  float *part_o, *part_lse;
+  bool empty;  // nothing to carve: the forward then takes workspace == NULL
+};
+static FwdLayout lay_out(Carver& c, const vdetr_attn_desc* d) {
+  const int ks = choose_ksplit(d);
+  const bool own_sched = pipe_eligible(d) && !d->fwd_sched, own_img = pipe_split(d) && !d->kv_img;
+  const size_t rows = (size_t)d->B * d->nQ * d->H;
+  FwdLayout L{};
+  L.empty = !own_sched && !own_img && ks == 1;
+  if (own_sched) L.sched = reinterpret_cast<unsigned*>(c.take_head16<uint4>(own_img || ks > 1));
+  if (own_img) L.kv_img = c.take<char>(attn_fwd_pipe_img_bytes(d->B, d->nK, 3));  // whole 10 KB tiles: a multiple of 256 as it is
+  if (own_img && ks > 1) c.take<char>(256);  // nothing lives here: the size has always counted a second rounding, and callers hold its figures
+  if (ks > 1) {
+    L.part_o = c.take_unpadded<float>((size_t)ks * rows * kDh);
+    L.part_lse = c.take_unpadded<float>((size_t)ks * rows);
+  }
+  return L;
+}
+
 extern "C" size_t vdetr_attn_fwd_workspace_bytes(const vdetr_attn_desc* d) {
   if (!d) return 0;
-  const int ks = choose_ksplit(d);
-  const size_t sched = pipe_eligible(d) && !d->fwd_sched ? 256 : 0;  // the item counter, where the caller brings none
-  const size_t img = pipe_split(d) && !d->kv_img ? attn_fwd_pipe_img_bytes(d->B, d->nK, 3) + 256 : 0;  // (the bf16 forward's image is smaller: same bound)
-  if (ks == 1) return sched + img;
-  const size_t rows = (size_t)d->B * d->nQ * d->H;
-  return (size_t)ks * rows * (kDh + 1) * sizeof(float) + 256 + sched + img;
+  Carver c(nullptr);
+  return lay_out(c, d).empty ? 0 : c.bytes() + 256;
 }
 
 extern "C" size_t vdetr_attn_kv_image_bytes(int B, int nK) { return B > 0 && nK > 0 ? attn_fwd_pipe_img_bytes(B, nK, 3) : 0; }
 extern "C" size_t vdetr_attn_kv_image_parts_bytes(int B, int nK, int parts) {
   return B > 0 && nK > 0 && (parts == 1 || parts == 3) ? attn_fwd_pipe_img_bytes(B, nK, parts) : 0;
-}
-
-extern "C" int vdetr_attn_pack_kv_f32(const float* k, const float* v, int B, int nK, int k_row_stride, int v_row_stride, int nlayers,
-                                      int64_t layer_stride, void* img, vdetr_stream_t stream) {
-  VDETR_REQUIRE(k && v && img, "attn_pack_kv: null pointer");
-  VDETR_REQUIRE(B > 0 && nK > 0 && nlayers > 0 && nlayers <= 65535 && B <= 65535, "attn_pack_kv: B=%d nK=%d nlayers=%d", B, nK, nlayers);
-  VDETR_REQUIRE(k_row_stride >= kDh && v_row_stride >= kDh && k_row_stride % 4 == 0 && v_row_stride % 4 == 0 && layer_stride % 4 == 0 &&
-                (((uintptr_t)k | (uintptr_t)v | (uintptr_t)img) & 15) == 0, "attn_pack_kv: rows of >= 64 floats, strides multiples of 4, 16-B aligned");
-  return attn_fwd_pack_launch(k, v, B, nK, k_row_stride, v_row_stride, nlayers, (long)layer_stride, (char*)img, 3, true, (hipStream_t)stream);
 }
 
 extern "C" int vdetr_attn_pack_kv_parts_f32(const float* k, const float* v, int B, int nK, int k_row_stride, int v_row_stride, int nlayers,
@@ -606,58 +620,15 @@ extern "C" int vdetr_attn_pack_kv_parts_f32(const float* k, const float* v, int 
   return attn_fwd_pack_launch(k, v, B, nK, k_row_stride, v_row_stride, nlayers, (long)layer_stride, (char*)img, parts, true, (hipStream_t)stream);
 }
 
-// parts != nullptr: the key-split merge is left to the consumer (vdetr_attn_fwd_parts_f32)
-static int attn_fwd_run(const vdetr_attn_desc* d, const float* q, const float* k, const float* v, float* out, float* lse, float* scores,
-                        void* workspace, size_t workspace_bytes, vdetr_attn_parts* parts, vdetr_stream_t stream) {
-  AttnParams P;
-  if (int e = attn_fill_params(d, &P, "attn_fwd")) return e;
-  VDETR_REQUIRE(q && k && v && out && lse, "attn_fwd: null pointer");
-  P.q = q; P.k = k; P.v = v; P.out = out; P.lse = lse; P.scores = scores;
-  const bool perhead = d->kind == VDETR_ATTN_PER_HEAD;
-  const bool rpe = d->table != nullptr;
-  const int ks = choose_ksplit(d);
-  const bool pipe = pipe_eligible(d);
-  const size_t need = vdetr_attn_fwd_workspace_bytes(d);
-  if (need && (!workspace || workspace_bytes < need)) {
-    set_error("attn_fwd: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
-  unsigned* sched = d->fwd_sched;
-  size_t sched_bytes = 0;
-  if (pipe && !sched) {  // head of the workspace, cleared in front of the launch (a memset node in a captured graph)
-    sched = (unsigned*)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
-    sched_bytes = 256;
-    if (hipMemsetAsync(sched, 0, 16, (hipStream_t)stream) != hipSuccess) {
-      set_error("attn_fwd: cannot clear the item counter");
-      return VDETR_ERR_LAUNCH;
-    }
-  }
-  uintptr_t ws_top = (uintptr_t)workspace + sched_bytes;
-  if (ks > 1) {
-    const size_t rows = (size_t)d->B * d->nQ * d->H;
-    uintptr_t base = (ws_top + 255) & ~(uintptr_t)255;
-    P.part_o = (float*)base;
-    P.part_lse = P.part_o + (size_t)ks * rows * kDh;
-    P.ksplit = ks;
-    const int ntiles = (d->nK + 15) / 16;
-    P.tiles_per_split = (ntiles + ks - 1) / ks;
-    ws_top = base + (size_t)ks * rows * (kDh + 1) * sizeof(float);
-  }
-  char* kv_img = pipe_split(d) ? (d->kv_img ? (char*)d->kv_img : (char*)((ws_top + 255) & ~(uintptr_t)255)) : nullptr;
-  VDETR_REQUIRE(!d->kv_img || (((uintptr_t)d->kv_img) & 15) == 0, "attn_fwd: kv_img must be 16-B aligned");
-  const size_t lds_table = rpe ? (size_t)kRpeVerts * P.T * P.T * P.T * 16 : 0;
-  const size_t lds_bilinear = lds_table + (size_t)kFwdWaves * 16 * kPPad * 4 > (size_t)kFwdWaves * kWave * 24 * 4
-                                  ? lds_table + (size_t)kFwdWaves * 16 * kPPad * 4
-                                  : (size_t)kFwdWaves * kWave * 24 * 4;
-  const size_t lds = lds_bilinear + (P.rpe_nearest ? 16 : 0);  // nearest: the zero cell behind the pads
-  hipStream_t st = (hipStream_t)stream;
-  if (pipe) {
-    VDETR_REQUIRE((size_t)d->nK * P.k_stride < (1u << 30) && (size_t)d->nK * P.v_stride < (1u << 30) && (size_t)4 * d->nK < (1u << 30),
-                  "attn_fwd: nK=%d too large for the persistent forward's 32-bit tile offsets", d->nK);
-    if (int e = attn_fwd_pipe_launch(P, sched, device_cu_count(), kv_img, pipe_split(d), d->kv_img != nullptr, true, st)) return e;
-  } else if (perhead && attn_fwd_self_eligible(d, ks)) {
-    if (int e = attn_fwd_self_launch(P, st)) return e;  // the lean kernel of the decoder's own case (attn_fwd_self.hip)
-  } else if (perhead) {
+extern "C" int vdetr_attn_pack_kv_f32(const float* k, const float* v, int B, int nK, int k_row_stride, int v_row_stride, int nlayers,
+                                      int64_t layer_stride, void* img, vdetr_stream_t stream) {
+  return vdetr_attn_pack_kv_parts_f32(k, v, B, nK, k_row_stride, v_row_stride, nlayers, layer_stride, 3, img, stream);
+}
+
+// The grid kernels of the f32 entry points (every case the persistent forward does not take)
+static int fwd_grid_f32(const vdetr_attn_desc* d, AttnParams& P, int ks, size_t lds, hipStream_t st) {
+  if (d->kind == VDETR_ATTN_PER_HEAD) {
+    if (attn_fwd_self_eligible(d, ks)) return attn_fwd_self_launch(P, st);  // the lean kernel of the decoder's own case (attn_fwd_self.hip)
     dim3 grid((d->nQ + 15) / 16, d->H * ks, d->B);
     const long wgs = (long)grid.x * grid.y * grid.z;
     // four-wave workgroups where the eight-wave ones would (almost) fill the chip or more (fwd_kernel 1: the eight-wave form, A/B)
@@ -669,25 +640,101 @@ static int attn_fwd_run(const vdetr_attn_desc* d, const float* q, const float* k
       if (int e = set_lds(attn_fwd_kernel<true, false>, lds, "attn_fwd")) return e;
       hipLaunchKernelGGL((attn_fwd_kernel<true, false>), grid, dim3(kFwdThreads), lds, st, P);
     }
-  } else {
-    dim3 grid((d->nQ + 3) / 4, ks, d->B);
-    if (rpe) {
-      // one launch, the box / general body chosen per workgroup on the device; rotated boxes take the box body too
-      // (docs/DESIGN_rounds1-4.md 4.3)
-      P.box_path = true;
-      if (P.rpe_nearest) {
-        if (int e = set_lds(attn_fwd_rpe_auto_kernel<false, true>, lds, "attn_fwd")) return e;
-        hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<false, true>), grid, dim3(kFwdThreads), lds, st, P);
-      } else {
-        if (int e = set_lds(attn_fwd_rpe_auto_kernel<false>, lds, "attn_fwd")) return e;
-        hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<false>), grid, dim3(kFwdThreads), lds, st, P);
-      }
-    } else {
-      if (int e = set_lds(attn_fwd_kernel<false, false>, lds, "attn_fwd")) return e;
-      hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, dim3(kFwdThreads), lds, st, P);
-    }
+    return VDETR_OK;
   }
-  if (int e = check_launch("attn_fwd")) return e;
+  dim3 grid((d->nQ + 3) / 4, ks, d->B);
+  if (!d->table) {
+    if (int e = set_lds(attn_fwd_kernel<false, false>, lds, "attn_fwd")) return e;
+    hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, dim3(kFwdThreads), lds, st, P);
+    return VDETR_OK;
+  }
+  // one launch, the box / general body chosen per workgroup on the device; rotated boxes take the box body too
+  // (docs/DESIGN_rounds1-4.md 4.3)
+  P.box_path = true;
+  if (P.rpe_nearest) {
+    if (int e = set_lds(attn_fwd_rpe_auto_kernel<false, true>, lds, "attn_fwd")) return e;
+    hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<false, true>), grid, dim3(kFwdThreads), lds, st, P);
+  } else {
+    if (int e = set_lds(attn_fwd_rpe_auto_kernel<false>, lds, "attn_fwd")) return e;
+    hipLaunchKernelGGL((attn_fwd_rpe_auto_kernel<false>), grid, dim3(kFwdThreads), lds, st, P);
+  }
+  return VDETR_OK;
+}
+
+// ... and of the bf16 entry point: with a table, the general and the box instantiation side by side over the same grid (the
+// merged kernel of the fp32 path spills 11 registers when built for bf16 operands)
+static int fwd_grid_bf16(const vdetr_attn_desc* d, AttnParams& P, int ks, size_t lds, hipStream_t st) {
+  dim3 grid((d->nQ + 3) / 4, ks, d->B);
+  P.box_path = d->table != nullptr;
+  if (d->table && P.rpe_nearest) {
+    if (int e = set_lds(attn_fwd_bf16_nearest_kernel<false>, lds, "attn_fwd_bf16")) return e;
+    hipLaunchKernelGGL(attn_fwd_bf16_nearest_kernel<false>, grid, dim3(kFwdThreads), lds, st, P);
+    if (int e = set_lds(attn_fwd_bf16_nearest_kernel<true>, lds, "attn_fwd_bf16")) return e;
+    hipLaunchKernelGGL(attn_fwd_bf16_nearest_kernel<true>, grid, dim3(kFwdThreads), lds, st, P);
+  } else if (d->table) {
+    if (int e = set_lds(attn_fwd_kernel<false, true, false, true>, lds, "attn_fwd_bf16")) return e;
+    hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true>), grid, dim3(kFwdThreads), lds, st, P);
+    if (int e = set_lds(attn_fwd_kernel<false, true, true, true>, lds, "attn_fwd_bf16")) return e;
+    hipLaunchKernelGGL((attn_fwd_kernel<false, true, true, true>), grid, dim3(kFwdThreads), lds, st, P);
+  } else {
+    if (int e = set_lds(attn_fwd_kernel<false, false, false, true>, lds, "attn_fwd_bf16")) return e;
+    hipLaunchKernelGGL((attn_fwd_kernel<false, false, false, true>), grid, dim3(kFwdThreads), lds, st, P);
+  }
+  return VDETR_OK;
+}
+
+// The host path of the three forward entry points.  bf16: q, k, v are bf16 (op "attn_fwd_bf16"), else f32 (op "attn_fwd").
+// parts != nullptr: the key-split merge is left to the consumer (vdetr_attn_fwd_parts_f32)
+static int attn_fwd_run(const char* op, bool bf16, const vdetr_attn_desc* d, const void* q, const void* k, const void* v, float* out,
+                        float* lse, float* scores, void* workspace, size_t workspace_bytes, vdetr_attn_parts* parts,
+                        vdetr_stream_t stream) {
+  AttnParams P;
+  if (int e = attn_fill_params(d, &P, op)) return e;
+  VDETR_REQUIRE(!bf16 || d->kind == VDETR_ATTN_SHARED_KV, "%s: built for the shared-KV kinds", op);
+  VDETR_REQUIRE(q && k && v && out && lse, "%s: null pointer", op);
+  if (bf16) {
+    VDETR_REQUIRE(P.k_stride % 8 == 0 && P.v_stride % 8 == 0, "%s: K / V row strides %d / %d must be multiples of 8", op, P.k_stride, P.v_stride);
+    VDETR_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0, "%s: operands must be 16-B aligned", op);
+    VDETR_REQUIRE(!d->kv_img, "%s: kv_img holds images of f32 parts, which this entry does not read: leave it NULL", op);
+  }
+  P.q = (const float*)q; P.k = (const float*)k; P.v = (const float*)v; P.out = out; P.lse = lse; P.scores = scores;
+  const int ks = choose_ksplit(d);
+  // the persistent forward (attn_fwd_pipe.hip); for bf16 operands only as fwd_kernel 0, re-laid into one-part images of its own
+  const bool pipe = bf16 ? pipe_split(d) == 3 : pipe_eligible(d);
+  const int split = bf16 ? 1 : pipe_split(d);
+  Carver carver(workspace);
+  const FwdLayout L = lay_out(carver, d);
+  if (!L.empty)
+    if (int e = require_workspace(op, workspace, workspace_bytes, vdetr_attn_fwd_workspace_bytes(d))) return e;
+  VDETR_REQUIRE(!d->kv_img || (((uintptr_t)d->kv_img) & 15) == 0, "%s: kv_img must be 16-B aligned", op);
+  if (pipe) {
+    VDETR_REQUIRE((bf16 || ((size_t)d->nK * P.k_stride < (1u << 30) && (size_t)d->nK * P.v_stride < (1u << 30))) && (size_t)4 * d->nK < (1u << 30),
+                  "%s: nK=%d too large for the persistent forward's 32-bit tile offsets", op, d->nK);
+  }
+  if (ks > 1) {
+    P.part_o = L.part_o; P.part_lse = L.part_lse;
+    P.ksplit = ks;
+    P.tiles_per_split = ((d->nK + 15) / 16 + ks - 1) / ks;
+  }
+  const size_t lds_table = d->table ? (size_t)kRpeVerts * P.T * P.T * P.T * 16 : 0;
+  const size_t lds_bilinear = std::max(lds_table + (size_t)kFwdWaves * 16 * kPPad * 4, (size_t)kFwdWaves * kWave * 24 * 4);
+  const size_t lds = lds_bilinear + (P.rpe_nearest ? 16 : 0);  // nearest: the zero cell behind the pads
+  hipStream_t st = (hipStream_t)stream;
+  if (pipe) {
+    unsigned* sched = d->fwd_sched;
+    if (!sched) {  // head of the workspace, cleared in front of the launch (a memset node in a captured graph)
+      sched = L.sched;
+      if (hipMemsetAsync(sched, 0, 16, st) != hipSuccess) {
+        set_error("%s: cannot clear the item counter", op);
+        return VDETR_ERR_LAUNCH;
+      }
+    }
+    char* kv_img = !split ? nullptr : d->kv_img ? (char*)d->kv_img : L.kv_img;
+    if (int e = attn_fwd_pipe_launch(P, sched, device_cu_count(), kv_img, split, d->kv_img != nullptr, !bf16, st)) return e;
+  } else {
+    if (int e = bf16 ? fwd_grid_bf16(d, P, ks, lds, st) : fwd_grid_f32(d, P, ks, lds, st)) return e;
+  }
+  if (int e = check_launch(op)) return e;
   if (parts) {
     parts->part_o = ks > 1 ? P.part_o : nullptr;
     parts->part_lse = ks > 1 ? P.part_lse : nullptr;
@@ -707,7 +754,7 @@ static int attn_fwd_run(const vdetr_attn_desc* d, const float* q, const float* k
 extern "C" int vdetr_attn_fwd_f32(const vdetr_attn_desc* d, const float* q, const float* k, const float* v,
                                   float* out, float* lse, float* scores, void* workspace, size_t workspace_bytes,
                                   vdetr_stream_t stream) {
-  return attn_fwd_run(d, q, k, v, out, lse, scores, workspace, workspace_bytes, nullptr, stream);
+  return attn_fwd_run("attn_fwd", false, d, q, k, v, out, lse, scores, workspace, workspace_bytes, nullptr, stream);
 }
 
 extern "C" int vdetr_attn_fwd_parts_f32(const vdetr_attn_desc* d, const float* q, const float* k, const float* v,
@@ -715,90 +762,13 @@ extern "C" int vdetr_attn_fwd_parts_f32(const vdetr_attn_desc* d, const float* q
                                         vdetr_attn_parts* parts, vdetr_stream_t stream) {
   VDETR_REQUIRE(d && parts, "attn_fwd_parts: null pointer");
   VDETR_REQUIRE(d->kind == VDETR_ATTN_SHARED_KV, "attn_fwd_parts: built for the shared-KV kinds (rows in (b, q, h) order)");
-  return attn_fwd_run(d, q, k, v, out, lse, scores, workspace, workspace_bytes, parts, stream);
+  return attn_fwd_run("attn_fwd", false, d, q, k, v, out, lse, scores, workspace, workspace_bytes, parts, stream);
 }
 
 // q, k, v bf16 (k_row_stride / v_row_stride in ELEMENTS, multiples of 8: 16-B aligned operand loads); out, lse, scores fp32
 extern "C" int vdetr_attn_fwd_bf16(const vdetr_attn_desc* d, const void* q, const void* k, const void* v, float* out, float* lse,
                                    float* scores, void* workspace, size_t workspace_bytes, vdetr_stream_t stream) {
-  AttnParams P;
-  if (int e = attn_fill_params(d, &P, "attn_fwd_bf16")) return e;
-  VDETR_REQUIRE(d->kind == VDETR_ATTN_SHARED_KV, "attn_fwd_bf16: built for the shared-KV kinds");
-  VDETR_REQUIRE(q && k && v && out && lse, "attn_fwd_bf16: null pointer");
-  VDETR_REQUIRE(P.k_stride % 8 == 0 && P.v_stride % 8 == 0, "attn_fwd_bf16: K / V row strides %d / %d must be multiples of 8", P.k_stride, P.v_stride);
-  VDETR_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0, "attn_fwd_bf16: operands must be 16-B aligned");
-  P.q = (const float*)q; P.k = (const float*)k; P.v = (const float*)v; P.out = out; P.lse = lse; P.scores = scores;
-  const bool rpe = d->table != nullptr;
-  const int ks = choose_ksplit(d);
-  const bool pipe = pipe_split(d) == 3;  // (fwd_kernel 0) the persistent forward, bf16 operands re-laid into its images (attn_fwd_pipe.hip, SPLIT = 1)
-  const size_t need = vdetr_attn_fwd_workspace_bytes(d);
-  if (need && (!workspace || workspace_bytes < need)) {
-    set_error("attn_fwd_bf16: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
-  unsigned* sched = d->fwd_sched;
-  size_t sched_bytes = 0;
-  if (pipe && !sched) {
-    sched = (unsigned*)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
-    sched_bytes = 256;
-    if (hipMemsetAsync(sched, 0, 16, (hipStream_t)stream) != hipSuccess) {
-      set_error("attn_fwd_bf16: cannot clear the item counter");
-      return VDETR_ERR_LAUNCH;
-    }
-  }
-  uintptr_t ws_top = (uintptr_t)workspace + sched_bytes;
-  if (ks > 1) {
-    const size_t rows = (size_t)d->B * d->nQ * d->H;
-    uintptr_t base = (ws_top + 255) & ~(uintptr_t)255;
-    P.part_o = (float*)base;
-    P.part_lse = P.part_o + (size_t)ks * rows * kDh;
-    P.ksplit = ks;
-    P.tiles_per_split = ((d->nK + 15) / 16 + ks - 1) / ks;
-    ws_top = base + (size_t)ks * rows * (kDh + 1) * sizeof(float);
-  }
-  if (pipe) {
-    VDETR_REQUIRE((size_t)4 * d->nK < (1u << 30), "attn_fwd_bf16: nK=%d too large for the persistent forward's 32-bit tile offsets", d->nK);
-    char* kv_img = (char*)((ws_top + 255) & ~(uintptr_t)255);
-    if (int e = attn_fwd_pipe_launch(P, sched, device_cu_count(), kv_img, 1, false, false, (hipStream_t)stream)) return e;
-    if (ks > 1) {
-      const size_t elems = (size_t)d->B * d->nQ * d->H * kDh;
-      hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P);
-      return check_launch("attn_fwd_combine");
-    }
-    return VDETR_OK;
-  }
-  const size_t lds_table = rpe ? (size_t)kRpeVerts * P.T * P.T * P.T * 16 : 0;
-  const size_t lds_bilinear = lds_table + (size_t)kFwdWaves * 16 * kPPad * 4 > (size_t)kFwdWaves * kWave * 24 * 4
-                                  ? lds_table + (size_t)kFwdWaves * 16 * kPPad * 4
-                                  : (size_t)kFwdWaves * kWave * 24 * 4;
-  const size_t lds = lds_bilinear + (P.rpe_nearest ? 16 : 0);  // nearest: the zero cell behind the pads
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid((d->nQ + 3) / 4, ks, d->B);
-  if (rpe && P.rpe_nearest) {
-    P.box_path = true;
-    if (int e = set_lds(attn_fwd_bf16_nearest_kernel<false>, lds, "attn_fwd_bf16")) return e;
-    hipLaunchKernelGGL(attn_fwd_bf16_nearest_kernel<false>, grid, dim3(kFwdThreads), lds, st, P);
-    if (int e = set_lds(attn_fwd_bf16_nearest_kernel<true>, lds, "attn_fwd_bf16")) return e;
-    hipLaunchKernelGGL(attn_fwd_bf16_nearest_kernel<true>, grid, dim3(kFwdThreads), lds, st, P);
-  } else if (rpe) {
-    // the general and the box instantiation side by side over the same grid (the merged kernel of the fp32 path spills 11
-    // registers when built for bf16 operands)
-    P.box_path = true;
-    if (int e = set_lds(attn_fwd_kernel<false, true, false, true>, lds, "attn_fwd_bf16")) return e;
-    hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true>), grid, dim3(kFwdThreads), lds, st, P);
-    if (int e = set_lds(attn_fwd_kernel<false, true, true, true>, lds, "attn_fwd_bf16")) return e;
-    hipLaunchKernelGGL((attn_fwd_kernel<false, true, true, true>), grid, dim3(kFwdThreads), lds, st, P);
-  } else {
-    if (int e = set_lds(attn_fwd_kernel<false, false, false, true>, lds, "attn_fwd_bf16")) return e;
-    hipLaunchKernelGGL((attn_fwd_kernel<false, false, false, true>), grid, dim3(kFwdThreads), lds, st, P);
-  }
-  if (int e = check_launch("attn_fwd_bf16")) return e;
-  if (ks > 1) {
-    const size_t elems = (size_t)d->B * d->nQ * d->H * kDh;
-    hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, P);
-    return check_launch("attn_fwd_combine");
-  }
-  return VDETR_OK;
+  return attn_fwd_run("attn_fwd_bf16", true, d, q, k, v, out, lse, scores, workspace, workspace_bytes, nullptr, stream);
 }
 
 extern "C" int vdetr_rpe_bias_f32(const vdetr_attn_desc* d, float* rpe, vdetr_stream_t stream) {

@@ -26,6 +26,7 @@
 // Work drops from n*(m-1) distance evaluations to roughly 4 n ln m; the per-round cost is a few L2
 // round trips instead of a 640 KB sweep.
 #include "fps.h"
+#include "workspace.h"
 
 #include <stdlib.h>
 
@@ -375,10 +376,29 @@ static size_t ws_points(int n) {
   return rows > (size_t)npad ? rows : (size_t)npad;
 }
 
-extern "C" size_t vdetr_fps_workspace_bytes(int b, int n) {
-  if (b <= 0) return 0;
-  return (size_t)b * ws_points(n) * (sizeof(float4) + sizeof(uint32_t)) + 256;
+// the launch's points in the order their kernel sorts them, then their keys.  `points` counts the padded scenes: ws_points
+// each when measuring, the padding of the kernel that takes the launch (never more) when carving
+struct FpsLayout {
+  float4* pts;
+  uint32_t* keys;
+};
+static FpsLayout lay_out(Carver& c, size_t points) {
+  FpsLayout L;
+  L.pts = c.take_unpadded<float4>(points);
+  L.keys = c.take_unpadded<uint32_t>(points);
+  return L;
 }
+static FpsLayout lay_out(void* workspace, size_t points) {
+  Carver c(workspace);
+  return lay_out(c, points);
+}
+static size_t fps_bytes(size_t points) {
+  Carver c(nullptr);
+  lay_out(c, points);
+  return c.bytes() + 256;
+}
+
+extern "C" size_t vdetr_fps_workspace_bytes(int b, int n) { return b <= 0 ? 0 : fps_bytes((size_t)b * ws_points(n)); }
 
 extern "C" int vdetr_furthest_point_sampling_f32(const float* xyz, int b, int n, int m, int32_t* idx,
                                                  void* workspace, size_t workspace_bytes,
@@ -388,19 +408,13 @@ extern "C" int vdetr_furthest_point_sampling_f32(const float* xyz, int b, int n,
   VDETR_REQUIRE(n > 0, "furthest_point_sampling: empty cloud with nsamples=%d", m);
   VDETR_REQUIRE(xyz && idx, "furthest_point_sampling: null pointer");
   VDETR_REQUIRE((long)n < (1L << 30), "furthest_point_sampling: n=%d too large", n);
-  const size_t need = vdetr_fps_workspace_bytes(b, n);
-  if (!workspace || workspace_bytes < need) {
-    set_error("furthest_point_sampling: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
-  uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+  if (int e = require_workspace("furthest_point_sampling", workspace, workspace_bytes, vdetr_fps_workspace_bytes(b, n))) return e;
   RowsPlan plan;
   if (b <= kFpsMaxScenes && fps_rows_plan(n, &plan)) {  // the row-per-bucket kernel (fps_rows.hip)
     RowsParams R{};
     const long npad = fps_rows_npad(n, plan);
-    R.pts = (float4*)base;
-    R.keys = (uint32_t*)(base + (size_t)b * npad * sizeof(float4));
-    R.m = m;
+    const FpsLayout L = lay_out(workspace, (size_t)b * npad);
+    R.pts = L.pts; R.keys = L.keys; R.m = m;
     for (int i = 0; i < b; ++i) {
       RowsScene& S = R.scenes[i];
       S.xyz = xyz + (size_t)i * n * 3;
@@ -414,8 +428,8 @@ extern "C" int vdetr_furthest_point_sampling_f32(const float* xyz, int b, int n,
   }
   FpsParams P;
   fps_geometry(n, &P.npad, &P.bucket_pts, &P.nbuckets);
-  P.pts = (float4*)base;
-  P.keys = (uint32_t*)(base + (size_t)b * P.npad * sizeof(float4));
+  const FpsLayout L = lay_out(workspace, (size_t)b * P.npad);
+  P.pts = L.pts; P.keys = L.keys;
   P.xyz = xyz; P.idx = idx; P.n = n; P.m = m;
   P.nscenes = 0;
   P.ref_log2 = ref_log2_of(n); P.ref_block = 1 << P.ref_log2;
@@ -428,7 +442,7 @@ extern "C" size_t vdetr_fps_varlen_workspace_bytes(const int32_t* counts, int b)
   for (int i = 0; i < b; ++i) {
     total += ws_points(counts[i]);
   }
-  return b > 0 ? total * (sizeof(float4) + sizeof(uint32_t)) + 256 : 0;
+  return b > 0 ? fps_bytes(total) : 0;
 }
 
 extern "C" int vdetr_furthest_point_sampling_varlen_f32(const float* const* xyz, const int32_t* counts, int b, int m,
@@ -437,11 +451,7 @@ extern "C" int vdetr_furthest_point_sampling_varlen_f32(const float* const* xyz,
   if (b == 0 || m <= 0) return VDETR_OK;
   VDETR_REQUIRE(b > 0 && b <= kFpsMaxScenes, "furthest_point_sampling_varlen: 1..%d scenes per launch, got %d", kFpsMaxScenes, b);
   VDETR_REQUIRE(xyz && counts && idx, "furthest_point_sampling_varlen: null pointer");
-  const size_t need = vdetr_fps_varlen_workspace_bytes(counts, b);
-  if (!workspace || workspace_bytes < need) {
-    set_error("furthest_point_sampling_varlen: workspace %zu B < required %zu B", workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
+  if (int e = require_workspace("furthest_point_sampling_varlen", workspace, workspace_bytes, vdetr_fps_varlen_workspace_bytes(counts, b))) return e;
   int nmax = 0;
   for (int i = 0; i < b; ++i) {
     VDETR_REQUIRE(counts[i] > 0 && (long)counts[i] < (1L << 30), "furthest_point_sampling_varlen: scene %d has %d points", i, counts[i]);
@@ -462,10 +472,8 @@ extern "C" int vdetr_furthest_point_sampling_varlen_f32(const float* const* xyz,
       S.ref_block = 1 << S.ref_log2;
       total += fps_rows_npad(S.n, plan);
     }
-    uintptr_t rbase = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    R.pts = (float4*)rbase;
-    R.keys = (uint32_t*)(rbase + (size_t)total * sizeof(float4));
-    R.m = m;
+    const FpsLayout L = lay_out(workspace, (size_t)total);
+    R.pts = L.pts; R.keys = L.keys; R.m = m;
     return fps_rows_launch(R, b, plan, (hipStream_t)stream);
   }
   FpsParams P{};
@@ -480,9 +488,8 @@ extern "C" int vdetr_furthest_point_sampling_varlen_f32(const float* const* xyz,
     S.ref_log2 = ref_log2_of(S.n);
     S.ref_block = 1 << S.ref_log2;
   }
-  uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-  P.pts = (float4*)base;
-  P.keys = (uint32_t*)(base + (size_t)total * sizeof(float4));
+  const FpsLayout L = lay_out(workspace, (size_t)total);
+  P.pts = L.pts; P.keys = L.keys;
   P.idx = idx; P.m = m; P.nscenes = b;
   hipLaunchKernelGGL(fps_kernel<false>, dim3(b), dim3(kFpsThreads), 0, (hipStream_t)stream, P);
   return check_launch("furthest_point_sampling_varlen");

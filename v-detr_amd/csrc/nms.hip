@@ -13,6 +13,7 @@
 // The rotated form (vdetr_nms3d_rot_f32) replaces steps 1 and 2: the corners themselves in rank order, and
 // the relation from the reference's box3d_iou of the two boxes (nms3d_rot_relation_kernel, next to the clip routine below).
 #include "wave.h"
+#include "workspace.h"
 
 namespace vdetr {
 namespace {
@@ -428,19 +429,25 @@ __global__ __launch_bounds__(64) void nms3d_rot_relation_kernel(NmsParams P) {
 
 using namespace vdetr;
 
-static size_t nms_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-extern "C" size_t vdetr_nms3d_workspace_bytes(int B, int K) {
+// the workspace, as the fields of the kernels' parameters that point into it: the relation bit matrix, the prepared boxes
+// (extents, or the rotated form's corners) and their classes
+static NmsParams lay_out(Carver& c, bool rotated, int B, int K) {
+  const size_t rows = (size_t)B * K, W = (K + 63) / 64;
+  NmsParams P{};
+  P.rel = c.take<unsigned long long>(rows * W);
+  (rotated ? P.rcorn : P.ext) = c.take<float>(rows * (rotated ? 24 : 6));
+  P.rcls = c.take<int>(rows);
+  return P;
+}
+static size_t nms3d_bytes(bool rotated, int B, int K) {
   if (B <= 0 || K <= 0) return 0;
-  const size_t W = (K + 63) / 64;
-  return nms_align((size_t)B * K * W * 8) + nms_align((size_t)B * K * 6 * 4) + nms_align((size_t)B * K * 4) + 256;
+  Carver c(nullptr);
+  lay_out(c, rotated, B, K);
+  return c.bytes() + 256;
 }
 
-extern "C" size_t vdetr_nms3d_rot_workspace_bytes(int B, int K) {
-  if (B <= 0 || K <= 0) return 0;
-  const size_t W = (K + 63) / 64;
-  return nms_align((size_t)B * K * W * 8) + nms_align((size_t)B * K * 24 * 4) + nms_align((size_t)B * K * 4) + 256;
-}
+extern "C" size_t vdetr_nms3d_workspace_bytes(int B, int K) { return nms3d_bytes(false, B, K); }
+extern "C" size_t vdetr_nms3d_rot_workspace_bytes(int B, int K) { return nms3d_bytes(true, B, K); }
 
 static int nms3d_launch(bool rotated, const float* corners, const float* score, const int32_t* cls, const uint8_t* valid,
                         const int64_t* order, int B, int K, double iou_threshold, int old_type, uint8_t* keep, void* workspace,
@@ -450,21 +457,11 @@ static int nms3d_launch(bool rotated, const float* corners, const float* score, 
   if (B == 0 || K == 0) return VDETR_OK;
   VDETR_REQUIRE(corners && score && order && keep, "%s: null pointer", op);
   VDETR_REQUIRE(K <= 4096 && B <= 65535, "%s: %d scenes x %d boxes: limits are 65535 x 4096", op, B, K);
-  const size_t need = rotated ? vdetr_nms3d_rot_workspace_bytes(B, K) : vdetr_nms3d_workspace_bytes(B, K);
-  if (!workspace || workspace_bytes < need) {
-    set_error("%s: workspace %zu B < required %zu B", op, workspace_bytes, need);
-    return VDETR_ERR_WORKSPACE;
-  }
-  NmsParams P;
+  if (int e = require_workspace(op, workspace, workspace_bytes, nms3d_bytes(rotated, B, K))) return e;
+  Carver carver(workspace);
+  NmsParams P = lay_out(carver, rotated, B, K);
   P.corners = corners; P.cls = cls; P.valid = valid; P.order = order; P.keep = keep;
   P.K = K; P.W = (K + 63) / 64; P.old_type = old_type; P.thr = iou_threshold;
-  uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-  P.rel = reinterpret_cast<unsigned long long*>(base);
-  base += nms_align((size_t)B * K * P.W * 8);
-  P.ext = rotated ? nullptr : reinterpret_cast<float*>(base);
-  P.rcorn = rotated ? reinterpret_cast<float*>(base) : nullptr;
-  base += nms_align((size_t)B * K * (rotated ? 24 : 6) * 4);
-  P.rcls = reinterpret_cast<int*>(base);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(nms3d_prepare_kernel, dim3(ceil_div(K, 256), B), dim3(256), 0, st, P);
   if (int e = check_launch("nms3d_prepare")) return e;

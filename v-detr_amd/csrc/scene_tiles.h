@@ -3,9 +3,10 @@
 // straddle scenes; a workgroup finds its scene by adding up the tile counts of the device offsets (B <= kMaxScenes).  A
 // per-scene min / max goes through ONE partial per tile, written with ordinary stores, which one wave per scene merges in a
 // second launch: no atomics, no ticket, and float min / max give the same bits in any order.  The host half sizes the grid
-// from the host offsets and carves the caller's workspace.
+// from the host offsets; the workspace carver these files began with now serves the whole library from workspace.h.
 #pragma once
 #include "wave.h"
+#include "workspace.h"
 
 namespace vdetr {
 
@@ -57,8 +58,6 @@ __device__ __forceinline__ void store_tile_partial(const float (&v)[K], float (&
 // compiler simplifies the loop before it inlines it and each of the three kernels comes out with other instructions.
 
 // ---- host: the grid ----------------------------------------------------------------------------------------------------------
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // number of tiles, or -1 if the host offsets are unusable (with the error set if `op` is given)
 inline long count_tiles(const int32_t* offsets_host, int B, int tile, const char* op) {
   long tiles = 0;
@@ -71,37 +70,6 @@ inline long count_tiles(const int32_t* offsets_host, int B, int tile, const char
     tiles += (n + tile - 1) / tile;
   }
   return tiles;
-}
-
-// ---- host: the workspace -----------------------------------------------------------------------------------------------------
-// Hands out the regions of a workspace in order, each starting on a multiple of 256 B.  A file writes its layout once, as a
-// function of a Carver: on nullptr it measures (bytes(); the *_workspace_bytes functions add 256 for the start's own
-// rounding), on the caller's pointer it yields the regions, so the two cannot drift apart.
-class Carver {
- public:
-  explicit Carver(const void* workspace) : start_(align256((uintptr_t)workspace)), at_(start_) {}
-  template <typename T>
-  T* take(size_t count) {
-    T* p = take_unpadded<T>(count);
-    at_ = align256(at_);
-    return p;
-  }
-  template <typename T>
-  T* take_unpadded(size_t count) {                                      // for a last region whose size was never rounded up
-    T* p = reinterpret_cast<T*>(at_);
-    at_ += count * sizeof(T);
-    return p;
-  }
-  size_t bytes() const { return at_ - start_; }
-
- private:
-  uintptr_t start_, at_;
-};
-
-inline int require_workspace(const char* op, const void* workspace, size_t have, size_t need) {
-  if (workspace && have >= need) return VDETR_OK;
-  set_error("%s: workspace %zu B < required %zu B", op, have, need);
-  return VDETR_ERR_WORKSPACE;
 }
 
 }  // namespace vdetr
