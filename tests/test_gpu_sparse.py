@@ -1,5 +1,6 @@
 """Sparse-convolution backbone on the GPU (HIP index kernels through the C-ABI + library GEMMs) vs the CPU oracle."""
 import copy
+import functools
 
 import numpy as np
 import pytest
@@ -97,8 +98,141 @@ def test_sparse_conv_forward_backward(n, cin, cout, ks, monkeypatch):
     torch.testing.assert_close(S.gather_sum(dc.to(DEV), inv.to(DEV)).cpu(), O.gather_sum(dc, inv), rtol=1e-5, atol=1e-5)
 
 
+#               map: (input sites, output sites, pairs P, 128-pair tiles), counted on the CPU with the oracle
+_PAIR_GEOMETRIES = {"D-same": (2554, 2554, 38622, 316), "D-s2k3": (2554, 512, 7603, 74), "D-s2k1": (2554, 512, 312, 3),
+                    "D-up": (512, 2554, 2554, 24), "E": (40, 40, None, None), "1": (1, 1, 1, 1), "0": (1, 1, 0, 0)}
+
+
+@functools.lru_cache(maxsize=None)
+def _pair_geometry(name):
+    """(nbr [K, Nout], inv [K, Nin], Nin) of the maps the pair kernels are compared on, built by the oracle on the CPU.
+    D: 2554 sites in a 16^3 box (62 % filled), as a same-stride 3x3x3 map, the stride-2 3x3x3 and 1x1x1 maps onto its 512
+    coarse sites, and the 2x2x2 transposed map back (every fine site reads exactly one coarse site).  E: 40 sites in an 80^3
+    box (most of the 27 offsets have no pair at all).  1: a single site.  0: one input site that
+    the 1x1x1 stride-2 map does not read (no pair at all)."""
+    if name.startswith("D"):
+        fine = _cloud(4000, 1, batch=1, extent=8)
+        coarse = O.strided_coords(fine, 2)
+        src, dst, off = {"D-same": (fine, fine, O.region_offsets(3)), "D-s2k3": (fine, coarse, O.region_offsets(3)),
+                          "D-s2k1": (fine, coarse, O.region_offsets(1)), "D-up": (coarse, fine, -O.region_offsets(2))}[name]
+    elif name == "0":
+        src, off = np.array([[0, 1, 1, 1]]), O.region_offsets(1)
+        dst = O.strided_coords(src, 2)
+    else:
+        src = dst = _cloud(40, 3, batch=1, extent=40) if name == "E" else _cloud(1, 1, batch=1)
+        off = O.region_offsets(3)
+    ik, ok = torch.from_numpy(O.pack_keys_np(src)), torch.from_numpy(O.pack_keys_np(dst))
+    nbr = O.kernel_map(ik, ok, torch.from_numpy(off))
+    return nbr, O.inverse_map(nbr, ik.shape[0]), int(ik.shape[0])
+
+
+# The arms of vdetr_sp_pairs_gemm_f32 (forward; input gradient = the same dispatch with the contraction CA = cout and the
+# output width CB = cin, transposed) and vdetr_sp_pairs_wgrad_f32 that every case is there for.  `multi` names the directions
+# in which the persistent kernel must hand a workgroup a SECOND work item (ntiles * ceil(CB / 128) > 2 * CUs): only there does
+# it swap the weight descriptor and the operand offsets under the last K-step and store with the previous item's.
+#   gemm arms:  narrow<T>           sp_pairs_gemm_kernel<T, 4, 1, 2, 4>            CB <= 64
+#               split<T>            sp_pairs_gemm_persistent_kernel<T, 2, true>    CB > 64, CA % 64 == 0
+#               persistent<T, 1>    sp_pairs_gemm_persistent_kernel<T, 1>          CB > 64, CA % 64 == 32
+#               plain<T>            sp_pairs_gemm_kernel<T, 2, 2, 4, 4>            CB > 64, CA % 32 != 0
+#   wgrad arms: split 128 x 128     sp_pairs_wgrad_kernel<2, 2, 4, 4, 32, true>    cin >= 128 and cout >= 128
+#               exact 64 x 64       sp_pairs_wgrad_kernel<4, 1, 1, 4, 32>          otherwise
+_PAIR_CASES = [
+    # map, cin, cout, multi      forward                           input gradient                  weight gradient
+    ("D-same", 256, 256, "fd"),  # split<false>, NT 2, 632 items   split<true>, 632 items          split, 2 x 2 tiles
+    ("D-same", 512, 512, "fd"),  # split<false>, NT 4, 1264 items  split<true>, 1264 items         split, 4 x 4 tiles, reduce of 512 * 512 / 4
+    ("D-same", 96, 256, "f"),    # persistent<false, 1>, 632 items split<true>, CB 96, NT 1        exact, partial ci tile (96 = 64 + 32)
+    ("D-same", 256, 96, "d"),    # split<false>, CB 96, NT 1       persistent<true, 1>, 632 items  exact, partial co tile
+    ("D-same", 48, 160, ""),     # plain<false>, partial column tile  narrow<true>, CB 48          exact, 1 x 3 tiles
+    ("D-same", 160, 80, ""),     # persistent<false, 1>, CB 80     plain<true>, CA 80              exact, 3 x 2 tiles
+    ("D-same", 64, 256, "f"),    # (out_block) split<false>, NT 2, 632 items  narrow<true>         exact, 1 x 4 tiles
+    ("D-s2k3", 64, 128, ""),     # stage entry, nin != nout: split<false>  narrow<true>            exact
+    ("D-s2k3", 256, 512, ""),    # stage entry: split<false>, NT 4 split<true>, NT 2               split, 2 x 4 tiles
+    ("D-s2k1", 64, 128, ""),     # the skip, K = 1, 3 tiles: split<false>  narrow<true>            exact
+    ("D-up", 512, 256, ""),      # transposed convolution, one pair per output row: split<false>, NT 2  split<true>, NT 4  split, 4 x 2 tiles
+    ("D-up", 128, 64, ""),       # narrow<false> with nin != nout  split<true>, CB 128, NT 1       exact
+    ("E", 128, 128, ""),         # >= 20 empty offsets: the tile list skips them, the reduce launch has empty segments
+    ("1", 128, 128, ""),         # P = 1: one tile of one pair, 26 empty segments, split arms
+    ("1", 64, 64, ""),           # P = 1: narrow arms, exact weight gradient
+    ("0", 64, 128, ""),          # P = 0 (a 1x1x1 stride-2 map whose only input site is no output site): no launch, zeros
+]
+
+
+@pytest.mark.parametrize("geom,cin,cout,multi", _PAIR_CASES, ids=[f"{g}-{a}to{b}" for g, a, b, _ in _PAIR_CASES])
+def test_pair_kernels_every_dispatch_arm(geom, cin, cout, multi):
+    """The default path (PairPlan + the three matrix-core launches) against the float64 oracle with autograd, at the backbone's
+    real widths and on maps with nin != nout, empty offsets and a single pair: out, dfeats and dweight within the tolerance of
+    test_sparse_conv_forward_backward (1e-4 of the largest reference value + 1e-6).
+
+    Measured max|got - ref| / max|ref| on an MI355X (out, dfeats, dweight):
+      map     cin->cout   out       dfeats    dweight
+      D-same  256->256    4.63e-06  4.30e-06  4.48e-06
+      D-same  512->512    4.31e-06  4.13e-06  4.70e-06
+      D-same  96->256     2.62e-07  4.60e-06  6.11e-07
+      D-same  256->96     4.27e-06  2.57e-07  5.44e-07
+      D-same  48->160     1.95e-07  3.06e-07  3.44e-07
+      D-same  160->80     2.45e-07  2.04e-07  3.91e-07
+      D-same  64->256     4.29e-06  3.37e-07  3.33e-07
+      D-s2k3  64->128     4.58e-06  2.17e-07  2.05e-07
+      D-s2k3  256->512    4.95e-06  4.55e-06  4.35e-06
+      D-s2k1  64->128     6.17e-06  4.50e-07  1.95e-07
+      D-up    512->256    4.93e-06  4.36e-06  4.71e-06
+      D-up    128->64     4.44e-07  4.93e-06  2.08e-07
+      E       128->128    4.09e-06  5.44e-06  5.84e-06
+      1       128->128    7.18e-06  6.83e-06  1.83e-05
+      1       64->64      1.77e-07  2.51e-07  5.43e-08
+      0       64->128     0.00e+00  0.00e+00  0.00e+00
+    (the single pair of 1 128->128 is one split-bf16 product per weight-gradient element, with nothing to average over:
+    1.8e-5 = 1.2 * 2^-16 is exactly what hi hi + hi lo + lo hi gives for these operands when evaluated in float64.)
+    """
+    from vdetr_amd import sparse_ops as S
+    nbr, inv, nin = _pair_geometry(geom)
+    K, nout = nbr.shape
+    counts = (nbr >= 0).sum(1)
+    P, ntiles = int(counts.sum()), int(((counts + 127) // 128).sum())
+    want = _PAIR_GEOMETRIES[geom]
+    assert (nin, nout) == want[:2] and (want[2] is None or (P, ntiles) == want[2:]), (geom, nin, nout, P, ntiles)
+    empty = [k for k in range(K) if int(counts[k]) == 0]
+    if geom == "E":
+        assert len(empty) >= 20, f"geometry E: only {len(empty)} of the 27 offsets are empty"
+    g = torch.Generator().manual_seed(1000 * cin + cout)
+    f = torch.randn((nin, cin), generator=g)
+    w = torch.randn((K, cin, cout), generator=g) / np.sqrt(cin * K)
+    dy = torch.randn((nout, cout), generator=g)
+
+    fr, wr = f.double().requires_grad_(True), w.double().requires_grad_(True)
+    ref = O.sparse_conv(fr, wr, nbr)
+    ref.backward(dy.double())
+
+    nbr_d = nbr.to(DEV)
+    plan = S.PairPlan(nbr_d, nin)
+    assert plan.P == P and plan.ntiles == ntiles
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    for direction, CB in (("f", cout), ("d", cin)):
+        if direction in multi:
+            items = plan.ntiles * -(-CB // 128)
+            assert items > 2 * cus, f"{items} work items on {cus} CUs: no workgroup of the persistent kernel takes a second item"
+    fd, wd = f.to(DEV).requires_grad_(True), w.to(DEV).requires_grad_(True)
+    got = S.sparse_conv(fd, wd, nbr_d, inv.to(DEV), plan)
+    got.backward(dy.to(DEV))
+    errs = {}
+    for name, a, b in (("out", got, ref), ("dfeats", fd.grad, fr.grad), ("dweight", wd.grad, wr.grad)):
+        scale = float(b.detach().abs().max())
+        errs[name] = (float((a.detach().cpu().double() - b.detach()).abs().max()), scale)
+    print(f"PAIR_ERR {geom} {cin}->{cout} " + " ".join(f"{n} {e / max(s, 1e-300):.2e}" for n, (e, s) in errs.items()))
+    for name, (e, scale) in errs.items():
+        assert e <= 1e-4 * scale + 1e-6, (name, e, scale)
+    if geom == "E":
+        for k in empty:  # no pair, no partial product: the reduce launch writes the zeros itself
+            assert torch.equal(wd.grad[k], torch.zeros_like(wd.grad[k])), k
+        alone = torch.nonzero((nbr >= 0).sum(0) == 1)[:, 0]  # sites whose only pair is the centre offset
+        assert alone.numel() > 0
+        centre = f.double()[alone] @ w.double()[13]
+        assert float((got.detach().cpu().double()[alone] - centre).abs().max()) <= 1e-4 * float(centre.abs().max()) + 1e-6
+
+
 @pytest.mark.parametrize("n,c,act,res,training", [(5000, 64, "relu", True, True), (777, 256, "elu", False, True),
-                                                  (130, 16, None, True, True), (3000, 512, "relu", False, False), (1, 8, "relu", False, True)])
+                                                  (130, 16, None, True, True), (3000, 512, "relu", False, False), (1, 8, "relu", False, True),
+                                                  (2554, 512, "relu", True, True), (300, 1024, "elu", False, True)])
 def test_fused_batchnorm_activation(n, c, act, res, training):
     """csrc/sp_bn.hip against nn.BatchNorm1d + residual + activation in float64: outputs, all gradients, running statistics"""
     from vdetr_amd import sparse_ops as S

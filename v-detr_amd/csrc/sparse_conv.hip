@@ -321,7 +321,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, kSpWaves
 // B operand addresses are a uniform row pointer (scalar registers) + a per-lane column offset: no 64-bit vector address
 // arithmetic in the loop (the plain kernel: 16 v_lshl_add_u64 per K-step).
 // fp32 operands on the bf16 matrix unit: x = hi + lo (both round-to-nearest bf16), products as the three leading cross terms
-// hi hi + hi lo + lo hi: relative error of a product <= 2^-16, fp32 accumulation.  v_mfma_f32_16x16x4_f32 runs at 1/16 of
+// hi hi + hi lo + lo hi: relative error of a product <= 3 * 2^-16 (hi + lo is within 2^-16 of x for either operand and the
+// dropped lo lo term is below 2^-16; 2.3e-5 = 1.5 * 2^-16 is what a single product of random operands reaches, and what the
+// one-pair case of tests/test_gpu_sparse.py measures), fp32 accumulation.  v_mfma_f32_16x16x4_f32 runs at 1/16 of
 // the bf16 rate (MI355X_MICROARCH.md): the fp32 form of these kernels sat at 45-55 % of THAT peak.
 typedef __bf16 sp_bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void sp_split8(const f32x4& x0, const f32x4& x1, sp_bf16x8& hi, sp_bf16x8& lo) {
