@@ -1382,6 +1382,67 @@ int vdetr_probe_timestamp(uint64_t* slot, vdetr_stream_t stream);
 /* MFMA layout self-test: C[16,16] = A[16,64] * B[16,64]^T through v_mfma_f32_16x16x4_f32. */
 int vdetr_selftest_mfma_f32(const float* a, const float* b, float* c, vdetr_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * PointNet++ layers in inference form (eval mode, no autograd), ONE launch each (group_mlp.hip): a workgroup owns a tile of
+ * grouped rows, stages the layer input in LDS and runs 1 to 3 layers of y = relu(scale * (W x) + shift) on it
+ * (v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation), each layer's output replacing its input in LDS.
+ * scale / shift are the folded eval-mode BatchNorm (gamma * rsqrt(var + eps), beta - mean * that) or (1, conv.bias); they are
+ * applied per element BEFORE any pooling.  No allocation, no atomics: two runs give the same bits.
+ *
+ * The weights are read through zero-padded transposed images: layer l's image is [pad16(in_l)][pad64(out_l)] floats,
+ * image[k][c] = W_l[c][k], where in_0 = cin, in_l = width[l - 1], pad16 / pad64 round up to a multiple of 16 / 64; scale and
+ * shift are [pad64(out_l)] with zeros behind out_l.  vdetr_group_mlp_pack_f32 writes one layer's three arrays.
+ * Needs 1 <= nlayers <= 3, 1 <= cin <= 512, every width a multiple of 16 in [16, 256], 16-B aligned images and vectors.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct vdetr_group_mlp_desc {
+  int32_t nlayers;         /* 1 .. 3 */
+  int32_t cin;             /* length of the first contraction (not padded) */
+  int32_t width[3];        /* output channels of each layer */
+  int32_t reserved;
+  const float* wt[3];      /* transposed, zero-padded weight images */
+  const float* scale[3];
+  const float* shift[3];
+} vdetr_group_mlp_desc;
+
+/* One layer's image and vectors from W [cout][cin] (row-major) and, all four or none, the BatchNorm's gamma / beta / running
+ * mean / running variance [cout]; `bias` [cout] or NULL.  With BatchNorm: scale = gamma * rsqrt(var + eps), shift = beta +
+ * (bias - mean) * scale; without: scale = 1, shift = bias (or 0). */
+int vdetr_group_mlp_pack_f32(const float* w, const float* bias, const float* gamma, const float* beta, const float* mean,
+                             const float* var, float eps, int cin, int cout, float* wt, float* scale, float* shift,
+                             vdetr_stream_t stream);
+
+/* Set abstraction after the ball query: out[b][c][m] = max over s of mlp(row(b, m, s)), where row = concat((xyz[b][idx[b][m][s]]
+ * - new_xyz[b][m]) * inv_radius if use_xyz, features[b][:, idx[b][m][s]]).  The [B, ., M, S] tensors never exist.
+ * S in {16, 32, 64}; mlp.cin = (use_xyz ? 3 : 0) + C; idx entries outside [0, N) are clamped into it. */
+typedef struct vdetr_sa_mlp_desc {
+  int32_t B, N, M, S;      /* scenes, points, centres, neighbours per centre */
+  int32_t C, use_xyz;      /* feature channels (0: features is NULL) */
+  float inv_radius;        /* 1 unless normalize_xyz */
+  int32_t reserved;
+  const float* xyz;        /* [B, N, 3] */
+  const float* features;   /* [B, C, N] or NULL */
+  const float* new_xyz;    /* [B, M, 3] */
+  const int32_t* idx;      /* [B, M, S] */
+  float* out;              /* [B, width[nlayers - 1], M] */
+  vdetr_group_mlp_desc mlp;
+} vdetr_sa_mlp_desc;
+int vdetr_sa_mlp_max_infer_f32(const vdetr_sa_mlp_desc* d, vdetr_stream_t stream);
+
+/* Feature propagation: out[b][:, i] = mlp(concat(sum_k weight[b][i][k] * known_feats[b][:, idx[b][i][k]], unknow_feats[b][:, i])).
+ * mlp.cin = C2 + C1; idx entries outside [0, m) are clamped into it. */
+typedef struct vdetr_fp_mlp_desc {
+  int32_t B, n, m;         /* scenes, unknown points, known points */
+  int32_t C1, C2;          /* channels of unknow_feats (0: NULL) and of known_feats */
+  int32_t reserved;
+  const float* known_feats;  /* [B, C2, m] */
+  const float* unknow_feats; /* [B, C1, n] or NULL */
+  const int32_t* idx;      /* [B, n, 3] */
+  const float* weight;     /* [B, n, 3] */
+  float* out;              /* [B, width[nlayers - 1], n] */
+  vdetr_group_mlp_desc mlp;
+} vdetr_fp_mlp_desc;
+int vdetr_fp_mlp_infer_f32(const vdetr_fp_mlp_desc* d, vdetr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

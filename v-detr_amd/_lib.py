@@ -178,6 +178,27 @@ class HeadsInferDesc(ctypes.Structure):
                                 "y")]
 
 
+class GroupMlpDesc(ctypes.Structure):
+    """Mirror of ``vdetr_group_mlp_desc``."""
+
+    _fields_ = [("nlayers", ctypes.c_int32), ("cin", ctypes.c_int32), ("width", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32),
+                ("wt", c_void_p * 3), ("scale", c_void_p * 3), ("shift", c_void_p * 3)]
+
+
+class SaMlpDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sa_mlp_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "N", "M", "S", "C", "use_xyz")] + [("inv_radius", c_float), ("reserved", ctypes.c_int32)] + [
+        (n, c_void_p) for n in ("xyz", "features", "new_xyz", "idx", "out")] + [("mlp", GroupMlpDesc)]
+
+
+class FpMlpDesc(ctypes.Structure):
+    """Mirror of ``vdetr_fp_mlp_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "n", "m", "C1", "C2", "reserved")] + [
+        (n, c_void_p) for n in ("known_feats", "unknow_feats", "idx", "weight", "out")] + [("mlp", GroupMlpDesc)]
+
+
 class AttnParts(ctypes.Structure):
     """Mirror of ``vdetr_attn_parts``."""
 
@@ -495,6 +516,9 @@ _SIGNATURES = {
     "vdetr_gather_proposals_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 14),
     "vdetr_selftest_lds_atomics": (c_int, [c_int, c_int, c_void_p, c_void_p]),
     "vdetr_selftest_mfma_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vdetr_group_mlp_pack_f32": (c_int, [c_void_p] * 6 + [c_float, c_int, c_int] + [c_void_p] * 4),
+    "vdetr_sa_mlp_max_infer_f32": (c_int, [ctypes.POINTER(SaMlpDesc), c_void_p]),
+    "vdetr_fp_mlp_infer_f32": (c_int, [ctypes.POINTER(FpMlpDesc), c_void_p]),
 }
 
 _lib = None
