@@ -1262,6 +1262,26 @@ int vdetr_sp_bn_act_fwd_f32(const vdetr_spbn_desc* d, vdetr_stream_t stream);
 int vdetr_sp_bn_act_bwd_f32(const vdetr_spbn_desc* d, const float* dy, float* dx, float* dresidual, float* dgamma, float* dbeta,
                             vdetr_stream_t stream);
 
+/* The flat gather-sum of a pair-list layer with the layer's eval-mode epilogue, in one launch (inference: conv -> BatchNorm
+ * with running statistics -> activation, model_vdetr.py:141-176, mink_resnet.py:38-84 under model.eval()):
+ *   acc = sum over k = 0..K-1, in that order, of src[slot[k][u]]             (slot < 0: no pair; src rows src_stride floats apart)
+ *   v   = (acc + conv_bias[c]) * scale[c] + shift[c] + residual[u][c]        scale = gamma * rsqrt(running_var + eps),
+ *   out[u][c] = act(v) + post_add[u][c]                                      shift = beta - running_mean * scale
+ * act: 0 none, 1 ReLU, 2 ELU(alpha = 1).  src [P,src_stride] f32 (vdetr_sp_pairs_gemm_f32's y; may be NULL when the layer has
+ * no pair at all), slot [K,nrows] i32 (vdetr_sp_pair_plan_i32), residual / post_add / out [nrows,C] f32, the rest [C] f32.
+ * conv_bias, gamma (= 1), beta (= 0), residual and post_add may be NULL.  C % 4 == 0, src_stride % 4 == 0, src_stride >= C.
+ * Same summation and expression order as vdetr_sp_gather_sum_f32 + vdetr_sp_bn_act_fwd_f32 (training = 0): the same bits.
+ * No atomics, no workspace, nothing cached between calls. */
+typedef struct vdetr_sp_gsum_bn_desc {
+  int32_t K, nrows, C, src_stride, act;
+  float eps;
+  const float* src;
+  const int32_t* slot;
+  const float *conv_bias, *gamma, *beta, *running_mean, *running_var, *residual, *post_add;
+  float* out;
+} vdetr_sp_gsum_bn_desc;
+int vdetr_sp_gather_sum_bn_act_f32(const vdetr_sp_gsum_bn_desc* d, vdetr_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Fixed coordinate embeddings — PositionEmbeddingCoordsSine (models/position_embedding.py:21-148); one launch each.
  *   xyz (b,n,3); range_min / range_max (b,3) = the scene extent for `normalize=True` (shift_scale_points,

@@ -371,6 +371,14 @@ class SpBnDesc(ctypes.Structure):
                                          "y", "save_mean", "save_invstd", "workspace")])
 
 
+class SpGsumBnDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_gsum_bn_desc``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("K", "nrows", "C", "src_stride", "act")] + [("eps", c_float)] +
+                [(n, c_void_p) for n in ("src", "slot", "conv_bias", "gamma", "beta", "running_mean", "running_var", "residual",
+                                         "post_add", "out")])
+
+
 # name -> (restype, argtypes); must list every symbol of include/vdetr_hip.h (tests check this)
 _SIGNATURES = {
     "vdetr_abi_version": (c_int, []),
@@ -485,6 +493,7 @@ _SIGNATURES = {
     "vdetr_sp_inverse_map_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_sp_gather_cols_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_sp_gather_sum_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vdetr_sp_gather_sum_bn_act_f32": (c_int, [ctypes.POINTER(SpGsumBnDesc), c_void_p]),
     "vdetr_sp_pairs_gemm_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_sp_pair_plan_workspace_ints": (c_int, [c_int, c_int]),
     "vdetr_sp_pair_plan_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -38,4 +38,17 @@ __device__ __forceinline__ bool bn_keep(const BnRng& g, unsigned chankey, int e)
 // the two 16-bit draws of elements 2 p and 2 p + 1
 __device__ __forceinline__ unsigned bn_draw2(unsigned chankey, int pair) { return fmix32(chankey ^ ((unsigned)pair * 0x165667B1u)); }
 
+// the activation behind a sparse tensor's BatchNorm (sp_bn.hip, and the eval-mode epilogue of sparse_conv.hip): 0 none, 1 ReLU,
+// 2 ELU (alpha 1), on the four channels a thread holds
+__device__ __forceinline__ f32x4 bn_act(f32x4 v, int act) {
+  if (act == 1) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+  } else if (act == 2) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : expm1f(v[e]);
+  }
+  return v;
+}
+
 }  // namespace vdetr

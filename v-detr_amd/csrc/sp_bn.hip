@@ -11,7 +11,7 @@
 //   backward: partials of sum(g), sum(g * xhat) with g = dy * act'(y) -> apply dx = gamma * invstd * (g - mean(g) -
 //             xhat * mean(g xhat)), dresidual = g; workgroup 0 stores dgamma / dbeta.
 // Pure HBM streams: x (and residual) read twice / once, y written once.
-#include "common.h"
+#include "bn_common.h"
 
 namespace vdetr {
 
@@ -19,16 +19,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBnRowsMin = 16, kBnRowsMax = 128;  // rows per workgroup: chosen so that a table gives >= ~1000 workgroups
 static inline int bn_rows(int N) { int r = N / 1024; r = r < kBnRowsMin ? kBnRowsMin : r > kBnRowsMax ? kBnRowsMax : r; return (r + 15) / 16 * 16; }
 
-__device__ __forceinline__ f32x4 bn_act(f32x4 v, int act) {
-  if (act == 1) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-  } else if (act == 2) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : expm1f(v[e]);
-  }
-  return v;
-}
 // d act / d pre-activation from the OUTPUT y
 __device__ __forceinline__ f32x4 bn_act_grad(f32x4 dy, f32x4 y, int act) {
   if (act == 1) {

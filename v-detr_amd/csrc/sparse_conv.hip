@@ -16,12 +16,15 @@
 //   vdetr_sp_gather_cols_f32  col[u][k][:] = in[nbr[k][u]][:] or 0     (the im2col operand of ONE library GEMM per layer)
 //   vdetr_sp_gather_sum_f32   din[i][:] = sum_k dcol[inv[k][i]][k][:]  (its adjoint as a GATHER: no float atomics; the source
 //                             may also be offset-major [K][M][C]: the compacted per-offset row lists of sparse_ops.ConvPlan)
+//   vdetr_sp_gather_sum_bn_act_f32  the flat gather-sum of a pair-list layer that FINISHES the row in eval mode instead of
+//                             storing the sum: + conv bias, BatchNorm with its running statistics, + residual, activation,
+//                             + skip (the conv -> BatchNorm -> activation sites of the backbone under inference: one launch)
 // The two feature kernels are pure HBM streams of C-float rows (256 B - 2 KB each): float4 per lane, rows x offsets over
 // the whole chip.
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
-#include "common.h"
+#include "bn_common.h"
 
 namespace vdetr {
 
@@ -173,6 +176,64 @@ __global__ __launch_bounds__(256) void sp_gather_kernel(const float* __restrict_
   }
 }
 
+// The flat gather-sum (SUM, nmap < 0 above) with the eval-mode epilogue of its layer: what sp_gather_kernel<true>, the ATen add
+// of the convolution's bias, sp_bn_apply_kernel (running statistics) and the neck's skip add do in three to five launches
+// that exchange [N, C] tables.  With running statistics BatchNorm is a per-channel affine, and the thread already holds its
+// four channels of the row.  Same summation order as above, same expression order as sp_bn_apply_kernel (x * scale + shift,
+// += residual, bn_act), no contraction (-ffp-contract=off): bit-equal to the composition.  BatchNorm's own tensors are read
+// and folded per thread (4 x 4 floats from L2): no packed-parameter cache to invalidate, nothing launched beforehand.
+// src rows are src_stride floats apart (the GEMM's Cout padded to 16); out rows are C floats: no slice copy.
+struct SpGsumBnParams {
+  int K, nrows, C4, stride4, act;
+  float eps;
+  const float* src;
+  const int* slot;
+  const float *conv_bias, *gamma, *beta, *mean, *var, *residual, *post_add;
+  float* out;
+};
+
+__global__ __launch_bounds__(256) void sp_gather_sum_bn_act_kernel(SpGsumBnParams P) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)P.nrows * P.C4) return;
+  const int c4 = (int)(t % P.C4);
+  const int i = (int)(t / P.C4);
+  // everything that does not hang on a map entry is requested first: it arrives under the index -> row round trips
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 mean = reinterpret_cast<const f32x4*>(P.mean)[c4], var = reinterpret_cast<const f32x4*>(P.var)[c4];
+  const f32x4 g = P.gamma ? reinterpret_cast<const f32x4*>(P.gamma)[c4] : f32x4{1.f, 1.f, 1.f, 1.f};
+  const f32x4 b = P.beta ? reinterpret_cast<const f32x4*>(P.beta)[c4] : zero;
+  const f32x4 cb = P.conv_bias ? reinterpret_cast<const f32x4*>(P.conv_bias)[c4] : zero;
+  const f32x4 res = P.residual ? reinterpret_cast<const f32x4*>(P.residual)[t] : zero;
+  const f32x4 post = P.post_add ? reinterpret_cast<const f32x4*>(P.post_add)[t] : zero;
+  const bool has_src = P.src != nullptr;  // a layer without a single pair has no source: every slot counts as empty
+  f32x4 acc = zero;
+  constexpr int G = 8;  // eight offsets at a time, as in sp_gather_kernel: map entries together, then their rows
+  for (int k0 = 0; k0 < P.K; k0 += G) {
+    int u[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) u[j] = (has_src && k0 + j < P.K) ? P.slot[(size_t)(k0 + j) * P.nrows + i] : -1;
+    f32x4 v[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      v[j] = zero;
+      if (u[j] >= 0) v[j] = reinterpret_cast<const f32x4*>(P.src)[(size_t)u[j] * P.stride4 + c4];
+    }
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+      if (u[j] >= 0) acc += v[j];
+  }
+  f32x4 invstd;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) invstd[e] = rsqrtf(var[e] + P.eps);
+  const f32x4 scale = invstd * g, shift = b - mean * scale;
+  if (P.conv_bias) acc += cb;
+  f32x4 v = acc * scale + shift;
+  if (P.residual) v += res;
+  v = bn_act(v, P.act);
+  if (P.post_add) v += post;
+  reinterpret_cast<f32x4*>(P.out)[t] = v;
+}
+
 }  // namespace vdetr
 
 using namespace vdetr;
@@ -220,6 +281,28 @@ extern "C" int vdetr_sp_gather_sum_f32(const float* dcol, const int32_t* inv, in
   hipLaunchKernelGGL((sp_gather_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dcol,
                      inv, K, nin, offset_major_rows, C / 4, din);
   return check_launch("sp_gather_sum");
+}
+
+extern "C" int vdetr_sp_gather_sum_bn_act_f32(const vdetr_sp_gsum_bn_desc* d, vdetr_stream_t stream) {
+  VDETR_REQUIRE(d, "sp_gather_sum_bn_act: null descriptor");
+  VDETR_REQUIRE(d->C > 0 && d->C % 4 == 0, "sp_gather_sum_bn_act: C=%d must be a positive multiple of 4 (float4 rows)", d->C);
+  VDETR_REQUIRE(d->src_stride % 4 == 0 && d->src_stride >= d->C,
+                "sp_gather_sum_bn_act: src_stride=%d must be a multiple of 4 and >= C=%d", d->src_stride, d->C);
+  VDETR_REQUIRE(d->K > 0, "sp_gather_sum_bn_act: K=%d must be positive", d->K);
+  VDETR_REQUIRE(d->nrows >= 0, "sp_gather_sum_bn_act: nrows=%d is negative", d->nrows);
+  VDETR_REQUIRE(d->act >= 0 && d->act <= 2, "sp_gather_sum_bn_act: act=%d (0 none, 1 relu, 2 elu)", d->act);
+  VDETR_REQUIRE(d->running_mean && d->running_var, "sp_gather_sum_bn_act: %s is NULL (the eval form needs running statistics)",
+                d->running_mean ? "running_var" : "running_mean");
+  if (d->nrows == 0) return VDETR_OK;
+  VDETR_REQUIRE(d->slot && d->out, "sp_gather_sum_bn_act: %s is NULL with nrows=%d", d->slot ? "out" : "slot", d->nrows);
+  const long long blocks = ((long long)d->nrows * (d->C / 4) + 255) / 256;
+  VDETR_REQUIRE(blocks <= 0x7fffffffLL, "sp_gather_sum_bn_act: nrows=%d x C=%d is more than one launch covers", d->nrows, d->C);
+  SpGsumBnParams P;
+  P.K = d->K; P.nrows = d->nrows; P.C4 = d->C / 4; P.stride4 = d->src_stride / 4; P.act = d->act; P.eps = d->eps;
+  P.src = d->src; P.slot = d->slot; P.conv_bias = d->conv_bias; P.gamma = d->gamma; P.beta = d->beta;
+  P.mean = d->running_mean; P.var = d->running_var; P.residual = d->residual; P.post_add = d->post_add; P.out = d->out;
+  hipLaunchKernelGGL(sp_gather_sum_bn_act_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P);
+  return check_launch("sp_gather_sum_bn_act");
 }
 
 // ====================================================================================================================

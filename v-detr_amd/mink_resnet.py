@@ -55,6 +55,7 @@ class MinkResNet(nn.Module):
                 ME.kaiming_normal_(mod.kernel, mode="fan_out", nonlinearity="relu")
 
     def forward(self, x):
+        ME.clear_last_paths()
         x = self.conv1(x)
         fused_stem = isinstance(self.norm1, ME.MinkowskiBatchNorm)
         x = self.norm1(x, act="relu") if fused_stem else self.relu(self.norm1(x))

@@ -21,7 +21,46 @@ import threading
 import torch
 import torch.nn as nn
 
+from . import heads as HD
 from . import sparse_ops as S
+
+# Inference (``heads.inference``: eval mode, autograd off): a convolution -> BatchNorm -> activation site is TWO launches, the
+# pair GEMM and a gather-sum that finishes the row (sparse_ops.gather_sum_bn_act), instead of GEMM, gather-sum,
+# (bias add,) BatchNorm pass(, skip add).  ``INFER_FUSED = False`` keeps the composition (A/B runs, parity tests).
+INFER_FUSED = True
+LAST_PATHS = []  # "fused" / "composition" per convolution -> BatchNorm site of the last forward (cleared by MinkResNet.forward / backbone_forward)
+
+
+def clear_last_paths():
+    if not _geometry_only():  # (a loader thread's geometry pass runs beside the training thread's forward)
+        del LAST_PATHS[:]
+
+
+def _record_path(path):
+    if len(LAST_PATHS) >= 4096:  # (sites driven in a loop without either forward above: keep the record bounded)
+        del LAST_PATHS[:]
+    LAST_PATHS.append(path)
+
+
+def _conv_bn_fusable(module, feats, plan=None, cout=None, bn=None):
+    """The gate of the fused inference form, asked twice per site: by the convolution (``plan``, ``cout``: may its pair products
+    stay un-summed?) and by the BatchNorm that receives them (``bn``: can it finish them in the fused launch?).  Everything
+    else — training, autograd, SyncBatchNorm / no running statistics, CPU tensors, the plan / im2col modes — takes the
+    composition of launches, unchanged."""
+    if not (INFER_FUSED and HD.inference(module)) or _geometry_only():
+        return False
+    if plan is not None:
+        if not (isinstance(plan, S.PairPlan) and feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous()):
+            return False
+        width = cout + (-cout) % 16
+        if cout % 4 or max(feats.numel(), plan.K * plan.nout, plan.nout * width, plan.P * width) >= 2 ** 31:
+            return False
+    if bn is not None:
+        if type(bn) is not nn.BatchNorm1d or bn.running_mean is None or bn.running_var is None:
+            return False
+        if not all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+            return False
+    return True
 
 
 # Geometry-only pass (ModelVDETR.prepare_geometry): convolutions build their sites / kernel maps / pair lists and hand on an
@@ -162,6 +201,26 @@ class CoordinateManager:
         return self
 
 
+class _PendingConv:
+    """The pair products y [P, Cout padded to 16] of a convolution (None: the layer has no pair) with the rest of its forward
+    still to run: the gather-sum over ``slot`` [K, Nout], the cut to ``channels`` and the ``bias`` add."""
+    __slots__ = ("y", "slot", "channels", "bias")
+
+    def __init__(self, y, slot, channels, bias):
+        self.y, self.slot, self.channels, self.bias = y, slot, channels, bias
+
+    def materialise(self):
+        """what MinkowskiConvolution.forward computes without the hand-over, op for op"""
+        width = self.channels + (-self.channels) % 16
+        if self.y is None:
+            f = torch.zeros((self.slot.shape[1], width), dtype=torch.float32, device=self.slot.device)
+        else:
+            f = S.gather_sum(self.y, self.slot, flat=True)
+        if width != self.channels:
+            f = f[:, :self.channels]
+        return f if self.bias is None else f + self.bias
+
+
 class SparseTensor:
     """features [N, C] on the sites ``coordinates`` [N, 4] = (batch, x, y, z) (MinkowskiEngine's SparseTensor)."""
 
@@ -171,10 +230,28 @@ class SparseTensor:
             coordinate_manager = CoordinateManager(features.device)
             coordinate_manager.insert_points(coordinates)
             features = features[coordinate_manager.unique_index]  # one row per site, in site (key) order
-        self.F = features
+        self._F, self._pending = features, None
         self.tensor_stride = tensor_stride
         self.coordinate_manager = coordinate_manager
         self.keys = keys if keys is not None else coordinate_manager.keys[tensor_stride]
+
+    @classmethod
+    def pending(cls, conv, tensor_stride, coordinate_manager, keys):
+        """the output of a convolution under inference whose gather-sum has not run: ``conv`` (_PendingConv) is finished by the
+        MinkowskiBatchNorm that receives this tensor, or summed by whatever else reads ``.F``"""
+        out = cls(None, tensor_stride=tensor_stride, coordinate_manager=coordinate_manager, keys=keys)
+        out._pending = conv
+        return out
+
+    @property
+    def F(self):
+        if self._pending is not None:
+            self._F, self._pending = self._pending.materialise(), None
+        return self._F
+
+    @F.setter
+    def F(self, features):
+        self._F, self._pending = features, None
 
     @property
     def C(self):
@@ -182,7 +259,7 @@ class SparseTensor:
 
     @property
     def device(self):
-        return self.F.device
+        return self.keys.device if self._pending is not None else self._F.device
 
     def _like(self, features):
         return SparseTensor(features, tensor_stride=self.tensor_stride, coordinate_manager=self.coordinate_manager, keys=self.keys)
@@ -241,6 +318,9 @@ class MinkowskiConvolution(nn.Module):
                 plan.request_wgrad(w.shape[1], w.shape[2])
             return SparseTensor(x.F.new_empty((out_keys.shape[0], self.out_channels)), tensor_stride=out_ts,
                                 coordinate_manager=cm, keys=out_keys)
+        if _conv_bn_fusable(self, x.F, plan=plan, cout=self.out_channels):
+            return SparseTensor.pending(_PendingConv(S.pair_products(x.F, w, plan), plan.slot, self.out_channels, self.bias),
+                                        out_ts, cm, out_keys)
         f = S.sparse_conv(x.F, w, nbr, inv, plan)
         if self.bias is not None:
             f = f + self.bias
@@ -265,11 +345,23 @@ class MinkowskiBatchNorm(nn.Module):
 
     fused_act = None  # "elu" / "relu": the activation module that follows in an nn.Sequential is folded into this layer
 
-    def forward(self, x, act=None, residual=None):
+    def forward(self, x, act=None, residual=None, post_add=None):
+        """act(bn(x) + residual) (+ post_add: a skip tensor added behind the activation, ``post_add + out``)"""
         if _geometry_only():
             return x
         act = act or self.fused_act
-        out = x._like(S.bn_act(x.F, self.bn, act, None if residual is None else residual.F))
+        conv = x._pending
+        if conv is not None and _conv_bn_fusable(self, None, bn=self.bn):
+            if post_add is not None:
+                assert x.keys is post_add.keys or torch.equal(x.keys, post_add.keys), "sparse tensors on different coordinate maps"
+            out = x._like(S.gather_sum_bn_act(conv.y, conv.slot, self.bn, act, None if residual is None else residual.F,
+                                              None if post_add is None else post_add.F, conv.bias, conv.channels))
+            _record_path("fused")
+        else:
+            out = x._like(S.bn_act(x.F, self.bn, act, None if residual is None else residual.F))
+            if post_add is not None:
+                out = post_add + out
+            _record_path("composition")
         out.applied_act = act
         return out
 
@@ -376,6 +468,19 @@ def fuse_activations(module):
                 if isinstance(a, MinkowskiBatchNorm) and isinstance(b, _Pointwise) and (b.kind == "relu" or b.fn.alpha == 1.0):
                     a.fused_act = b.kind
     return module
+
+
+def sequential_add(block, x, skip):
+    """``skip + block(x)`` for an nn.Sequential that ends BatchNorm -> folded activation (``fuse_activations``).  Under inference
+    the add is the ``post_add`` of the block's last fused launch; everywhere else it is exactly ``skip + block(x)``."""
+    mods = list(block) if isinstance(block, nn.Sequential) else []
+    tail = mods[-2] if len(mods) >= 2 else None
+    if not (INFER_FUSED and HD.inference(block)) or _geometry_only() or not isinstance(tail, MinkowskiBatchNorm) \
+            or not isinstance(mods[-1], _Pointwise) or tail.fused_act != mods[-1].kind:
+        return skip + block(x)
+    for m in mods[:-2]:
+        x = m(x)
+    return mods[-1](tail(x, post_add=skip))
 
 
 def kaiming_normal_(tensor, a=0, mode="fan_in", nonlinearity="leaky_relu"):

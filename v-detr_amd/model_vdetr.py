@@ -126,6 +126,7 @@ class ModelVDETR(nn.Module):
         """model_vdetr.py:248-280: voxelise at ``voxel_size``, MinkResNet, top-down FPN, out block -> per scene
         (xyz [n,3] = out.C[:,1:] * voxel_size, features [n,C] = out.F).  The reference's default (no colour) path reads an
         undefined name (:259); the evident intent — xyz as the input features — is what runs here."""
+        ME.clear_last_paths()
         clouds = inputs["point_clouds"]
         if self.use_color:
             data = [(p[:, :3] / self.voxel_size, p[:, :] if self.xyz_color else p[:, 3:]) for p in clouds]
@@ -147,8 +148,7 @@ class ModelVDETR(nn.Module):
         for i in range(len(stages) - 1, self.layer_idx - 1, -1):
             if self.use_fpn:
                 if i < len(stages) - 1:
-                    x = getattr(self, f"up_block_{i + 1}")(x)
-                    x = stages[i] + x
+                    x = ME.sequential_add(getattr(self, f"up_block_{i + 1}"), x, stages[i])  # stages[i] + up_block(x)
             else:
                 x = stages[i]
             if i == self.layer_idx:

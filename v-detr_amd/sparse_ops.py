@@ -607,6 +607,63 @@ def bn_act(x, bn, act=None, residual=None):
                             bn.num_batches_tracked if bn.track_running_stats else None, training, momentum, bn.eps, _ACT[act])
 
 
+def _pair_operands(feats, weight):
+    """the operands of the fused pair kernels: they contract over multiples of 16 channels on either side (forward: Cin, input
+    gradient: Cout), so both widths are zero-padded to 16"""
+    pi, po = (-feats.shape[1]) % 16, (-weight.shape[2]) % 16
+    if pi or po:
+        feats = torch.nn.functional.pad(feats, (0, pi))
+        weight = torch.nn.functional.pad(weight, (0, po, 0, pi))
+    return feats.contiguous(), weight
+
+
+def pair_products(feats, weight, plan):
+    """The pair path of ``sparse_conv`` up to its gather-sum, for an inference caller that finishes the rows itself
+    (``gather_sum_bn_act``): y [P, Cout padded to 16] = feats[pin[p]] @ W[k(p)], or None when the layer has no pair at all.
+    ``gather_sum(y, plan.slot, flat=True)[:, :Cout]`` is what ``sparse_conv`` returns.  No autograd."""
+    feats, weight = _pair_operands(feats, weight)
+    return pairs_gemm(feats, plan.pin, weight.contiguous(), plan, False) if plan.P else None
+
+
+def gather_sum_bn_act(y, slot, bn, act=None, residual=None, post_add=None, conv_bias=None, channels=None):
+    """act(bn(gather_sum(y, slot)[:, :channels] + conv_bias) + residual) + post_add in ONE launch, for an ``nn.BatchNorm1d``
+    with running statistics (eval mode; vdetr_sp_gather_sum_bn_act_f32).  y [P, stride >= channels] are a layer's pair products
+    (``pair_products``; None: the layer has no pair), slot [K, N] its PairPlan.slot; residual / post_add [N, channels],
+    conv_bias [channels] or [1, channels].  Reads bn's own tensors at every call: nothing is cached.  No autograd."""
+    L.require_gpu(slot, "slot")
+    L.require_int(slot, "slot")
+    L.require_contiguous(slot, "slot")
+    K, n = slot.shape
+    d = L.SpGsumBnDesc()
+    if y is not None:
+        L.require_gpu(y, "y")
+        L.require_float(y, "y")
+        L.require_contiguous(y, "y")
+        d.src, d.src_stride = y.data_ptr(), y.shape[1]
+    C = channels if channels is not None else (y.shape[1] if y is not None else bn.num_features)
+    if y is None:
+        d.src_stride = C
+    if bn.running_mean is None or bn.running_var is None or bn.num_features != C:
+        raise RuntimeError(f"gather_sum_bn_act: a BatchNorm1d of {C} channels with running statistics is required")
+    out = torch.empty((n, C), dtype=torch.float32, device=slot.device)
+    d.K, d.nrows, d.C, d.act, d.eps = K, n, C, _ACT[act], float(bn.eps)
+    keep = []  # (the contiguous copies the descriptor points into)
+    for name, t, numel in (("conv_bias", conv_bias, C), ("gamma", bn.weight, C), ("beta", bn.bias, C), ("running_mean", bn.running_mean, C),
+                           ("running_var", bn.running_var, C), ("residual", residual, n * C), ("post_add", post_add, n * C)):
+        if t is None:
+            continue
+        L.require_gpu(t, name)
+        L.require_float(t, name)
+        if t.numel() != numel:
+            raise RuntimeError(f"gather_sum_bn_act: {name} has {t.numel()} elements, expected {numel}")
+        t = t.detach().contiguous()
+        keep.append(t)
+        setattr(d, name, t.data_ptr())
+    d.slot, d.out = slot.data_ptr(), out.data_ptr()
+    L.check(L.lib().vdetr_sp_gather_sum_bn_act_f32(ctypes.byref(d), L.stream_ptr()), "sp_gather_sum_bn_act")
+    return out
+
+
 _MODE = os.environ.get("VDETR_SP_MODE", "pairs")  # pairs (fused kernels) | plan (batched library GEMMs) | im2col
 _IM2COL = _MODE == "im2col" or os.environ.get("VDETR_SP_IM2COL", "0") == "1"  # A/B switch: one dense im2col GEMM per layer instead of the plan
 
@@ -618,13 +675,9 @@ def sparse_conv(feats, weight, nbr, inv, plan=None):
     if isinstance(plan, PairPlan) or (plan is None and _MODE == "pairs"):
         if plan is None:
             plan = PairPlan(nbr, feats.shape[0])
-        # the fused kernels contract over multiples of 16 channels on either side (forward: Cin, input gradient: Cout)
-        pi, po = (-cin) % 16, (-cout) % 16
-        if pi or po:
-            feats = torch.nn.functional.pad(feats, (0, pi))
-            weight = torch.nn.functional.pad(weight, (0, po, 0, pi))
-        out = _PairsConvFn.apply(feats.contiguous(), weight, plan)
-        return out[:, :cout] if po else out
+        feats, weight = _pair_operands(feats, weight)
+        out = _PairsConvFn.apply(feats, weight, plan)
+        return out[:, :cout] if out.shape[1] != cout else out
     pad = (-cin) % 4
     if pad:
         feats = torch.nn.functional.pad(feats, (0, pad))
