@@ -1463,6 +1463,23 @@ typedef struct vdetr_fp_mlp_desc {
 } vdetr_fp_mlp_desc;
 int vdetr_fp_mlp_infer_f32(const vdetr_fp_mlp_desc* d, vdetr_stream_t stream);
 
+/* The shared post MLP of PointnetLFPModuleMSG on up to four scales' pooled features, one launch:
+ * out[b][out_channel0 + k * P + :, i] = mlp(concat(pooled[k][b][:, i], features2[b][:, i])), P = width[nlayers - 1], k < K.
+ * Neither the per-scale concatenation nor the one over the scales exists.  mlp.cin = Ck + C2; out_channel0 + K * P <= out_channels.
+ * Rows are (scale, scene, point) in 32-row tiles; no atomics, no workspace. */
+typedef struct vdetr_pw_mlp_desc {
+  int32_t B, n, K;         /* scenes, points, scales of this launch (1 .. 4) */
+  int32_t Ck, C2;          /* channels of every pooled tensor and of features2 (0: NULL) */
+  int32_t out_channels;    /* channels of `out` (all scales of the layer) */
+  int32_t out_channel0;    /* first channel this launch writes */
+  int32_t reserved;
+  const float* pooled[4];  /* [B, Ck, n] each; entries from K on are not read */
+  const float* features2;  /* [B, C2, n] or NULL */
+  float* out;              /* [B, out_channels, n] */
+  vdetr_group_mlp_desc mlp;
+} vdetr_pw_mlp_desc;
+int vdetr_pw_mlp_infer_f32(const vdetr_pw_mlp_desc* d, vdetr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,13 @@ class FpMlpDesc(ctypes.Structure):
         (n, c_void_p) for n in ("known_feats", "unknow_feats", "idx", "weight", "out")] + [("mlp", GroupMlpDesc)]
 
 
+class PwMlpDesc(ctypes.Structure):
+    """Mirror of ``vdetr_pw_mlp_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "n", "K", "Ck", "C2", "out_channels", "out_channel0", "reserved")] + [
+        ("pooled", c_void_p * 4), ("features2", c_void_p), ("out", c_void_p), ("mlp", GroupMlpDesc)]
+
+
 class AttnParts(ctypes.Structure):
     """Mirror of ``vdetr_attn_parts``."""
 
@@ -528,6 +535,7 @@ _SIGNATURES = {
     "vdetr_group_mlp_pack_f32": (c_int, [c_void_p] * 6 + [c_float, c_int, c_int] + [c_void_p] * 4),
     "vdetr_sa_mlp_max_infer_f32": (c_int, [ctypes.POINTER(SaMlpDesc), c_void_p]),
     "vdetr_fp_mlp_infer_f32": (c_int, [ctypes.POINTER(FpMlpDesc), c_void_p]),
+    "vdetr_pw_mlp_infer_f32": (c_int, [ctypes.POINTER(PwMlpDesc), c_void_p]),
 }
 
 _lib = None

@@ -18,6 +18,8 @@
 // 64 block + 4 j + u (heads.hip's interleave): the four B operands of one contraction index are one float4 of an image row, and a
 // lane's four accumulators of a row are four adjacent columns, one float4 of the LDS tile.
 // LDS rows are (widest layer rounded up to 64) + 4 floats: 16 consecutive rows land on 16 different 16-byte slots.
+//
+// pw_mlp_kernel is the point-wise sibling (PointnetLFPModuleMSG's shared post MLP): no gather, rows = (scale, scene, point).
 #include "attn_common.h"
 
 namespace vdetr {
@@ -223,6 +225,72 @@ __global__ __launch_bounds__(kGmThreads) void group_mlp_kernel(GmArgs A) {
   }
 }
 
+// The shared post MLP of PointnetLFPModuleMSG on every scale's pooled features, ONE launch for up to four scales: row g = (scale k,
+// scene b, point i) = concat(pooled[k][b][:, i], features2[b][:, i]); the result goes to the scale's channel slice of `out`, so
+// neither the per-scale concatenation nor the one over the scales exists.  32-row tiles like the feature propagation; a row is
+// decomposed on its own, so a tile may straddle a scene and a scale boundary.
+struct PwArgs {
+  vdetr_group_mlp_desc mlp;
+  const float* p0; const float* p1; const float* p2; const float* p3;  // pooled [B, Ck, n] per scale (named, not an array: the scale is per thread)
+  const float* feats2;   // [B, C2, n] or null
+  float* out;            // [B, out_channels, n]
+  int n, Ck, C2, out_channels, out_channel0;
+  int stride;            // floats per LDS row
+  long bn;               // B n
+  long rows;             // K B n
+};
+
+__global__ __launch_bounds__(kGmThreads) void pw_mlp_kernel(PwArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float gm_xs[];
+  float* xs = gm_xs;
+  constexpr int kRows = 32, kGroups = kGmThreads / kRows;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int stride = A.stride, cin = A.mlp.cin, k0pad = (cin + 15) & ~15;
+  // thread = (row r, every kGroups-th column from cq on), in the prologue and in the epilogue: the row is decomposed once
+  const int r = tid % kRows, cq = tid / kRows;
+  const long g = (long)blockIdx.x * kRows + r;
+  const bool live = g < A.rows;
+  long k = 0, b = 0, i = 0;
+  if (live) {
+    k = g / A.bn;
+    const long rem = g - k * A.bn;
+    b = rem / A.n;
+    i = rem - b * A.n;
+  }
+  {  // ---- prologue ----
+    const float* pk = k == 0 ? A.p0 : k == 1 ? A.p1 : k == 2 ? A.p2 : A.p3;
+    const float* pr = pk + b * A.Ck * A.n + i;                          // channel c of the row: pr[c n]
+    const float* fr = A.feats2 ? A.feats2 + b * A.C2 * A.n + i : pk;    // (never read when C2 == 0: cin == Ck)
+    float* xr = xs + r * stride;
+    for (int c = cq; c < k0pad; c += kGroups) {
+      float v = 0.f;
+      if (live) {
+        if (c < A.Ck) v = pr[(long)c * A.n];
+        else if (c < cin) v = fr[(long)(c - A.Ck) * A.n];
+      }
+      xr[c] = v;
+    }
+  }
+  __syncthreads();
+  // ---- the layers ----
+  int kin = k0pad, cout = 0;
+#pragma unroll
+  for (int l = 0; l < 3; ++l) {
+    if (l < A.mlp.nlayers) {
+      cout = A.mlp.width[l];
+      gm_layer<2>(xs, stride, A.mlp.wt[l], A.mlp.scale[l], A.mlp.shift[l], kin >> 4, (cout + 63) & ~63, w, lane);
+      kin = cout;
+    }
+  }
+  // ---- epilogue (gm_share ended on a barrier): consecutive threads store consecutive i ----
+  if (live) {
+    float* orow = A.out + (b * A.out_channels + A.out_channel0 + k * cout) * A.n + i;
+    const float* xr = xs + r * stride;
+    for (int ch = cq; ch < cout; ch += kGroups) orow[(long)ch * A.n] = xr[ch];
+  }
+}
+
 // One layer's transposed, zero-padded image and its folded vectors (vdetr_group_mlp_pack_f32)
 __global__ __launch_bounds__(kGmThreads) void group_mlp_pack_kernel(const float* __restrict__ w, const float* __restrict__ bias,
                                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -338,4 +406,36 @@ extern "C" int vdetr_fp_mlp_infer_f32(const vdetr_fp_mlp_desc* d, vdetr_stream_t
   A.stride = maxw + 4;
   A.rows = (long)d->B * d->n;
   return gm_launch<2, false>(A, stream, "fp_mlp_infer");
+}
+
+extern "C" int vdetr_pw_mlp_infer_f32(const vdetr_pw_mlp_desc* d, vdetr_stream_t stream) {
+  VDETR_REQUIRE(d != nullptr, "pw_mlp_infer: null descriptor");
+  VDETR_REQUIRE(d->K >= 1 && d->K <= 4, "pw_mlp_infer: K=%d outside [1, 4]", d->K);
+  VDETR_REQUIRE(d->B > 0 && d->n > 0, "pw_mlp_infer: B=%d, n=%d must be positive", d->B, d->n);
+  VDETR_REQUIRE(d->Ck >= 1 && d->C2 >= 0 && (d->C2 > 0) == (d->features2 != nullptr), "pw_mlp_infer: Ck=%d, C2=%d and features2 do not go together",
+                d->Ck, d->C2);
+  VDETR_REQUIRE(d->mlp.cin == d->Ck + d->C2, "pw_mlp_infer: cin=%d is not Ck=%d + C2=%d", d->mlp.cin, d->Ck, d->C2);
+  int maxw = 0;
+  if (int e = gm_check_mlp(&d->mlp, "pw_mlp_infer", &maxw)) return e;
+  const long lim = 2147483647L, cout = d->mlp.width[d->mlp.nlayers - 1];
+  VDETR_REQUIRE(d->out_channel0 >= 0 && d->out_channels >= 1 && (long)d->out_channel0 + d->K * cout <= d->out_channels,
+                "pw_mlp_infer: out_channel0=%d + K=%d x %ld channels do not fit out_channels=%d", d->out_channel0, d->K, cout, d->out_channels);
+  VDETR_REQUIRE((long)d->K * d->B * d->n <= lim && (long)d->B * d->Ck * d->n <= lim && (long)d->B * d->C2 * d->n <= lim &&
+                    (long)d->B * d->out_channels * d->n <= lim,
+                "pw_mlp_infer: a tensor of 2^31 elements or more");
+  bool operands = d->out != nullptr;
+  for (int k = 0; k < d->K; ++k) operands = operands && d->pooled[k] != nullptr;
+  VDETR_REQUIRE(operands, "pw_mlp_infer: null operand");
+  PwArgs A;
+  A.mlp = d->mlp;
+  A.p0 = d->pooled[0]; A.p1 = d->pooled[1]; A.p2 = d->pooled[2]; A.p3 = d->pooled[3];
+  A.feats2 = d->features2; A.out = d->out;
+  A.n = d->n; A.Ck = d->Ck; A.C2 = d->C2; A.out_channels = d->out_channels; A.out_channel0 = d->out_channel0;
+  A.stride = maxw + 4;
+  A.bn = (long)d->B * d->n;
+  A.rows = A.bn * d->K;
+  const size_t lds = (size_t)32 * A.stride * sizeof(float);
+  if (int e = set_lds(pw_mlp_kernel, lds, "pw_mlp_infer")) return e;
+  hipLaunchKernelGGL(pw_mlp_kernel, dim3(ceil_div(A.rows, 32)), dim3(kGmThreads), lds, (hipStream_t)stream, A);
+  return check_launch("pw_mlp_infer");
 }

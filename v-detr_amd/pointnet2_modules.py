@@ -12,6 +12,8 @@ Two paths:
   Shapes it is not built for take the composition (``_sa_fusable`` / ``_fp_fusable``); a missing kernel is an error, not a
   fallback.  ``FUSED = False`` keeps every call on the composition (A/B runs, parity tests); ``LAST_PATHS`` and each module's
   ``last_paths`` record which path every scale of the last call took, ``FUSED_LAUNCHES`` counts the fused launches.
+  ``PointnetLFPModuleMSG`` adds a third launch: its shared post MLP on every scale's pooled features (``_post_fusable``), up to
+  four scales at a time, written straight into the scales' channel slices; its ``last_paths`` end with that stage's entry.
 
 One deliberate difference from the reference: the constructors work on a COPY of the caller's ``mlp`` / ``mlps`` lists.  The
 reference adds 3 to the caller's first entry in place (``use_xyz``), so building two layers from one list gives the second a wrong
@@ -380,3 +382,80 @@ class PointnetFPModule(nn.Module):
             interpolated = known_feats.expand(*known_feats.size()[0:2], unknown.size(1))
         joint = interpolated if unknow_feats is None else torch.cat([interpolated, unknow_feats], dim=1)  # [B, C2 + C1, n]
         return self.mlp(joint.unsqueeze(-1)).squeeze(-1)
+
+
+# ---- learnable feature propagation ----------------------------------------------------------------------------------------------
+_PW_SCALES = 4  # scales per post-MLP launch (vdetr_pw_mlp_desc.pooled)
+
+
+def _post_fusable(owner, pooled, features2):
+    """the post MLP's layers if one launch per four scales can run it on `pooled` (one [B, Ck, n] per scale) and `features2`"""
+    if not (FUSED and HD.inference(owner) and pooled):
+        return None
+    if not (all(_dense(p) for p in pooled) and (features2 is None or _dense(features2))):
+        return None
+    B, Ck, n = pooled[0].shape
+    if any(p.shape != pooled[0].shape for p in pooled) or B * n == 0:
+        return None
+    C2 = 0
+    if features2 is not None:
+        if features2.dim() != 3 or features2.shape[0] != B or features2.shape[2] != n or features2.shape[1] == 0:
+            return None
+        C2 = features2.shape[1]
+    layers = _mlp_layers(owner.post_mlp)
+    if not _mlp_shape_ok(layers, Ck + C2):
+        return None
+    if max(B * max(Ck, C2) * n, len(pooled) * B * layers[-1][0].out_channels * n) >= _LIMIT:
+        return None
+    return layers
+
+
+def _post_fused(owner, layers, pooled, features2):
+    """concat(pooled_k, features2) -> post MLP for every scale k, written to its channel slice: [B, K post_mlp[-1], n]"""
+    global FUSED_LAUNCHES
+    ent = packed_mlp(owner, "post", layers)
+    B, Ck, n = pooled[0].shape
+    K, P = len(pooled), ent["cout"]
+    out = torch.empty((B, K * P, n), dtype=torch.float32, device=pooled[0].device)
+    for k0 in range(0, K, _PW_SCALES):
+        chunk = pooled[k0:k0 + _PW_SCALES]
+        d = L.PwMlpDesc()
+        d.B, d.n, d.K, d.Ck = B, n, len(chunk), Ck
+        d.C2 = 0 if features2 is None else features2.shape[1]
+        d.out_channels, d.out_channel0 = K * P, k0 * P
+        for j, p in enumerate(chunk):
+            d.pooled[j] = p.data_ptr()
+        d.features2 = features2.data_ptr() if features2 is not None else None
+        d.out = out.data_ptr()
+        _fill_desc(d.mlp, ent)
+        L.check(L.lib().vdetr_pw_mlp_infer_f32(ctypes.byref(d), L.stream_ptr()), "pw_mlp_infer")
+        FUSED_LAUNCHES += 1
+    return out
+
+
+class PointnetLFPModuleMSG(nn.Module):
+    """Learnable feature propagation: a multi-scale set abstraction of (xyz1, features1) around the GIVEN centres xyz2, then the
+    same ``post_mlp`` on ``concat(pooled_k, features2)`` once per scale, the results concatenated over the scales.  ``post_mlp`` is
+    registered before ``groupers`` / ``mlps`` (the reference's state-dict order); in train mode its BatchNorm sees one batch per
+    scale.  ``last_paths``: one entry per scale, then one for the post MLP.  Works on a copy of ``mlps`` and ``post_mlp``."""
+
+    def __init__(self, *, mlps, radii, nsamples, post_mlp, bn=True, use_xyz=True, sample_uniformly=False):
+        super().__init__()
+        self.post_mlp = pt_utils.SharedMLP(list(post_mlp), bn=bn)
+        self.groupers, self.mlps = _make_scales(False, radii, nsamples, mlps, bn, use_xyz, sample_uniformly)
+
+    def forward(self, xyz2, xyz1, features2, features1):
+        """xyz2 [B, N2, 3] (the centres), xyz1 [B, N1, 3], features2 [B, C2, N2] or None, features1 [B, C1, N1]
+        -> [B, len(mlps) * post_mlp[-1], N2]"""
+        pooled, paths = _scales_forward(self, xyz1, xyz2, features1)
+        layers = _post_fusable(self, pooled, features2)
+        if layers is not None:
+            out = _post_fused(self, layers, pooled, features2)
+            _record(self, paths + ["fused"])
+            return out
+        _record(self, paths + ["composition"])
+        outs = []
+        for p in pooled:  # one call per scale: in train mode the BatchNorm's statistics are each call's own
+            joint = p if features2 is None else torch.cat([p, features2], dim=1)  # [B, mlps[k][-1] + C2, N2]
+            outs.append(self.post_mlp(joint.unsqueeze(-1)))
+        return torch.cat(outs, dim=1).squeeze(-1)
