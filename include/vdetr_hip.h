@@ -1282,6 +1282,49 @@ typedef struct vdetr_sp_gsum_bn_desc {
 } vdetr_sp_gsum_bn_desc;
 int vdetr_sp_gather_sum_bn_act_f32(const vdetr_sp_gsum_bn_desc* d, vdetr_stream_t stream);
 
+/* Pooling of a sparse tensor over a kernel map nbr [K,nout] (vdetr_sp_kernel_map_i32): ME.MinkowskiSumPooling / AvgPooling /
+ * MaxPooling / PoolingTranspose behind models/modules/common.py:192-259.  With N(u) = {k : nbr[k][u] >= 0}:
+ *   mode 0 sum: y[u] = sum over k in N(u), ascending, of x[nbr[k][u]]
+ *   mode 1 avg: that sum times inv_count[u] = 1 / |N(u)| (the neighbours that exist, not K); |N(u)| = 0: y = 0, inv_count = 0
+ *   mode 2 max: per channel the maximum over N(u); arg[u][c] = the lowest k that attains it; N(u) empty: y = 0, arg = -1
+ * The backward is a gather through inv [K,nin] (vdetr_sp_inverse_map_i32 of nbr), ascending k, no float atomics, no memset:
+ *   dx[i] = sum_k dy[inv[k][i]] (* inv_count[inv[k][i]] for avg; only where arg[inv[k][i]][c] == k for max)
+ * Deterministic: two runs agree bit for bit.  C % 4 == 0, 1 <= K <= 127.  nout == 0 (forward) / nin == 0 (backward): no-op. */
+typedef struct vdetr_sp_pool_desc {
+  int32_t K, nout, nin, C, mode;
+  const float* x;     /* [nin,C] (forward) */
+  const int32_t* nbr; /* [K,nout] (forward) */
+  float* y;           /* [nout,C] (forward) */
+  float* inv_count;   /* [nout]: written by the avg forward, read by its backward; NULL otherwise */
+  int8_t* arg;        /* [nout,C]: written by the max forward, read by its backward; NULL otherwise */
+} vdetr_sp_pool_desc;
+int vdetr_sp_pool_fwd_f32(const vdetr_sp_pool_desc* d, vdetr_stream_t stream);
+int vdetr_sp_pool_bwd_f32(const vdetr_sp_pool_desc* d, const int32_t* inv, const float* dy, float* dx, vdetr_stream_t stream);
+
+/* InstanceNorm over the point-major table [N,C] of a sparse tensor (ME.MinkowskiInstanceNorm; models/mink_resnet.py with
+ * stem_bn = False, models/modules/common.py:24-30): per scene s (rows seg[s] .. seg[s+1], key order keeps them contiguous) and
+ * channel,  y = (x - mean_s) * rsqrt(var_s + eps) * gamma + beta  with the biased variance over the scene's rows.
+ * seg [nseg+1] i32 lives on the DEVICE (ascending, seg[nseg] = N); a scene without rows is skipped, a scene of one row gives beta.
+ * Forward: two launches ((count, mean, M2) partials cut at scene boundaries; every workgroup of the second merges its scene's
+ * partials in index order with Chan's formula and writes y).  save_mean / save_invstd [nseg,C] are written for the backward
+ * (rows of empty scenes are left untouched).  Backward: three launches (partials of sum g, sum g xhat; dx; dgamma / dbeta).
+ * Deterministic, no float atomics, no host read.  C % 4 == 0, C <= 1024.  workspace: vdetr_sp_inorm_workspace_bytes(N, C, nseg),
+ * shared by forward and backward.  gamma / beta [C] may be NULL (1 / 0). */
+typedef struct vdetr_sp_inorm_desc {
+  int32_t N, C, nseg;
+  float eps;
+  const float* x;
+  const int32_t* seg;
+  const float *gamma, *beta;
+  float *y, *save_mean, *save_invstd;
+  void* workspace;
+} vdetr_sp_inorm_desc;
+size_t vdetr_sp_inorm_workspace_bytes(int N, int C, int nseg);
+int vdetr_sp_inorm_fwd_f32(const vdetr_sp_inorm_desc* d, vdetr_stream_t stream);
+/* dx [N,C] (or NULL), dgamma / dbeta [C] (or NULL) from dy [N,C], the forward's x, save_mean, save_invstd (y is not read) */
+int vdetr_sp_inorm_bwd_f32(const vdetr_sp_inorm_desc* d, const float* dy, float* dx, float* dgamma, float* dbeta,
+                           vdetr_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Fixed coordinate embeddings — PositionEmbeddingCoordsSine (models/position_embedding.py:21-148); one launch each.
  *   xyz (b,n,3); range_min / range_max (b,3) = the scene extent for `normalize=True` (shift_scale_points,

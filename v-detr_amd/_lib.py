@@ -386,6 +386,23 @@ class SpGsumBnDesc(ctypes.Structure):
                                          "post_add", "out")])
 
 
+VDETR_POOL_SUM, VDETR_POOL_AVG, VDETR_POOL_MAX = 0, 1, 2
+
+
+class SpPoolDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_pool_desc``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("K", "nout", "nin", "C", "mode")] +
+                [(n, c_void_p) for n in ("x", "nbr", "y", "inv_count", "arg")])
+
+
+class SpInormDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_inorm_desc``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("N", "C", "nseg")] + [("eps", c_float)] +
+                [(n, c_void_p) for n in ("x", "seg", "gamma", "beta", "y", "save_mean", "save_invstd", "workspace")])
+
+
 # name -> (restype, argtypes); must list every symbol of include/vdetr_hip.h (tests check this)
 _SIGNATURES = {
     "vdetr_abi_version": (c_int, []),
@@ -510,6 +527,11 @@ _SIGNATURES = {
     "vdetr_sp_bn_workspace_bytes": (c_size_t, [c_int, c_int]),
     "vdetr_sp_bn_act_fwd_f32": (c_int, [ctypes.POINTER(SpBnDesc), c_void_p]),
     "vdetr_sp_bn_act_bwd_f32": (c_int, [ctypes.POINTER(SpBnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vdetr_sp_pool_fwd_f32": (c_int, [ctypes.POINTER(SpPoolDesc), c_void_p]),
+    "vdetr_sp_pool_bwd_f32": (c_int, [ctypes.POINTER(SpPoolDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vdetr_sp_inorm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vdetr_sp_inorm_fwd_f32": (c_int, [ctypes.POINTER(SpInormDesc), c_void_p]),
+    "vdetr_sp_inorm_bwd_f32": (c_int, [ctypes.POINTER(SpInormDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vdetr_rb_transpose_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vdetr_rb_qkv_f32": (c_int, [ctypes.POINTER(RbQkvDesc), c_void_p]),
     "vdetr_rb_proj_q_f32": (c_int, [ctypes.POINTER(RbProjQDesc), c_void_p]),

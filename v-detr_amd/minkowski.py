@@ -10,14 +10,19 @@ MinkowskiEngine is NOT under /root/reference (un-vendored): semantics follow its
   * a transposed convolution with stride 2 divides the tensor stride; ``MinkowskiConvolutionTranspose`` writes the sites
     that already exist at that stride in the coordinate manager, ``MinkowskiGenerativeConvolutionTranspose`` generates
     every child site;
+  * kernels other than the cube (``RegionType``, ``KernelGenerator``: cross, custom, dilation), the pooling layers and
+    ``MinkowskiInstanceNorm`` serve the reference's module library (models/modules/, here ``vdetr_amd.modules``): DESIGN 6.10 says
+    which of their conventions (the cross's offset order, ``MinkowskiAvgUnpooling``) are this package's own;
   * duplicated input coordinates keep one feature row (here: the first in input order), sites are held in key order.
 The ORDER of the sites of a MinkowskiEngine tensor is an implementation detail of its hash map; here it is ascending
 (batch, x, y, z).  Parity against the MinkowskiEngine binary is unpinned; ``oracle/sparse_oracle.py`` pins the arithmetic
 against torch's dense convolutions.
 """
+import enum
 import math
 import threading
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -86,18 +91,123 @@ def _region_offsets(kernel_size):
     return [(x, y, z) for z in r for y in r for x in r]  # x fastest
 
 
+class RegionType(enum.Enum):
+    """ME.RegionType: the shape of a kernel's neighbourhood"""
+    HYPER_CUBE = 0
+    HYPER_CROSS = 1
+    CUSTOM = 2
+
+
+def _triple(value, name):
+    if isinstance(value, (int, np.integer)):
+        return (int(value),) * 3
+    value = tuple(int(v) for v in value)
+    if len(value) != 3:
+        raise NotImplementedError(f"{name} {value}: three spatial dimensions only")
+    return value
+
+
+def _axis_range(k):
+    return range(-(k // 2), k // 2 + 1) if k % 2 else range(k)
+
+
+class KernelGenerator:
+    """ME.KernelGenerator for three spatial dimensions: the offsets of a kernel, in a FIXED order (``kernel[k]`` of a checkpoint
+    belongs to ``offsets[k]``), in units of dilation x tensor stride:
+      HYPER_CUBE   ``_region_offsets`` per axis, x fastest: an odd size k covers -(k//2) .. k//2, an even size 0 .. k-1;
+      HYPER_CROSS  odd sizes only: the centre, then for axis x, y, z and distance d = 1 .. k//2: -d, then +d (volume
+                   1 + sum(k_a - 1); this order is this package's own, MinkowskiEngine's is not pinned: DESIGN 6.10);
+      CUSTOM       ``region_offsets`` [K, 3] as given.
+    ``stride > 1`` together with ``dilation > 1`` raises ValueError."""
+
+    def __init__(self, kernel_size=-1, stride=1, dilation=1, is_transpose=False, region_type=RegionType.HYPER_CUBE,
+                 region_offsets=None, expand_coordinates=False, axis_types=None, dimension=-1):
+        if dimension != 3:
+            raise NotImplementedError(f"KernelGenerator: dimension {dimension} (three spatial dimensions only)")
+        if axis_types is not None:
+            axis_types = list(axis_types)
+            if len(axis_types) != 3 or any(a != axis_types[0] for a in axis_types):
+                raise NotImplementedError("KernelGenerator: mixed axis_types (one region type for all three axes only)")
+            region_type = axis_types[0]
+        self.region_type = RegionType(region_type) if not isinstance(region_type, RegionType) else region_type
+        self.kernel_size, self.kernel_stride = _triple(kernel_size, "kernel_size"), _triple(stride, "stride")
+        self.kernel_dilation = _triple(dilation, "dilation")
+        self.is_transpose, self.expand_coordinates, self.axis_types, self.dimension = is_transpose, expand_coordinates, axis_types, 3
+        if max(self.kernel_stride) > 1 and max(self.kernel_dilation) > 1:
+            raise ValueError(f"KernelGenerator: stride {self.kernel_stride} together with dilation {self.kernel_dilation}")
+        if min(self.kernel_stride) < 1 or min(self.kernel_dilation) < 1:
+            raise ValueError("KernelGenerator: stride and dilation must be positive")
+        ks = self.kernel_size
+        if self.region_type is RegionType.CUSTOM:
+            if region_offsets is None:
+                raise ValueError("KernelGenerator: RegionType.CUSTOM needs region_offsets [K, 3]")
+            rows = region_offsets.tolist() if hasattr(region_offsets, "tolist") else region_offsets
+            self.offsets = [tuple(int(v) for v in row) for row in rows]
+            if not self.offsets or any(len(o) != 3 for o in self.offsets):
+                raise ValueError("KernelGenerator: region_offsets must be [K, 3] with K >= 1")
+        elif min(ks) < 1:
+            raise ValueError(f"KernelGenerator: kernel_size {ks} must be positive")
+        elif self.region_type is RegionType.HYPER_CUBE:
+            self.offsets = [(x, y, z) for z in _axis_range(ks[2]) for y in _axis_range(ks[1]) for x in _axis_range(ks[0])]
+        else:
+            if any(k % 2 == 0 for k in ks):
+                raise ValueError(f"KernelGenerator: a HYPER_CROSS region needs odd sizes, not {ks}")
+            self.offsets = [(0, 0, 0)]
+            for axis in range(3):
+                for d in range(1, ks[axis] // 2 + 1):
+                    for sign in (-1, 1):
+                        self.offsets.append(tuple(sign * d if a == axis else 0 for a in range(3)))
+        self.kernel_volume = len(self.offsets)
+
+    def scaled_offsets(self):
+        """the offsets times the dilation, per axis: what a kernel map multiplies by the tensor stride"""
+        d = self.kernel_dilation
+        return tuple((x * d[0], y * d[1], z * d[2]) for x, y, z in self.offsets)
+
+
+class _Offsets(tuple):
+    """offsets already in the canonical form (a tuple of int 3-tuples), hashed once: what the layers hand to the coordinate manager
+    at every forward (equal to, and hashing like, the plain tuple of the same offsets)"""
+
+    def __new__(cls, offsets):
+        self = super().__new__(cls, offsets)
+        self._hash = tuple.__hash__(self)
+        return self
+
+    def __hash__(self):
+        return self._hash
+
+
+def _kernel_offsets(kernel):
+    """what ``CoordinateManager.kernel_map`` / ``generated`` accept as a kernel -> its offsets as a tuple of 3-tuples: a
+    KernelGenerator, a cube's size (an int or one size per axis), or the offsets themselves"""
+    if isinstance(kernel, _Offsets):
+        return kernel
+    if isinstance(kernel, KernelGenerator):
+        return kernel.scaled_offsets()
+    if isinstance(kernel, (int, np.integer)):
+        return tuple(_region_offsets(int(kernel)))
+    kernel = tuple(kernel)
+    if kernel and isinstance(kernel[0], (tuple, list)):
+        return tuple(tuple(int(v) for v in o) for o in kernel)
+    return KernelGenerator(kernel, dimension=3).scaled_offsets()
+
+
 class CoordinateManager:
     """Sites per tensor stride + cached kernel maps of one batch (geometry only: no gradients flow through it)."""
 
     def __init__(self, device):
         self.device = device
         self.keys = {}    # tensor_stride -> canonical sorted int64 keys of that stride
-        self.maps = {}    # (in key set, out key set, strides, kernel_size, transposed) -> (nbr [K,Nout], inv [K,Nin])
+        self.maps = {}    # (in key set, out key set, strides, kernel offsets, transposed) -> (nbr [K,Nout], inv [K,Nin], plan)
+        self.num_scenes = None  # batch size: read once, with the coordinate range, when the points are inserted
 
     def insert_points(self, coordinates):
         """raw integer coordinates [N,4] -> the sites of tensor stride 1 (+ ``unique_index``: the input row kept per site:
         the first occurrence in input order; MinkowskiEngine: RANDOM_SUBSAMPLE)"""
         keys_in = S.pack_keys(coordinates)
+        # (pack_keys has just read the coordinate range back: the one place where the scene count may be read as well)
+        self.num_scenes = int(coordinates[:, 0].max()) + 1 if coordinates.shape[0] else 0
         keys, inverse = torch.unique(keys_in, return_inverse=True)
         first = torch.full((keys.shape[0],), keys_in.shape[0], dtype=torch.int64, device=keys.device)
         first.scatter_reduce_(0, inverse, torch.arange(keys_in.shape[0], device=keys.device), reduce="amin")
@@ -121,17 +231,22 @@ class CoordinateManager:
 
     @staticmethod
     def generated(keys, new_ts, kernel_size):
-        """children of every site (generative transposed convolution): a NEW key set at stride `new_ts`"""
+        """children of every site (generative transposed convolution): a NEW key set at stride `new_ts`.  ``kernel_size``:
+        anything ``_kernel_offsets`` takes"""
         c = S.unpack_keys(keys).to(torch.int64)
-        off = torch.tensor(_region_offsets(kernel_size), dtype=torch.int64, device=c.device) * new_ts
+        off = torch.tensor(_kernel_offsets(kernel_size), dtype=torch.int64, device=c.device) * new_ts
         child = c[:, None, :].repeat(1, off.shape[0], 1)
         child[:, :, 1:] += off[None]
         return torch.unique(S.pack_keys(child.reshape(-1, 4)))
 
     def kernel_map(self, in_keys, out_keys, in_ts, out_ts, kernel_size, transposed):
-        key = (in_keys.data_ptr(), out_keys.data_ptr(), in_ts, out_ts, kernel_size, transposed)
+        """(nbr, inv, plan) of a kernel (``_kernel_offsets``: a cube's size, a KernelGenerator or the offsets) between two key
+        sets.  Cached on the OFFSETS: a cube and a cross of one size do not share a plan, a pooling and a convolution of one
+        geometry do."""
+        region = _kernel_offsets(kernel_size)
+        key = (in_keys.data_ptr(), out_keys.data_ptr(), in_ts, out_ts, region, transposed)
         if key not in self.maps:
-            reg = torch.tensor(_region_offsets(kernel_size), dtype=torch.int32)
+            reg = torch.tensor(region, dtype=torch.int32)
             # convolution: output site u reads u + offset * in_stride; transposed: the output (fine) site v = u + offset *
             # out_stride of the input (coarse) site u reads v - offset * out_stride
             offsets = (reg * in_ts if not transposed else -reg * out_ts).to(self.device)
@@ -141,6 +256,30 @@ class CoordinateManager:
             plan = None if S._IM2COL else (S.PairPlan if pairs else S.ConvPlan)(nbr, in_keys.shape[0])
             self.maps[key] = (nbr, inv, plan, in_keys, out_keys)  # key tensors kept alive
         return self.maps[key][:3]
+
+    def pool_map(self, in_keys, out_keys, in_ts, out_ts, kernel_size, transposed):
+        """(nbr, inv) of ``kernel_map`` for a pooling: the same cached map, with the inverse map that the pair path of the
+        convolutions does not keep built on first use"""
+        nbr, inv, _ = self.kernel_map(in_keys, out_keys, in_ts, out_ts, kernel_size, transposed)
+        if inv is None:
+            cache = self.__dict__.setdefault("_pool_inverse", {})
+            key = (nbr.data_ptr(), in_keys.shape[0])
+            if key not in cache:
+                cache[key] = (S.inverse_map(nbr, in_keys.shape[0]), nbr)
+            inv = cache[key][0]
+        return nbr, inv
+
+    def scene_segments(self, keys):
+        """(seg [nseg + 1] int32 on the device, nseg): scene s of a key set is the rows seg[s] .. seg[s+1].  Cached per key set;
+        computed on the device.  nseg is the count read when the points were inserted (a manager filled by hand reads it here,
+        once)."""
+        cache = self.__dict__.setdefault("_scene_segments", {})
+        key = keys.data_ptr()
+        if key not in cache:
+            if self.num_scenes is None:
+                self.num_scenes = int(keys[-1] >> 48) + 1 if keys.numel() else 0
+            cache[key] = (S.scene_segments(keys, self.num_scenes), keys)
+        return cache[key][0], self.num_scenes
 
     def scene_counts(self, keys):
         """sites per batch element of a key set, as a host list.  Cached per key set: it is geometry, and reading it back is a
@@ -279,14 +418,31 @@ class SparseTensor:
 
 
 class MinkowskiConvolution(nn.Module):
-    """ME.MinkowskiConvolution(in, out, kernel_size, stride=1, dilation=1, bias=False, dimension=3)."""
+    """ME.MinkowskiConvolution(in, out, kernel_size, stride=1, dilation=1, bias=False, kernel_generator=None, dimension=3).
+    ``kernel_size`` / ``dilation``: an int or one value per axis; ``kernel_generator`` (KernelGenerator) replaces both and picks
+    the region (cube, cross, custom).  ``kernel`` is [volume, in, out] in the generator's offset order."""
     transposed, generative = False, False
 
-    def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3):
+    def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False, kernel_generator=None,
+                 dimension=3):
         super().__init__()
-        assert dimension == 3 and dilation == 1 and kernel_size > 0
+        assert dimension == 3
+        if kernel_generator is None:
+            kernel_generator = KernelGenerator(kernel_size, stride, dilation, is_transpose=self.transposed, dimension=dimension)
+        else:
+            ks, dl = kernel_generator.kernel_size, kernel_generator.kernel_dilation
+            kernel_size = ks[0] if len(set(ks)) == 1 else ks  # (a cubic size stays an int)
+            dilation = dl[0] if len(set(dl)) == 1 else dl
+        if isinstance(stride, (tuple, list)):
+            if any(s != stride[0] for s in stride):
+                raise NotImplementedError(f"stride {stride}: one stride for all three axes only")
+            stride = int(stride[0])
+        if stride > 1 and max(kernel_generator.kernel_dilation) > 1:
+            raise ValueError(f"stride {stride} together with dilation {kernel_generator.kernel_dilation}")
         self.in_channels, self.out_channels, self.kernel_size, self.stride = in_channels, out_channels, kernel_size, stride
-        kv = kernel_size ** 3
+        self.dilation, self.kernel_generator = dilation, kernel_generator
+        self._offsets = _Offsets(kernel_generator.scaled_offsets())
+        kv = kernel_generator.kernel_volume
         # MinkowskiEngine keeps a plain [in, out] matrix only for the 1x1x1 stride-1 case
         shape = (in_channels, out_channels) if (kv == 1 and stride == 1) else (kv, in_channels, out_channels)
         self.kernel = nn.Parameter(torch.empty(shape))
@@ -306,13 +462,13 @@ class MinkowskiConvolution(nn.Module):
         out_ts = self._out_stride(ts)
         w = self.kernel if self.kernel.dim() == 3 else self.kernel[None]
         if self.generative:
-            out_keys = cm.generated(x.keys, out_ts, self.kernel_size)
+            out_keys = cm.generated(x.keys, out_ts, self._offsets)
         elif self.transposed:
             assert out_ts in cm.keys, "MinkowskiConvolutionTranspose needs existing sites at the output stride"
             out_keys = cm.keys[out_ts]
         else:
             out_keys = x.keys if out_ts == ts else cm.strided(x.keys, ts, out_ts)
-        nbr, inv, plan = cm.kernel_map(x.keys, out_keys, ts, out_ts, self.kernel_size, self.transposed)
+        nbr, inv, plan = cm.kernel_map(x.keys, out_keys, ts, out_ts, self._offsets, self.transposed)
         if _geometry_only():
             if hasattr(plan, "request_wgrad"):  # the weight-gradient chunk table of this layer's width: built with the geometry
                 plan.request_wgrad(w.shape[1], w.shape[2])
@@ -378,13 +534,76 @@ class MinkowskiInstanceNorm(nn.Module):
     def forward(self, x):
         if _geometry_only():
             return x
-        b = x.keys >> 48
-        nb = int(b.max()) + 1
-        cnt = torch.bincount(b, minlength=nb).clamp(min=1).to(x.F.dtype)[:, None]
-        mean = torch.zeros((nb, x.F.shape[1]), dtype=x.F.dtype, device=x.F.device).index_add_(0, b, x.F) / cnt
-        d = x.F - mean[b]
-        var = torch.zeros_like(mean).index_add_(0, b, d * d) / cnt
-        return x._like(d / torch.sqrt(var[b] + self.eps) * self.weight + self.bias)
+        seg, nseg = x.coordinate_manager.scene_segments(x.keys)  # geometry: cached per key set, on the device
+        return x._like(S.instance_norm(x.F.contiguous(), seg, nseg, self.weight, self.bias, self.eps))
+
+
+class _MinkowskiPooling(nn.Module):
+    """Pooling over a kernel region: the output sites are those of a convolution of the same kernel and stride (the same sites
+    at stride 1, ``cm.strided`` above it), the map is the coordinate manager's, shared with such a convolution."""
+    mode, transposed = None, False
+
+    def __init__(self, kernel_size, stride=1, dilation=1, kernel_generator=None, dimension=3):
+        super().__init__()
+        assert dimension == 3
+        if kernel_generator is None:
+            kernel_generator = KernelGenerator(kernel_size, stride, dilation, is_transpose=self.transposed, dimension=dimension)
+        if isinstance(stride, (tuple, list)):
+            if any(s != stride[0] for s in stride):
+                raise NotImplementedError(f"stride {stride}: one stride for all three axes only")
+            stride = int(stride[0])
+        if stride > 1 and max(kernel_generator.kernel_dilation) > 1:
+            raise ValueError(f"stride {stride} together with dilation {kernel_generator.kernel_dilation}")
+        self.kernel_size, self.stride, self.dilation, self.kernel_generator = kernel_size, stride, dilation, kernel_generator
+        self._offsets = _Offsets(kernel_generator.scaled_offsets())
+
+    def _sites(self, x):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        if not self.transposed:
+            out_ts = ts * self.stride
+            return out_ts, (x.keys if out_ts == ts else cm.strided(x.keys, ts, out_ts))
+        assert ts % self.stride == 0, "transposed pooling below tensor stride 1"
+        out_ts = ts // self.stride
+        assert out_ts in cm.keys, f"{type(self).__name__} needs existing sites at the output stride"
+        return out_ts, cm.keys[out_ts]
+
+    def forward(self, x):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        out_ts, out_keys = self._sites(x)
+        if _geometry_only():
+            cm.kernel_map(x.keys, out_keys, ts, out_ts, self._offsets, self.transposed)
+            return SparseTensor(x.F.new_empty((out_keys.shape[0], x.F.shape[1])), tensor_stride=out_ts, coordinate_manager=cm,
+                                keys=out_keys)
+        nbr, inv = cm.pool_map(x.keys, out_keys, ts, out_ts, self._offsets, self.transposed)
+        return SparseTensor(S.sparse_pool(x.F.contiguous(), nbr, inv, self.mode), tensor_stride=out_ts, coordinate_manager=cm,
+                            keys=out_keys)
+
+
+class MinkowskiSumPooling(_MinkowskiPooling):
+    """ME.MinkowskiSumPooling: the sum over the neighbours that exist"""
+    mode = "sum"
+
+
+class MinkowskiAvgPooling(_MinkowskiPooling):
+    """ME.MinkowskiAvgPooling: that sum divided by the number of neighbours that exist (not by the kernel volume)"""
+    mode = "avg"
+
+
+class MinkowskiMaxPooling(_MinkowskiPooling):
+    """ME.MinkowskiMaxPooling: per channel the maximum over the neighbours that exist (ties: the lowest kernel index)"""
+    mode = "max"
+
+
+class MinkowskiPoolingTranspose(_MinkowskiPooling):
+    """ME.MinkowskiPoolingTranspose: the sum over the transposed map onto the existing sites of the output stride, exactly where
+    MinkowskiConvolutionTranspose lands"""
+    mode, transposed = "sum", True
+
+
+class MinkowskiAvgUnpooling(_MinkowskiPooling):
+    """MinkowskiPoolingTranspose with every output row divided by the number of input rows that reach it.  (The reference's
+    ``avg_unpool`` names a class MinkowskiEngine's master no longer has: this definition is this package's own)"""
+    mode, transposed = "avg", True
 
 
 class _Pointwise(nn.Module):

@@ -664,6 +664,147 @@ def gather_sum_bn_act(y, slot, bn, act=None, residual=None, post_add=None, conv_
     return out
 
 
+POOL_MODES = {"sum": L.VDETR_POOL_SUM, "avg": L.VDETR_POOL_AVG, "max": L.VDETR_POOL_MAX}
+
+
+class _SparsePoolFn(Function):
+    """y [Nout, C] = sum / average / maximum of feats[nbr[k, u]] over the neighbours that exist (csrc/sparse_pool.hip)."""
+
+    @staticmethod
+    def forward(ctx, feats, nbr, inv, mode):
+        K, nout = nbr.shape
+        nin, C = feats.shape
+        dev = feats.device
+        d = L.SpPoolDesc()
+        d.K, d.nout, d.nin, d.C, d.mode = K, nout, nin, C, mode
+        y = torch.empty((nout, C), dtype=torch.float32, device=dev)
+        inv_count = torch.empty(nout, dtype=torch.float32, device=dev) if mode == L.VDETR_POOL_AVG else None
+        arg = torch.empty((nout, C), dtype=torch.int8, device=dev) if mode == L.VDETR_POOL_MAX else None
+        d.x, d.nbr, d.y = feats.data_ptr(), nbr.data_ptr(), y.data_ptr()
+        d.inv_count, d.arg = L.ptr(inv_count).value, L.ptr(arg).value
+        L.check(L.lib().vdetr_sp_pool_fwd_f32(ctypes.byref(d), L.stream_ptr()), "sp_pool_fwd")
+        ctx.save_for_backward(inv, inv_count, arg)
+        ctx.cfg = (K, nout, nin, C, mode)
+        ctx.mark_non_differentiable(*(t for t in (inv_count, arg) if t is not None))
+        return y, inv_count, arg
+
+    @staticmethod
+    def backward(ctx, dy, _dcount, _darg):
+        inv, inv_count, arg = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        return _sparse_pool_backward(dy.contiguous(), inv, ctx.cfg, inv_count, arg), None, None, None
+
+
+def _sparse_pool_backward(dy, inv, cfg, inv_count, arg):
+    """the backward launch of ``_SparsePoolFn`` (cfg = (K, nout, nin, C, mode)): dx [Nin, C]"""
+    K, nout, nin, C, mode = cfg
+    d = L.SpPoolDesc()
+    d.K, d.nout, d.nin, d.C, d.mode = K, nout, nin, C, mode
+    d.inv_count, d.arg = L.ptr(inv_count).value, L.ptr(arg).value
+    dx = torch.empty((nin, C), dtype=torch.float32, device=dy.device)
+    L.check(L.lib().vdetr_sp_pool_bwd_f32(ctypes.byref(d), L.ptr(inv), L.ptr(dy), L.ptr(dx), L.stream_ptr()), "sp_pool_bwd")
+    return dx
+
+
+def sparse_pool(feats, nbr, inv, mode, return_aux=False):
+    """Pooling over a kernel map: feats [Nin, C] (contiguous fp32 on the device, C % 4 == 0), nbr [K, Nout] (``kernel_map``),
+    inv [K, Nin] (``inverse_map(nbr, Nin)``; None: built here), mode "sum" | "avg" | "max" -> y [Nout, C].  avg divides by the
+    neighbours that exist; a site without any gives 0 in every mode and passes no gradient.  One launch forward, one backward (a
+    gather through ``inv``): deterministic.  ``return_aux``: also (inv_count [Nout] or None, arg [Nout, C] int8 or None)."""
+    L.require_gpu(feats, "feats")
+    L.require_float(feats, "feats")
+    L.require_contiguous(feats, "feats")
+    L.require_gpu(nbr, "nbr")
+    L.require_int(nbr, "nbr")
+    L.require_contiguous(nbr, "nbr")
+    if mode not in POOL_MODES:
+        raise ValueError(f"sparse_pool: mode {mode!r} (sum, avg, max)")
+    if feats.dim() != 2 or nbr.dim() != 2:
+        raise RuntimeError("sparse_pool: feats must be [Nin, C] and nbr [K, Nout]")
+    if inv is None:
+        inv = inverse_map(nbr, feats.shape[0])
+    L.require_gpu(inv, "inv")
+    L.require_int(inv, "inv")
+    L.require_contiguous(inv, "inv")
+    if tuple(inv.shape) != (nbr.shape[0], feats.shape[0]):
+        raise RuntimeError(f"sparse_pool: inv is {tuple(inv.shape)}, expected {(nbr.shape[0], feats.shape[0])}")
+    y, inv_count, arg = _SparsePoolFn.apply(feats, nbr, inv, POOL_MODES[mode])
+    return (y, inv_count, arg) if return_aux else y
+
+
+class _SpInstanceNormFn(Function):
+    """y = (x - mean_s) * rsqrt(var_s + eps) * gamma + beta per scene s = rows seg[s] .. seg[s+1] (csrc/sp_inorm.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, seg, nseg, gamma, beta, eps):
+        N, C = x.shape
+        lib = L.lib()
+        d = L.SpInormDesc()
+        d.N, d.C, d.nseg, d.eps = N, C, nseg, float(eps)
+        y = torch.empty_like(x)
+        save_mean = torch.empty((max(nseg, 1), C), dtype=torch.float32, device=x.device)
+        save_invstd = torch.empty((max(nseg, 1), C), dtype=torch.float32, device=x.device)
+        ws = L.workspace(lib.vdetr_sp_inorm_workspace_bytes(N, C, nseg), x.device)
+        g = gamma.detach().reshape(-1).contiguous() if gamma is not None else None
+        b = beta.detach().reshape(-1).contiguous() if beta is not None else None
+        d.x, d.seg, d.gamma, d.beta = x.data_ptr(), seg.data_ptr(), L.ptr(g).value, L.ptr(b).value
+        d.y, d.save_mean, d.save_invstd, d.workspace = y.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), ws.data_ptr()
+        L.check(lib.vdetr_sp_inorm_fwd_f32(ctypes.byref(d), L.stream_ptr()), "sp_inorm_fwd")
+        ctx.save_for_backward(x, seg, g, save_mean, save_invstd)
+        ctx.cfg = (nseg, float(eps), None if gamma is None else gamma.shape, None if beta is None else beta.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, seg, g, save_mean, save_invstd = ctx.saved_tensors
+        nseg, eps, gshape, bshape = ctx.cfg
+        N, C = x.shape
+        lib = L.lib()
+        dy = dy.contiguous()
+        d = L.SpInormDesc()
+        d.N, d.C, d.nseg, d.eps = N, C, nseg, eps
+        ws = L.workspace(lib.vdetr_sp_inorm_workspace_bytes(N, C, nseg), x.device)
+        d.x, d.seg, d.gamma = x.data_ptr(), seg.data_ptr(), L.ptr(g).value
+        d.save_mean, d.save_invstd, d.workspace = save_mean.data_ptr(), save_invstd.data_ptr(), ws.data_ptr()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        # (a table without rows launches nothing: its parameter gradients are zeros)
+        new = torch.empty if N and nseg else torch.zeros
+        dgamma = new(C, dtype=torch.float32, device=x.device) if gshape is not None and ctx.needs_input_grad[3] else None
+        dbeta = new(C, dtype=torch.float32, device=x.device) if bshape is not None and ctx.needs_input_grad[4] else None
+        L.check(lib.vdetr_sp_inorm_bwd_f32(ctypes.byref(d), L.ptr(dy), L.ptr(dx), L.ptr(dgamma), L.ptr(dbeta), L.stream_ptr()),
+                "sp_inorm_bwd")
+        return (dx, None, None, dgamma.reshape(gshape) if dgamma is not None else None,
+                dbeta.reshape(bshape) if dbeta is not None else None, None)
+
+
+def scene_segments(keys, nseg):
+    """seg [nseg + 1] int32 on the device: scene s of a sorted key vector is the rows seg[s] .. seg[s+1].  No host read."""
+    bounds = torch.arange(nseg + 1, dtype=torch.int64, device=keys.device) << 48
+    return torch.searchsorted(keys, bounds).to(torch.int32)
+
+
+def instance_norm(x, seg, nseg, weight=None, bias=None, eps=1e-6):
+    """InstanceNorm of a sparse tensor's table x [N, C] (contiguous fp32 on the device, C % 4 == 0, C <= 1024) over the scenes
+    ``seg`` [nseg + 1] int32 (``scene_segments``; device): per scene and channel, biased variance.  weight / bias [C] or [1, C].
+    Two launches forward, three backward; deterministic; nothing is read back by the host."""
+    L.require_gpu(x, "x")
+    L.require_float(x, "x")
+    L.require_contiguous(x, "x")
+    L.require_gpu(seg, "seg")
+    L.require_int(seg, "seg")
+    L.require_contiguous(seg, "seg")
+    if x.dim() != 2 or seg.numel() != nseg + 1:
+        raise RuntimeError(f"instance_norm: x must be [N, C] and seg hold nseg + 1 = {nseg + 1} offsets (it holds {seg.numel()})")
+    for name, t in (("weight", weight), ("bias", bias)):
+        if t is not None:
+            L.require_gpu(t, name)
+            L.require_float(t, name)
+            if t.numel() != x.shape[1]:
+                raise RuntimeError(f"instance_norm: {name} has {t.numel()} elements, expected {x.shape[1]}")
+    return _SpInstanceNormFn.apply(x, seg, int(nseg), weight, bias, eps)
+
+
 _MODE = os.environ.get("VDETR_SP_MODE", "pairs")  # pairs (fused kernels) | plan (batched library GEMMs) | im2col
 _IM2COL = _MODE == "im2col" or os.environ.get("VDETR_SP_IM2COL", "0") == "1"  # A/B switch: one dense im2col GEMM per layer instead of the plan
 
