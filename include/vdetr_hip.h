@@ -1325,6 +1325,68 @@ int vdetr_sp_inorm_fwd_f32(const vdetr_sp_inorm_desc* d, vdetr_stream_t stream);
 int vdetr_sp_inorm_bwd_f32(const vdetr_sp_inorm_desc* d, const float* dy, float* dx, float* dgamma, float* dbeta,
                            vdetr_stream_t stream);
 
+/* Sparse tensors on DIFFERENT key sets: the skip add of the generative neck (models/model_vdetr.py:271 with
+ * woexpand_conv = False) and MinkowskiPruning.  Keys are the sorted unique int64 keys of vdetr_sp_kernel_map_i32.
+ *
+ * Union map of a [na] and b [nb]: u = the sorted union, row_a [na] / row_b [nb] = the position of every key in u, src_a / src_b =
+ * per row of u the row of a / b that holds its key, or -1.  The size nu of the union is data: u, src_a and src_b are allocated
+ * at the bound na + nb, their first nu entries are written and nu itself goes to count[0] (device memory), the one word a
+ * caller reads back.  Two launches (flag and count per tile of vdetr_sp_union_tile() keys; scan and fill), nothing waits
+ * between them; no atomics, no memset.  Every output equals np.union1d / np.searchsorted bit for bit.  na + nb < 2^31.
+ * na == 0 and nb == 0 together: no-op (count is left untouched).  Keys that are unsorted or repeated give wrong maps, but no
+ * write outside the buffers.  workspace: vdetr_sp_union_map_workspace_bytes(na, nb). */
+typedef struct vdetr_sp_union_map_desc {
+  int32_t na, nb;
+  const int64_t *a, *b;
+  int64_t* u;             /* [na + nb], nu written */
+  int32_t *row_a, *row_b; /* [na], [nb] */
+  int32_t *src_a, *src_b; /* [na + nb], nu written */
+  int32_t* count;         /* [1]: nu */
+  void* workspace;
+} vdetr_sp_union_map_desc;
+int vdetr_sp_union_tile(void);
+size_t vdetr_sp_union_map_workspace_bytes(int na, int nb);
+int vdetr_sp_union_map_i64(const vdetr_sp_union_map_desc* d, vdetr_stream_t stream);
+
+/* Prune map: the order-preserving compaction of the rows with mask[i] != 0.  kept [nk] = those rows, ascending (np.nonzero);
+ * pos [N] = the position of row i in kept, -1 where dropped; keys_out [nk] = keys[kept].  kept and keys_out are allocated at the
+ * bound N, nk goes to count[0].  The same two launches as the union map.  N == 0: no-op.
+ * workspace: vdetr_sp_prune_map_workspace_bytes(N). */
+typedef struct vdetr_sp_prune_map_desc {
+  int32_t N;
+  const uint8_t* mask; /* [N], one byte per row (torch.bool) */
+  const int64_t* keys; /* [N] */
+  int32_t *kept, *pos; /* [N] (nk written), [N] */
+  int64_t* keys_out;   /* [N], nk written */
+  int32_t* count;      /* [1]: nk */
+  void* workspace;
+} vdetr_sp_prune_map_desc;
+size_t vdetr_sp_prune_map_workspace_bytes(int N);
+int vdetr_sp_prune_map_i64(const vdetr_sp_prune_map_desc* d, vdetr_stream_t stream);
+
+/* y[u] = (src_a[u] >= 0 ? a[src_a[u]] : 0) + sign * (src_b[u] >= 0 ? b[src_b[u]] : 0), sign = 1 or -1 (one fp32 add or subtract
+ * of the two selected operands: a missing side is a zero that is selected, never a product, so an infinity stays one).
+ * a [na,C], b [nb,C], y [nu,C] f32, src_a / src_b [nu] i32; C % 4 == 0.  One launch, no memset, no atomics.  nu == 0: no-op;
+ * a / b may be NULL when na / nb is 0. */
+typedef struct vdetr_sp_union_add_desc {
+  int32_t nu, na, nb, C, sign;
+  const float *a, *b;
+  const int32_t *src_a, *src_b;
+  float* y;
+} vdetr_sp_union_add_desc;
+int vdetr_sp_union_add_f32(const vdetr_sp_union_add_desc* d, vdetr_stream_t stream);
+
+/* y[r] = idx[r] >= 0 ? sign * x[idx[r]] : 0 (an exact +0), sign = 1 or -1.  x [nsrc,C], y [nrows,C] f32, idx [nrows] i32;
+ * C % 4 == 0.  The union add's backward (through row_a / row_b), the pruning's forward (through kept) and its backward
+ * (through pos).  One launch.  nrows == 0: no-op; x may be NULL when nsrc is 0 (y is then all zeros). */
+typedef struct vdetr_sp_take_rows_desc {
+  int32_t nrows, nsrc, C, sign;
+  const float* x;
+  const int32_t* idx;
+  float* y;
+} vdetr_sp_take_rows_desc;
+int vdetr_sp_take_rows_f32(const vdetr_sp_take_rows_desc* d, vdetr_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Fixed coordinate embeddings — PositionEmbeddingCoordsSine (models/position_embedding.py:21-148); one launch each.
  *   xyz (b,n,3); range_min / range_max (b,3) = the scene extent for `normalize=True` (shift_scale_points,

@@ -403,6 +403,32 @@ class SpInormDesc(ctypes.Structure):
                 [(n, c_void_p) for n in ("x", "seg", "gamma", "beta", "y", "save_mean", "save_invstd", "workspace")])
 
 
+class SpUnionMapDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_union_map_desc``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("na", "nb")] +
+                [(n, c_void_p) for n in ("a", "b", "u", "row_a", "row_b", "src_a", "src_b", "count", "workspace")])
+
+
+class SpPruneMapDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_prune_map_desc``."""
+
+    _fields_ = [("N", ctypes.c_int32)] + [(n, c_void_p) for n in ("mask", "keys", "kept", "pos", "keys_out", "count", "workspace")]
+
+
+class SpUnionAddDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_union_add_desc``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("nu", "na", "nb", "C", "sign")] +
+                [(n, c_void_p) for n in ("a", "b", "src_a", "src_b", "y")])
+
+
+class SpTakeRowsDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_take_rows_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("nrows", "nsrc", "C", "sign")] + [(n, c_void_p) for n in ("x", "idx", "y")]
+
+
 # name -> (restype, argtypes); must list every symbol of include/vdetr_hip.h (tests check this)
 _SIGNATURES = {
     "vdetr_abi_version": (c_int, []),
@@ -532,6 +558,13 @@ _SIGNATURES = {
     "vdetr_sp_inorm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vdetr_sp_inorm_fwd_f32": (c_int, [ctypes.POINTER(SpInormDesc), c_void_p]),
     "vdetr_sp_inorm_bwd_f32": (c_int, [ctypes.POINTER(SpInormDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vdetr_sp_union_tile": (c_int, []),
+    "vdetr_sp_union_map_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "vdetr_sp_union_map_i64": (c_int, [ctypes.POINTER(SpUnionMapDesc), c_void_p]),
+    "vdetr_sp_prune_map_workspace_bytes": (c_size_t, [c_int]),
+    "vdetr_sp_prune_map_i64": (c_int, [ctypes.POINTER(SpPruneMapDesc), c_void_p]),
+    "vdetr_sp_union_add_f32": (c_int, [ctypes.POINTER(SpUnionAddDesc), c_void_p]),
+    "vdetr_sp_take_rows_f32": (c_int, [ctypes.POINTER(SpTakeRowsDesc), c_void_p]),
     "vdetr_rb_transpose_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vdetr_rb_qkv_f32": (c_int, [ctypes.POINTER(RbQkvDesc), c_void_p]),
     "vdetr_rb_proj_q_f32": (c_int, [ctypes.POINTER(RbProjQDesc), c_void_p]),

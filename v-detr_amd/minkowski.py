@@ -13,6 +13,9 @@ MinkowskiEngine is NOT under /root/reference (un-vendored): semantics follow its
   * kernels other than the cube (``RegionType``, ``KernelGenerator``: cross, custom, dilation), the pooling layers and
     ``MinkowskiInstanceNorm`` serve the reference's module library (models/modules/, here ``vdetr_amd.modules``): DESIGN 6.10 says
     which of their conventions (the cross's offset order, ``MinkowskiAvgUnpooling``) are this package's own;
+  * ``a + b`` / ``a - b`` of tensors on DIFFERENT key sets (the skip add behind a generative convolution) live on the union of the
+    sites, a side without a site counting as zero; ``MinkowskiUnion`` folds ``+``; ``MinkowskiPruning`` keeps the rows of a bool
+    mask in order (DESIGN 6.11: this package's own statement);
   * duplicated input coordinates keep one feature row (here: the first in input order), sites are held in key order.
 The ORDER of the sites of a MinkowskiEngine tensor is an implementation detail of its hash map; here it is ascending
 (batch, x, y, z).  Parity against the MinkowskiEngine binary is unpinned; ``oracle/sparse_oracle.py`` pins the arithmetic
@@ -229,15 +232,29 @@ class CoordinateManager:
             return self.keys[new_ts]
         return self._strided_keys(keys, new_ts)
 
-    @staticmethod
-    def generated(keys, new_ts, kernel_size):
-        """children of every site (generative transposed convolution): a NEW key set at stride `new_ts`.  ``kernel_size``:
-        anything ``_kernel_offsets`` takes"""
-        c = S.unpack_keys(keys).to(torch.int64)
-        off = torch.tensor(_kernel_offsets(kernel_size), dtype=torch.int64, device=c.device) * new_ts
-        child = c[:, None, :].repeat(1, off.shape[0], 1)
-        child[:, :, 1:] += off[None]
-        return torch.unique(S.pack_keys(child.reshape(-1, 4)))
+    def generated(self, keys, new_ts, kernel_size):
+        """children of every site (generative transposed convolution): a NEW, non-canonical key set at stride `new_ts`.
+        ``kernel_size``: anything ``_kernel_offsets`` takes.  Cached per (key set, stride, offsets), so that the forward pass
+        after a ``prepare_geometry`` meets the key tensors its maps were built for."""
+        region = _kernel_offsets(kernel_size)
+        cache = self.__dict__.setdefault("_generated", {})
+        key = (keys.data_ptr(), new_ts, region)
+        if key not in cache:
+            c = S.unpack_keys(keys).to(torch.int64)
+            off = torch.tensor(region, dtype=torch.int64, device=c.device) * new_ts
+            child = c[:, None, :].repeat(1, off.shape[0], 1)
+            child[:, :, 1:] += off[None]
+            cache[key] = (torch.unique(S.pack_keys(child.reshape(-1, 4))), keys)  # the parent key tensor is kept alive
+        return cache[key][0]
+
+    def union_map(self, a_keys, b_keys):
+        """(u, row_a, row_b, src_a, src_b) of ``sparse_ops.union_map`` for two key sets of one stride: the sites of
+        ``a + b`` on different coordinate maps.  Cached per pair of key tensors: it is geometry, and its size is read back once."""
+        cache = self.__dict__.setdefault("_union_maps", {})
+        key = (a_keys.data_ptr(), b_keys.data_ptr())
+        if key not in cache:
+            cache[key] = S.union_map(a_keys, b_keys) + (a_keys, b_keys)  # key tensors kept alive
+        return cache[key][:5]
 
     def kernel_map(self, in_keys, out_keys, in_ts, out_ts, kernel_size, transposed):
         """(nbr, inv, plan) of a kernel (``_kernel_offsets``: a cube's size, a KernelGenerator or the offsets) between two key
@@ -290,7 +307,9 @@ class CoordinateManager:
         if key not in cache:
             b = keys >> 48
             nb = int(b.max()) + 1 if b.numel() else 0
-            cache[key] = (torch.bincount(b, minlength=nb).tolist(), keys)  # the key tensor is kept alive with its entry
+            # (a key set from which MinkowskiPruning took a whole scene still has one entry per scene of the batch)
+            nb = max(nb, self.num_scenes or 0)
+            cache[key] =(torch.bincount(b, minlength=nb).tolist(), keys)  # the key tensor is kept alive with its entry
         return cache[key][0]
 
     def device_tensors(self):
@@ -403,9 +422,36 @@ class SparseTensor:
     def _like(self, features):
         return SparseTensor(features, tensor_stride=self.tensor_stride, coordinate_manager=self.coordinate_manager, keys=self.keys)
 
+    def _same_map(self, other):
+        return self.keys is other.keys or torch.equal(self.keys, other.keys)
+
+    def _on_union(self, other, sign):
+        """self + sign * other on DIFFERENT key sets: the result lives on the union of the two, in key order; a side without a
+        site contributes zero.  Geometry-only: the union map is built and cached, the table is uninitialised."""
+        cm, ts = self.coordinate_manager, self.tensor_stride
+        if other.coordinate_manager is not cm:
+            raise ValueError(f"sparse tensors of different coordinate managers: {cm!r} and {other.coordinate_manager!r}")
+        if other.tensor_stride != ts:
+            raise ValueError(f"sparse tensors of different tensor strides: {ts} and {other.tensor_stride}")
+        ca, cb = self.F.shape[1], other.F.shape[1]
+        if ca != cb:
+            raise ValueError(f"sparse tensors of different channel counts: {ca} and {cb}")
+        u, row_a, row_b, src_a, src_b = cm.union_map(self.keys, other.keys)
+        if _geometry_only():
+            f = self.F.new_empty((u.shape[0], ca))
+        else:
+            f = S.union_add(self.F.contiguous(), other.F.contiguous(), row_a, row_b, src_a, src_b, sign)
+        return SparseTensor(f, tensor_stride=ts, coordinate_manager=cm, keys=u)
+
     def __add__(self, other):
-        assert self.keys is other.keys or torch.equal(self.keys, other.keys), "sparse tensors on different coordinate maps"
+        if not self._same_map(other):
+            return self._on_union(other, 1)
         return self if _geometry_only() else self._like(self.F + other.F)
+
+    def __sub__(self, other):
+        if not self._same_map(other):
+            return self._on_union(other, -1)
+        return self if _geometry_only() else self._like(self.F - other.F)
 
     def decomposed(self):
         """per batch element: (coordinates [n,3] int32, features [n,C]) — key order keeps the scenes contiguous"""
@@ -606,6 +652,40 @@ class MinkowskiAvgUnpooling(_MinkowskiPooling):
     mode, transposed = "avg", True
 
 
+class MinkowskiUnion(nn.Module):
+    """ME.MinkowskiUnion: the sum of two or more sparse tensors of one coordinate manager and tensor stride on the union of their
+    sites — the left fold of ``+``."""
+
+    def forward(self, *inputs):
+        if len(inputs) < 2:
+            raise ValueError(f"MinkowskiUnion: {len(inputs)} input (two or more sparse tensors)")
+        out = inputs[0]
+        for x in inputs[1:]:
+            out = out + x
+        return out
+
+
+class MinkowskiPruning(nn.Module):
+    """ME.MinkowskiPruning: keep the rows of ``x`` whose ``mask`` entry is true, in order, at the same tensor stride and with the
+    same coordinate manager, on a new non-canonical key set (like the generated ones).  ``mask``: bool [N] on x's device, in
+    ``x.F``'s row order.  Backward: a kept row receives its gradient, a dropped one an exact zero.  The mask is DATA: under
+    ``geometry_only`` the module passes x through, and the maps of the layers behind a pruning are built in the real forward."""
+
+    def forward(self, x, mask):
+        if _geometry_only():
+            return x
+        n = x.keys.shape[0]
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool:
+            raise ValueError(f"MinkowskiPruning: the mask must be a bool tensor, not {getattr(mask, 'dtype', type(mask))}")
+        if mask.dim() != 1 or mask.shape[0] != n:
+            raise ValueError(f"MinkowskiPruning: a mask of shape {tuple(mask.shape)} for {n} rows")
+        if mask.device != x.keys.device:
+            raise ValueError(f"MinkowskiPruning: the mask is on {mask.device}, the tensor on {x.keys.device}")
+        kept, pos, keys = S.prune_map(mask.contiguous(), x.keys)
+        return SparseTensor(S.take_rows(x.F.contiguous(), kept, back=pos), tensor_stride=x.tensor_stride,
+                            coordinate_manager=x.coordinate_manager, keys=keys)
+
+
 class _Pointwise(nn.Module):
     kind = None
 
@@ -691,7 +771,9 @@ def fuse_activations(module):
 
 def sequential_add(block, x, skip):
     """``skip + block(x)`` for an nn.Sequential that ends BatchNorm -> folded activation (``fuse_activations``).  Under inference
-    the add is the ``post_add`` of the block's last fused launch; everywhere else it is exactly ``skip + block(x)``."""
+    the add is the ``post_add`` of the block's last fused launch; everywhere else it is exactly ``skip + block(x)``.  A block
+    whose output sites differ from the skip's (a generative up block) still runs its last launch fused, without ``post_add``,
+    and the add is the union add of ``skip + ...``."""
     mods = list(block) if isinstance(block, nn.Sequential) else []
     tail = mods[-2] if len(mods) >= 2 else None
     if not (INFER_FUSED and HD.inference(block)) or _geometry_only() or not isinstance(tail, MinkowskiBatchNorm) \
@@ -699,6 +781,8 @@ def sequential_add(block, x, skip):
         return skip + block(x)
     for m in mods[:-2]:
         x = m(x)
+    if not x._same_map(skip):
+        return skip + mods[-1](tail(x))  # tail records its own launch in LAST_PATHS
     return mods[-1](tail(x, post_add=skip))
 
 

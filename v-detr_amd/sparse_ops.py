@@ -805,6 +805,177 @@ def instance_norm(x, seg, nseg, weight=None, bias=None, eps=1e-6):
     return _SpInstanceNormFn.apply(x, seg, int(nseg), weight, bias, eps)
 
 
+# ---- sparse tensors on different key sets: union add / subtract and pruning (csrc/sparse_union.hip) ------------------
+def union_tile():
+    """keys per workgroup of the two map builders (the tests place their edge cases on its multiples)"""
+    return int(L.lib().vdetr_sp_union_tile())
+
+
+def _require_keys(t, name):
+    L.require_gpu(t, name)
+    L.require_contiguous(t, name)
+    if t.dtype != torch.int64 or t.dim() != 1:
+        raise RuntimeError(f"{name} must be a one-dimensional int64 key tensor (it is {t.dtype}, {tuple(t.shape)})")
+
+
+def union_map(a_keys, b_keys):
+    """The union of two sorted unique key sets (``pack_keys``) with its row maps: (u [nu] int64 ascending, row_a [na], row_b [nb]
+    int32 = the position of every key in u, src_a [nu], src_b [nu] int32 = the row of a / b behind a row of u, or -1).  Equal to
+    np.union1d / np.searchsorted bit for bit.  Two launches and ONE 4-byte read of nu behind them (geometry: the coordinate manager
+    caches the map); u, src_a and src_b are views of buffers of na + nb entries."""
+    _require_keys(a_keys, "a_keys")
+    _require_keys(b_keys, "b_keys")
+    if a_keys.device != b_keys.device:
+        raise RuntimeError(f"union_map: a_keys on {a_keys.device}, b_keys on {b_keys.device}")
+    na, nb, dev = a_keys.shape[0], b_keys.shape[0], a_keys.device
+    if na + nb >= 2 ** 31:
+        raise RuntimeError(f"union_map: {na} + {nb} keys are more than 31 bits hold")
+    u = torch.empty(na + nb, dtype=torch.int64, device=dev)
+    row_a, row_b = (torch.empty(n, dtype=torch.int32, device=dev) for n in (na, nb))
+    src_a, src_b = (torch.empty(na + nb, dtype=torch.int32, device=dev) for _ in range(2))
+    if na + nb == 0:
+        return u, row_a, row_b, src_a, src_b
+    lib = L.lib()
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = L.workspace(lib.vdetr_sp_union_map_workspace_bytes(na, nb), dev)
+    d = L.SpUnionMapDesc()
+    d.na, d.nb = na, nb
+    d.a, d.b, d.u = L.ptr(a_keys).value, L.ptr(b_keys).value, u.data_ptr()
+    d.row_a, d.row_b, d.src_a, d.src_b = L.ptr(row_a).value, L.ptr(row_b).value, src_a.data_ptr(), src_b.data_ptr()
+    d.count, d.workspace = count.data_ptr(), ws.data_ptr()
+    L.check(lib.vdetr_sp_union_map_i64(ctypes.byref(d), L.stream_ptr()), "sp_union_map")
+    nu = int(count)  # the size of the union is data: the one host read
+    return u[:nu], row_a, row_b, src_a[:nu], src_b[:nu]
+
+
+def prune_map(mask, keys):
+    """The order-preserving compaction of the rows with ``mask`` true: (kept [nk] int32 ascending = np.nonzero(mask), pos [N] int32
+    = the position of a row in kept or -1, keys_out [nk] = keys[kept]).  mask [N] bool and keys [N] int64 on the device.  Two
+    launches and one 4-byte read of nk per call: the output shape is data."""
+    _require_keys(keys, "keys")
+    L.require_gpu(mask, "mask")
+    L.require_contiguous(mask, "mask")
+    if mask.dtype != torch.bool:
+        raise RuntimeError(f"mask must be a bool tensor (it is {mask.dtype})")
+    if mask.dim() != 1 or mask.shape[0] != keys.shape[0]:
+        raise RuntimeError(f"prune_map: mask is {tuple(mask.shape)}, expected ({keys.shape[0]},): one entry per row")
+    if mask.device != keys.device:
+        raise RuntimeError(f"prune_map: mask on {mask.device}, keys on {keys.device}")
+    N, dev = keys.shape[0], keys.device
+    kept, pos = (torch.empty(N, dtype=torch.int32, device=dev) for _ in range(2))
+    keys_out = torch.empty(N, dtype=torch.int64, device=dev)
+    if N == 0:
+        return kept, pos, keys_out
+    lib = L.lib()
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = L.workspace(lib.vdetr_sp_prune_map_workspace_bytes(N), dev)
+    d = L.SpPruneMapDesc()
+    d.N, d.mask, d.keys = N, mask.data_ptr(), keys.data_ptr()
+    d.kept, d.pos, d.keys_out, d.count, d.workspace = kept.data_ptr(), pos.data_ptr(), keys_out.data_ptr(), count.data_ptr(), ws.data_ptr()
+    L.check(lib.vdetr_sp_prune_map_i64(ctypes.byref(d), L.stream_ptr()), "sp_prune_map")
+    nk = int(count)
+    return kept[:nk], pos, keys_out[:nk]
+
+
+def _require_table(t, name):
+    L.require_gpu(t, name)
+    L.require_float(t, name)
+    L.require_contiguous(t, name)
+    if t.dim() != 2:
+        raise RuntimeError(f"{name} must be a feature table [N, C] (it is {tuple(t.shape)})")
+
+
+def _require_index(t, name, n=None):
+    L.require_gpu(t, name)
+    L.require_int(t, name)
+    L.require_contiguous(t, name)
+    if t.dim() != 1 or (n is not None and t.shape[0] != n):
+        raise RuntimeError(f"{name} is {tuple(t.shape)}, expected ({'n' if n is None else n},)")
+
+
+def _take_rows(x, idx, sign):
+    nsrc, C = x.shape
+    y = torch.empty((idx.shape[0], C), dtype=torch.float32, device=x.device)
+    d = L.SpTakeRowsDesc()
+    d.nrows, d.nsrc, d.C, d.sign = idx.shape[0], nsrc, C, sign
+    d.x, d.idx, d.y = L.ptr(x).value, L.ptr(idx).value, L.ptr(y).value
+    L.check(L.lib().vdetr_sp_take_rows_f32(ctypes.byref(d), L.stream_ptr()), "sp_take_rows")
+    return y
+
+
+class _TakeRowsFn(Function):
+    """y[r] = sign * x[idx[r]] (0 where idx[r] < 0); backward: the same launch through ``back``, the inverse of ``idx``."""
+
+    @staticmethod
+    def forward(ctx, x, idx, back, sign):
+        ctx.save_for_backward(back)
+        ctx.sign = sign
+        return _take_rows(x, idx, sign)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (back,) = ctx.saved_tensors
+        return _take_rows(dy.contiguous(), back, ctx.sign), None, None, None
+
+
+def take_rows(x, idx, back=None, sign=1):
+    """y [R, C] = sign * x[idx[r]], an exact zero where idx[r] < 0.  x [N, C] contiguous fp32 on the device (C % 4 == 0), idx [R]
+    int32 holding every row of x AT MOST ONCE, sign 1 or -1.  One launch.  Gradients reach x only with ``back`` [N] int32, the
+    inverse of idx (back[i] = the r with idx[r] == i, or -1): the backward is this launch through it (the pruning's kept / pos, the
+    union's src / row)."""
+    _require_table(x, "x")
+    _require_index(idx, "idx")
+    if sign not in (1, -1):
+        raise ValueError(f"take_rows: sign {sign!r} (1 or -1)")
+    if back is None:
+        if x.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("take_rows: gradients of x need `back`, the inverse of idx")
+        return _take_rows(x, idx, sign)
+    _require_index(back, "back", x.shape[0])
+    return _TakeRowsFn.apply(x, idx, back, sign)
+
+
+class _UnionAddFn(Function):
+    """y [nu, C] = a-or-zero + sign * b-or-zero on the union of two key sets; dA = dY[row_a], dB = sign * dY[row_b] (gathers)."""
+
+    @staticmethod
+    def forward(ctx, fa, fb, row_a, row_b, src_a, src_b, sign):
+        nu, C = src_a.shape[0], fa.shape[1]
+        y = torch.empty((nu, C), dtype=torch.float32, device=fa.device)
+        d = L.SpUnionAddDesc()
+        d.nu, d.na, d.nb, d.C, d.sign = nu, fa.shape[0], fb.shape[0], C, sign
+        d.a, d.b, d.src_a, d.src_b, d.y = L.ptr(fa).value, L.ptr(fb).value, L.ptr(src_a).value, L.ptr(src_b).value, L.ptr(y).value
+        L.check(L.lib().vdetr_sp_union_add_f32(ctypes.byref(d), L.stream_ptr()), "sp_union_add")
+        ctx.save_for_backward(row_a, row_b)
+        ctx.sign = sign
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        row_a, row_b = ctx.saved_tensors
+        dy = dy.contiguous()
+        da = _take_rows(dy, row_a, 1) if ctx.needs_input_grad[0] else None
+        db = _take_rows(dy, row_b, ctx.sign) if ctx.needs_input_grad[1] else None
+        return da, db, None, None, None, None, None
+
+
+def union_add(fa, fb, row_a, row_b, src_a, src_b, sign=1):
+    """y [nu, C] on the union of two key sets (``union_map``): row u is fa's row, zero where a has no such site, plus (sign 1) or
+    minus (sign -1) fb's row, likewise — one fp32 add or subtract of two selected operands.  fa [na, C], fb [nb, C] contiguous fp32
+    on the device, C % 4 == 0.  One launch forward, at most two backward (gathers through row_a / row_b); deterministic."""
+    _require_table(fa, "fa")
+    _require_table(fb, "fb")
+    if fa.shape[1] != fb.shape[1]:
+        raise ValueError(f"union_add: {fa.shape[1]} and {fb.shape[1]} channels")
+    if sign not in (1, -1):
+        raise ValueError(f"union_add: sign {sign!r} (1 or -1)")
+    _require_index(row_a, "row_a", fa.shape[0])
+    _require_index(row_b, "row_b", fb.shape[0])
+    _require_index(src_a, "src_a")
+    _require_index(src_b, "src_b", src_a.shape[0])
+    return _UnionAddFn.apply(fa, fb, row_a, row_b, src_a, src_b, sign)
+
+
 _MODE = os.environ.get("VDETR_SP_MODE", "pairs")  # pairs (fused kernels) | plan (batched library GEMMs) | im2col
 _IM2COL = _MODE == "im2col" or os.environ.get("VDETR_SP_IM2COL", "0") == "1"  # A/B switch: one dense im2col GEMM per layer instead of the plan
 
