@@ -1188,6 +1188,60 @@ int vdetr_box3d_iou_pairs_f64(const float* corners_a, int Na, const float* corne
                               vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Device-resident detection store of the evaluation loop (eval_store.hip) — what APCalculator.step
+ * (utils/ap_calculator.py:430-470) keeps per scan as host lists.  One row per kept BOX (not per (box, class)); every array
+ * and the four cursors live in device memory, the caller owns them:
+ *   box_corners [box_capacity,8,3] f32, box_scores [box_capacity,S] f32, box_cls / box_scan [box_capacity] i32,
+ *   box_begin [scan_capacity+1] i32: the boxes of scan s are rows box_begin[s] .. box_begin[s+1]-1,
+ *   gt_corners [gt_capacity,8,3] f32, gt_cls [gt_capacity] i32, gt_begin [scan_capacity+1] i32 likewise,
+ *   counters [4] i32 = boxes, ground-truth boxes, scans, dropped rows (zero-filled by the caller before the first append).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct vdetr_det_store {
+  int32_t box_capacity, gt_capacity, scan_capacity, S;
+  float* box_corners;
+  float* box_scores;
+  int32_t* box_cls;
+  int32_t* box_scan;
+  int32_t* box_begin;
+  float* gt_corners;
+  int32_t* gt_cls;
+  int32_t* gt_begin;
+  int32_t* counters;
+} vdetr_det_store;
+
+/* Appends one batch: the boxes with keep[b,k] != 0 (keep [B,K] u8; corners [B,K,8,3] f32, scores [B,K,S] f32, cls [B,K]
+ * i32) and the ground-truth boxes with gt_present[b,g] != 0 (gt_present [B,G] u8; gt_corners [B,G,8,3] f32, gt_cls [B,G]
+ * i32; G may be 0), scenes in batch order, rows in ascending index: the insertion order of the reference's lists.
+ * scan_base = number of scans appended before (the host knows it: the sum of the earlier B); scan_base + B <= scan_capacity.
+ * The row cursors are read from `counters`, never by the host: a row whose position is at or beyond its capacity is not
+ * written and is counted in counters[3]; the cursors go on counting positions.  Two launches (rows, then cursors), no
+ * float atomics: the same calls give the same bits. */
+int vdetr_det_append_f32(const vdetr_det_store* store, const uint8_t* keep, const float* corners, const float* scores,
+                         const int32_t* cls, const float* gt_corners, const int32_t* gt_cls, const uint8_t* gt_present, int B,
+                         int K, int G, int scan_base, vdetr_stream_t stream);
+
+/* vdetr_box3d_iou_max_f64 with the detections given as (box row, class) pairs of a store: nboxes rows, nscans scans and ngt
+ * ground-truth rows of it are used (the host's copy of the counters).  num_classes = C > 0 (per-class forms, S >= C): box
+ * row r of scan s with j = r - box_begin[s], n_s = box_begin[s+1] - box_begin[s] gives the C detections
+ * d = C box_begin[s] + c n_s + j of class c and score box_scores[r,c] — per scan class-major, the reference's list order
+ * (utils/ap_calculator.py:253-262); P = C nboxes.  num_classes = 0: d = r with box_cls[r] and box_scores[r,0]; P = nboxes.
+ * -> ovmax (P) f64, jmax (P) i32 as vdetr_box3d_iou_max_f64 (jmax = row of the store's gt_corners), det_cls (P) i32,
+ * det_score (P) f32.  The same arithmetic as vdetr_box3d_iou_max_f64, to the bit. */
+int vdetr_box3d_iou_max_idx_f64(const vdetr_det_store* store, int nboxes, int nscans, int ngt, int num_classes, double* ovmax,
+                                int32_t* jmax, int32_t* det_cls, float* det_score, vdetr_stream_t stream);
+
+/* Precision / recall curves and the VOC-12 average precision (utils/eval_det.py:23-56 voc_ap with use_07_metric=False,
+ * :127-141) of C classes at T thresholds in one launch.  tp [T,P] u8: the true-positive flags in ranked order (class-major,
+ * then descending score); seg [C+1] i32: class c owns ranks seg[c] .. seg[c+1]-1; npos [C] i32: its ground-truth boxes.
+ * Per (class, threshold): integer counts of tp and fp, rec = tp / float(npos) (zeros where npos == 0),
+ * prec = tp / max(tp + fp, eps) as one fp64 division each, the precision envelope as a suffix maximum, and the sum of
+ * (rec[i] - rec[i-1]) * envelope[i] in a fixed order (one partial per thread, then a fixed tree).
+ * -> out [T,4,C] f64 = AP, last recall, number of detections, npos (a class without detection reports 0, 0);
+ * rec / prec [T,P] f64 or both NULL. */
+int vdetr_voc_ap_f64(const uint8_t* tp, const int32_t* seg, const int32_t* npos, int T, int P, int C, double* out, double* rec,
+                     double* prec, vdetr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Sparse-convolution backbone: index kernels behind the MinkowskiEngine call sites of the
  * reference (models/mink_resnet.py:38-84 ME.MinkowskiConvolution / BasicBlock, models/model_vdetr.py:141-176
  * MinkowskiConvolution / MinkowskiConvolutionTranspose / MinkowskiGenerativeConvolutionTranspose, :250-280 run_encoder).

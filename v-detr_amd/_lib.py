@@ -429,6 +429,14 @@ class SpTakeRowsDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("nrows", "nsrc", "C", "sign")] + [(n, c_void_p) for n in ("x", "idx", "y")]
 
 
+class DetStore(ctypes.Structure):
+    """Mirror of ``vdetr_det_store``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("box_capacity", "gt_capacity", "scan_capacity", "S")] +
+                [(n, c_void_p) for n in ("box_corners", "box_scores", "box_cls", "box_scan", "box_begin", "gt_corners", "gt_cls",
+                                         "gt_begin", "counters")])
+
+
 # name -> (restype, argtypes); must list every symbol of include/vdetr_hip.h (tests check this)
 _SIGNATURES = {
     "vdetr_abi_version": (c_int, []),
@@ -505,6 +513,9 @@ _SIGNATURES = {
     "vdetr_box3d_iou_max_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
     "vdetr_box3d_iou_pairs_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "vdetr_det_append_f32": (c_int, [ctypes.POINTER(DetStore)] + [c_void_p] * 7 + [c_int] * 4 + [c_void_p]),
+    "vdetr_box3d_iou_max_idx_f64": (c_int, [ctypes.POINTER(DetStore)] + [c_int] * 4 + [c_void_p] * 5),
+    "vdetr_voc_ap_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vdetr_morton_sort_max": (c_int, []),
     "vdetr_morton_order_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vdetr_pack_chunk_floats": (c_int, []),

@@ -100,24 +100,32 @@ def prediction_masks(predicted_boxes, sem_cls_probs, objectness_probs, angle_pro
     return dict(pred_mask=pred_mask, keep=keep, pred_sem_cls=pred_sem_cls, nonempty=nonempty)
 
 
+def detection_scores(sem_cls_probs, objectness_probs, angle_probs, pred_sem_cls, config_dict):
+    """The confidence of every detection as a device tensor (ap_calculator.py:233-282) -> (scores [B,K,S], per_class): S =
+    num_semcls with one detection per (box, class) for the per-class forms (``per_class_proposal`` / ``angle_conf``), else S = 1
+    with the box's own class: its class probability (``use_cls_confidence_only``) or its objectness."""
+    cfg = config_dict
+    sem = sem_cls_probs.detach().float()
+    obj = objectness_probs.detach().float()
+    if cfg.get("angle_conf") or cfg["per_class_proposal"]:
+        assert cfg["use_cls_confidence_only"] is False
+        score = sem * obj[..., None]
+        if cfg.get("angle_conf"):
+            score = score * angle_probs.detach().float()[..., None]
+        return score[..., :cfg["dataset_config"].num_semcls], True
+    if cfg["use_cls_confidence_only"]:
+        return sem.gather(-1, pred_sem_cls[..., None]), False
+    return obj[..., None], False
+
+
 def parse_predictions(predicted_boxes, sem_cls_probs, objectness_probs, angle_probs, point_cloud, config_dict,
                       predicted_boxes_CSA=None):
     """ap_calculator.py:48-282, same arguments and the same result: a list (batch) of lists of
     ``(class, corners [8,3] float32 array, score)`` in the reference's order (class-major for the per-class forms)."""
     cfg = config_dict
     m = prediction_masks(predicted_boxes, sem_cls_probs, objectness_probs, angle_probs, point_cloud, cfg, predicted_boxes_CSA)
-    sem = sem_cls_probs.detach().float()
-    obj = objectness_probs.detach().float()
-    per_class = cfg.get("angle_conf") or cfg["per_class_proposal"]
-    if per_class:
-        assert cfg["use_cls_confidence_only"] is False
-        score = sem * obj[..., None]                                    # [B,K,C]
-        if cfg.get("angle_conf"):
-            score = score * angle_probs.detach().float()[..., None]
-    elif cfg["use_cls_confidence_only"]:
-        score = sem.gather(-1, m["pred_sem_cls"][..., None])[..., 0]    # [B,K]
-    else:
-        score = obj
+    score, per_class = detection_scores(sem_cls_probs, objectness_probs, angle_probs, m["pred_sem_cls"], cfg)
+    score = score if per_class else score[..., 0]                       # [B,K,C] or [B,K]
     keep, cls, corners, score = (t.cpu().numpy() for t in (m["keep"], m["pred_sem_cls"], predicted_boxes.detach().float(), score))
     out = []
     for i in range(keep.shape[0]):
@@ -141,18 +149,8 @@ def detections_flat(predicted_boxes, sem_cls_probs, objectness_probs, angle_prob
     numpy arrays, the m detections in the order of the reference's list (class-major for the per-class forms)."""
     cfg = config_dict
     m = prediction_masks(predicted_boxes, sem_cls_probs, objectness_probs, angle_probs, point_cloud, cfg, predicted_boxes_CSA)
-    sem = sem_cls_probs.detach().float()
-    obj = objectness_probs.detach().float()
-    per_class = cfg.get("angle_conf") or cfg["per_class_proposal"]
-    if per_class:
-        assert cfg["use_cls_confidence_only"] is False
-        score = sem * obj[..., None]
-        if cfg.get("angle_conf"):
-            score = score * angle_probs.detach().float()[..., None]
-    elif cfg["use_cls_confidence_only"]:
-        score = sem.gather(-1, m["pred_sem_cls"][..., None])[..., 0]
-    else:
-        score = obj
+    score, per_class = detection_scores(sem_cls_probs, objectness_probs, angle_probs, m["pred_sem_cls"], cfg)
+    score = score if per_class else score[..., 0]                       # [B,K,C] or [B,K]
     keep, cls, corners, score = (t.cpu().numpy() for t in (m["keep"], m["pred_sem_cls"], predicted_boxes.detach().float(), score))
     out = []
     for i in range(keep.shape[0]):
@@ -169,11 +167,18 @@ def detections_flat(predicted_boxes, sem_cls_probs, objectness_probs, angle_prob
 class APCalculator(object):
     """ap_calculator.py:324-529 with the same constructor, methods and result dictionaries.  ``step`` keeps the detections of
     a batch as flat arrays (no per-detection Python tuples) and ``compute_metrics`` hands them to the device matcher
-    (eval_det.evaluate_flat); ``accumulate`` still accepts the reference's lists of tuples."""
+    (eval_det.evaluate_flat); ``accumulate`` still accepts the reference's lists of tuples.
+
+    ``resident=True`` keeps the detections on the device instead (eval_store.DetectionStore): ``step`` /
+    ``step_meter`` launch and return without a host read, ``compute_metrics`` reads the store's four counters and one small
+    result buffer for all thresholds, and gives the same dictionaries and text.  ``capacity`` fixes the number of box rows of
+    the store (rows beyond it are dropped and ``compute_metrics`` raises RuntimeError naming their number); by default the
+    store grows geometrically from ``initial_capacity``.  Class labels of a resident calculator are 0 .. num_semcls-1."""
 
     def __init__(self, dataset_config, ap_iou_thresh=[0.25, 0.5], class2type_map=None, exact_eval=False, ap_config_dict=None,
-                 no_nms=False, args=None):
+                 no_nms=False, args=None, resident=False, capacity=None, initial_capacity=4096):
         self.ap_iou_thresh = ap_iou_thresh
+        self.resident, self._capacity, self._initial_capacity = bool(resident), capacity, initial_capacity
         if ap_config_dict is None:
             ap_config_dict = get_ap_config_dict(
                 dataset_config=dataset_config, remove_empty_box=exact_eval, no_nms=no_nms, use_3d_nms=not args.no_3d_nms,
@@ -191,6 +196,8 @@ class APCalculator(object):
         self._flat_pred = {}     # {scan_id: (corners [n,8,3], classes [m], box index [m], scores [m])}  (filled by step())
         self._flat_gt = {}       # {scan_id: (classes [g], corners [g,8,3])}
         self.scan_cnt = 0
+        self._store = None       # eval_store.DetectionStore of a resident calculator (made by the first step: device, S)
+        self._last_result = None  # [T,4,C] result buffer of the last resident compute_metrics
 
     def make_gt_list(self, gt_box_corners, gt_box_sem_cls_labels, gt_box_present):
         return [[(gt_box_sem_cls_labels[i, j].item(), gt_box_corners[i, j]) for j in range(gt_box_corners.shape[1])
@@ -209,6 +216,9 @@ class APCalculator(object):
 
     def step(self, predicted_box_corners, sem_cls_probs, objectness_probs, angle_probs, point_cloud, gt_box_corners,
              gt_box_sem_cls_labels, gt_box_present, predicted_box_CSA):
+        if self.resident:
+            return self._step_resident(predicted_box_corners, sem_cls_probs, objectness_probs, angle_probs, point_cloud,
+                                       gt_box_corners, gt_box_sem_cls_labels, gt_box_present, predicted_box_CSA)
         gt_c = gt_box_corners.detach().float().cpu().numpy()
         gt_k = gt_box_sem_cls_labels.detach().cpu().numpy()
         gt_p = gt_box_present.detach().cpu().numpy() == 1
@@ -219,7 +229,25 @@ class APCalculator(object):
             self._flat_gt[self.scan_cnt] = (gt_k[i][gt_p[i]].astype(np.int64), gt_c[i][gt_p[i]])
             self.scan_cnt += 1
 
+    def _step_resident(self, predicted_box_corners, sem_cls_probs, objectness_probs, angle_probs, point_cloud, gt_box_corners,
+                       gt_box_sem_cls_labels, gt_box_present, predicted_box_CSA):
+        """prediction_masks, the scores, one append: nothing is read back"""
+        from .eval_store import DetectionStore
+        cfg = self.ap_config_dict
+        m = prediction_masks(predicted_box_corners, sem_cls_probs, objectness_probs, angle_probs, point_cloud, cfg, predicted_box_CSA)
+        score, per_class = detection_scores(sem_cls_probs, objectness_probs, angle_probs, m["pred_sem_cls"], cfg)
+        if self._store is None:
+            self._store = DetectionStore(score.shape[-1], score.device, self._capacity, self._initial_capacity)
+            self._per_class = per_class
+            self._num_classes = max(int(cfg["dataset_config"].num_semcls), 1 if per_class else int(sem_cls_probs.shape[-1]))
+        self._store.append(m["keep"], predicted_box_corners, score, m["pred_sem_cls"], gt_box_corners, gt_box_sem_cls_labels,
+                           gt_box_present == 1)
+        self.scan_cnt += predicted_box_corners.shape[0]
+
     def accumulate(self, batch_pred_map_cls, batch_gt_map_cls):
+        if self.resident:
+            raise ValueError("accumulate() takes host lists: a resident APCalculator keeps its detections on the device (use step / "
+                             "step_meter, or resident=False)")
         assert len(batch_pred_map_cls) == len(batch_gt_map_cls)
         for pred, gt in zip(batch_pred_map_cls, batch_gt_map_cls):
             self.gt_map_cls[self.scan_cnt] = gt
@@ -227,11 +255,15 @@ class APCalculator(object):
             self.scan_cnt += 1
 
     def _flat_arrays(self):
+        flat_pred, flat_gt = self._flat_pred, self._flat_gt
+        if self.resident and self._store is not None:    # the store read back, in the form step() keeps
+            from .eval_store import expand_host
+            flat_pred, flat_gt = expand_host(self._store.to_host(), self._num_classes, self._per_class)
         pc, pi, pk, ps, gc, gi, gk = [], [], [], [], [], [], []
         for scan in range(self.scan_cnt):
-            if scan in self._flat_pred:
-                corners, cls, idx, score = self._flat_pred[scan]
-                g_cls, g_corners = self._flat_gt[scan]
+            if scan in flat_pred:
+                corners, cls, idx, score = flat_pred[scan]
+                g_cls, g_corners = flat_gt[scan]
                 pc.append(corners[idx]), pk.append(cls), ps.append(score.astype(np.float64))
             else:
                 dets, gts = self.pred_map_cls[scan], self.gt_map_cls[scan]
@@ -245,36 +277,97 @@ class APCalculator(object):
         return (cat(pc, (0, 8, 3), np.float32), cat(pi, 0, np.int64), cat(pk, 0, np.int64), cat(ps, 0, np.float64),
                 cat(gc, (0, 8, 3), np.float32), cat(gi, 0, np.int64), cat(gk, 0, np.int64))
 
-    def compute_metrics(self, size=""):
+    def _metrics(self, ap, last_rec):
+        """One threshold's dictionary (ap_calculator.py:455-480) from {class: AP} and {class: last recall}, both in ascending
+        class order: the per-class entries, mAP with NaN counted as 0, AR = the mean of the last recalls."""
         from collections import OrderedDict
+        name = lambda key: self.class2type_map[key] if self.class2type_map else str(key)  # noqa: E731
+        ret = OrderedDict()
+        for key in sorted(ap.keys()):
+            ret["%s Average Precision" % (name(key))] = ap[key]
+        ap_vals = np.array(list(ap.values()), dtype=np.float32)
+        ap_vals[np.isnan(ap_vals)] = 0
+        ret["mAP"] = ap_vals.mean()
+        rec_list = []
+        for key in sorted(ap.keys()):
+            ret["%s Recall" % (name(key))] = last_rec[key]
+            rec_list.append(last_rec[key])
+        ret["AR"] = np.mean(rec_list)
+        return ret
 
+    def _host_curves(self, size=""):
+        """The host path: {threshold: (rec, prec, ap)} of eval_det.evaluate_flat, keyed by integer class label.  The classes are
+        those with a detection or a ground-truth box, as in the reference's dictionary."""
         from .eval_det import evaluate_flat
         pc, pi, pk, ps, gc, gi, gk = self._flat_arrays()
-        # classes are reported under their integer label; the reference's dictionary holds every class that has a detection
-        # or a ground-truth box
         present = np.union1d(np.unique(pk), np.unique(gk)).astype(np.int64)
         remap = np.full(int(present.max()) + 1 if present.size else 1, -1, np.int64)
         remap[present] = np.arange(present.size)
+        return {thr: evaluate_flat(pc, pi, remap[pk], ps, gc, gi, remap[gk], self.scan_cnt, [int(c) for c in present], ovthresh=thr,
+                                   size=size) for thr in self.ap_iou_thresh}
+
+    def _resident_eval(self, curves=False):
+        from .eval_store import evaluate
+        if self._store is None:
+            raise RuntimeError("compute_metrics on a resident APCalculator before the first step")
+        res = evaluate(self._store, list(self.ap_iou_thresh), self._num_classes, self._per_class, curves)
+        self._last_result = res["result"]
+        return res
+
+    def compute_metrics(self, size=""):
+        """{threshold: {"<class> Average Precision", ..., "mAP", "<class> Recall", ..., "AR"}}.  A resident calculator computes
+        them on the device with two host reads (the store's counters, then one [T,4,C] buffer).  ``size`` = "S" / "M" / "L" is a
+        numpy-precision volume filter (eval_det.py:64-69, :90): a resident calculator then reads its store back and takes the
+        host path."""
+        from collections import OrderedDict
         overall_ret = OrderedDict()
-        for thr in self.ap_iou_thresh:
-            rec, prec, ap = evaluate_flat(pc, pi, remap[pk], ps, gc, gi, remap[gk], self.scan_cnt, [int(c) for c in present],
-                                          ovthresh=thr, size=size)
-            ret = OrderedDict()
-            for key in sorted(ap.keys()):
-                clsname = self.class2type_map[key] if self.class2type_map else str(key)
-                ret["%s Average Precision" % (clsname)] = ap[key]
-            ap_vals = np.array(list(ap.values()), dtype=np.float32)
-            ap_vals[np.isnan(ap_vals)] = 0
-            ret["mAP"] = ap_vals.mean()
-            rec_list = []
-            for key in sorted(ap.keys()):
-                clsname = self.class2type_map[key] if self.class2type_map else str(key)
-                last = rec[key][-1] if isinstance(rec[key], np.ndarray) and rec[key].size else 0   # no detection: 0 (:471-476)
-                ret["%s Recall" % (clsname)] = last
-                rec_list.append(last)
-            ret["AR"] = np.mean(rec_list)
-            overall_ret[thr] = ret
+        if self.resident and size == "":
+            result = self._resident_eval()["result"]
+            for t, thr in enumerate(self.ap_iou_thresh):
+                ap_row, rec_row, ndet, npos = result[t]
+                keys = [c for c in range(result.shape[2]) if ndet[c] > 0 or npos[c] > 0]
+                overall_ret[thr] = self._metrics({c: ap_row[c] if ndet[c] > 0 else 0 for c in keys},
+                                                 {c: rec_row[c] if ndet[c] > 0 else 0 for c in keys})
+            return overall_ret
+        for thr, (rec, prec, ap) in self._host_curves(size).items():
+            # a class without detection reports 0 (:471-476)
+            last = {key: rec[key][-1] if isinstance(rec[key], np.ndarray) and rec[key].size else 0 for key in ap}
+            overall_ret[thr] = self._metrics(ap, last)
         return overall_ret
+
+    def _ranking(self):
+        """{threshold: (order, tp)}: the detections' indices (insertion order over all scans) ranked by (class, descending score,
+        insertion) and the true-positive flag of every rank — what the precision / recall curves are counted from (tests)."""
+        if self.resident:
+            res = self._resident_eval()
+            order, tp = res["order"].cpu().numpy(), res["tp"].cpu().numpy().astype(bool)
+            return {thr: (order, tp[t]) for t, thr in enumerate(self.ap_iou_thresh)}
+        from .eval_det import match_detections
+        pc, pi, pk, ps, gc, gi, gk = self._flat_arrays()
+        g_order = np.argsort(gi, kind="stable")
+        out = {}
+        for thr in self.ap_iou_thresh:
+            order, tp = match_detections(pc, pi, pk, ps, gc[g_order], gi[g_order], gk[g_order], self.scan_cnt, thr)
+            out[thr] = (order, tp[order])
+        return out
+
+    def _curves(self):
+        """{threshold: (rec, prec, ap)} keyed by integer class label, a class without detection holding 0 (tests)."""
+        if not self.resident:
+            return self._host_curves()
+        res = self._resident_eval(curves=True)
+        seg, rec_all, prec_all = res["seg"].cpu().numpy(), res["rec"].cpu().numpy(), res["prec"].cpu().numpy()
+        out = {}
+        for t, thr in enumerate(self.ap_iou_thresh):
+            ap_row, _, ndet, npos = res["result"][t]
+            rec, prec, ap = {}, {}, {}
+            for c in range(len(ap_row)):
+                if ndet[c] > 0:
+                    rec[c], prec[c], ap[c] = rec_all[t, seg[c]:seg[c + 1]], prec_all[t, seg[c]:seg[c + 1]], ap_row[c]
+                elif npos[c] > 0:
+                    rec[c] = prec[c] = ap[c] = 0
+            out[thr] = (rec, prec, ap)
+        return out
 
     def __str__(self):
         return self.metrics_to_str(self.compute_metrics())

@@ -348,6 +348,47 @@ __global__ __launch_bounds__(128) void box3d_iou_max_kernel(const float* __restr
   jmax[d] = arg;
 }
 
+// The same matching with the detections given as (box row, class) pairs of the evaluation's device store (eval_store.hip,
+// DESIGN.md 6.12): thread e = r * max(C, 1) + c takes box row r and class c (C = 0: the stored class) and writes detection
+// d = C box_begin[s] + c n_s + (r - box_begin[s]) of the reference's per-scan class-major list order, with its class and
+// score.  The loop over the scan's ground truth is box3d_iou_max_kernel's, expression for expression.  Everything read from
+// the store is device data: rows and scans outside the host's counts write nothing.
+__global__ __launch_bounds__(128) void box3d_iou_max_idx_kernel(vdetr_det_store st, int nboxes, int nscans, int ngt, int C,
+                                                                double* __restrict__ ovmax, int* __restrict__ jmax,
+                                                                int* __restrict__ det_cls, float* __restrict__ det_score) {
+  const int per = C > 0 ? C : 1;
+  const long e = (long)blockIdx.x * 128 + threadIdx.x;
+  if (e >= (long)nboxes * per) return;
+  const int r = (int)(e / per), c = (int)(e % per);
+  const int s = st.box_scan[r];
+  if (s < 0 || s >= nscans) return;
+  const int b0 = st.box_begin[s], ns = st.box_begin[s + 1] - b0, j = r - b0;
+  if (j < 0 || j >= ns) return;
+  const long d = C > 0 ? (long)C * b0 + (long)c * ns + j : r;
+  if (d < 0 || d >= (long)nboxes * per) return;
+  float c1[24];
+  for (int k = 0; k < 24; ++k) c1[k] = st.box_corners[(size_t)r * 24 + k];
+  const int cls = C > 0 ? c : st.box_cls[r];
+  const double vol1 = box3d_vol64(c1);
+  double best = -INFINITY;
+  int arg = -1;
+  const int g0 = max(st.gt_begin[s], 0), g1 = min(st.gt_begin[s + 1], ngt);
+  for (int g = g0; g < g1; ++g) {
+    if (st.gt_cls[g] != cls) continue;
+    float c2[24];
+    for (int k = 0; k < 24; ++k) c2[k] = st.gt_corners[(size_t)g * 24 + k];
+    const double area = footprint_intersection(c1, c2);
+    const double ymax = fmin((double)c1[1], (double)c2[1]), ymin = fmax((double)c1[13], (double)c2[13]);
+    const double inter_vol = area * fmax(0.0, ymax - ymin);
+    const double iou = inter_vol / ((vol1 + box3d_vol64(c2)) - inter_vol);
+    if (iou > best) best = iou, arg = g;
+  }
+  ovmax[d] = best;
+  jmax[d] = arg;
+  det_cls[d] = cls;
+  det_score[d] = st.box_scores[(size_t)r * st.S + (C > 0 ? c : 0)];
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The reference's box3d_iou for all pairs: out[a, b] = box3d_iou(corners_a[a], corners_b[b]) (box a is the subject of the
 // clip, box b the clip polygon, as in box_util.py:139).  One thread per pair.
@@ -534,4 +575,25 @@ extern "C" int vdetr_box3d_iou_max_f64(const float* pred_corners, const int32_t*
   hipLaunchKernelGGL(box3d_iou_max_kernel, dim3(ceil_div(P, 128)), dim3(128), 0, (hipStream_t)stream, pred_corners, pred_img, pred_cls,
                      P, gt_corners, gt_cls, img_gt_begin, ovmax, jmax);
   return check_launch("box3d_iou_max");
+}
+
+extern "C" int vdetr_box3d_iou_max_idx_f64(const vdetr_det_store* store, int nboxes, int nscans, int ngt, int num_classes,
+                                           double* ovmax, int32_t* jmax, int32_t* det_cls, float* det_score,
+                                           vdetr_stream_t stream) {
+  VDETR_REQUIRE(store, "box3d_iou_max_idx: null store");
+  const vdetr_det_store& s = *store;
+  VDETR_REQUIRE(nboxes >= 0 && nscans >= 0 && ngt >= 0 && num_classes >= 0, "box3d_iou_max_idx: negative count");
+  VDETR_REQUIRE(nboxes <= s.box_capacity && nscans <= s.scan_capacity && ngt <= s.gt_capacity,
+                "box3d_iou_max_idx: %d boxes, %d scans, %d ground-truth boxes exceed the store's %d, %d, %d", nboxes, nscans, ngt,
+                s.box_capacity, s.scan_capacity, s.gt_capacity);
+  VDETR_REQUIRE(s.S >= (num_classes > 0 ? num_classes : 1), "box3d_iou_max_idx: %d scores per box < %d classes", s.S, num_classes);
+  const long P = (long)nboxes * (num_classes > 0 ? num_classes : 1);
+  VDETR_REQUIRE(P < ((long)1 << 31), "box3d_iou_max_idx: %ld detections >= 2^31", P);
+  if (P == 0) return VDETR_OK;
+  VDETR_REQUIRE(s.box_corners && s.box_scores && s.box_cls && s.box_scan && s.box_begin && s.gt_begin && ovmax && jmax &&
+                    det_cls && det_score && (ngt == 0 || (s.gt_corners && s.gt_cls)),
+                "box3d_iou_max_idx: null pointer");
+  hipLaunchKernelGGL(box3d_iou_max_idx_kernel, dim3(ceil_div(P, 128)), dim3(128), 0, (hipStream_t)stream, s, nboxes, nscans, ngt,
+                     num_classes, ovmax, jmax, det_cls, det_score);
+  return check_launch("box3d_iou_max_idx");
 }

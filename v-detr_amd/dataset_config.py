@@ -27,6 +27,11 @@ class ScannetDatasetConfig:
         # scannet.py:65-70: the nyu40 ids of the 18 classes, as the last column of a scan's _bbox.npy holds them
         self.nyu40ids = np.array([3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39])
         self.nyu40id2class = {int(nyu40id): i for i, nyu40id in enumerate(self.nyu40ids)}
+        # scannet.py:44-64: the names the metrics are reported under (the ScanNet 18-class benchmark's, in label order)
+        names = ("cabinet bed chair sofa table door window bookshelf picture counter desk curtain refrigerator showercurtrain "
+                 "toilet sink bathtub garbagebin").split()
+        self.type2class = {name: i for i, name in enumerate(names)}
+        self.class2type = {i: name for i, name in enumerate(names)}
 
     def box_parametrization_to_corners(self, box_center_unnorm, box_size, box_angle):
         """scannet.py:168-171"""
@@ -44,3 +49,5 @@ class RotatedBoxDatasetConfig(ScannetDatasetConfig):
         rng = np.random.default_rng(0)
         self.mean_size_arr = 0.4 + rng.random((num_semcls, 3)) * 1.6
         self.mean_size_arr_hard_anchor = np.ones((num_semcls, 3))
+        self.type2class = {f"class{i}": i for i in range(num_semcls)}
+        self.class2type = {i: name for name, i in self.type2class.items()}

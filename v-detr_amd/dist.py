@@ -690,3 +690,42 @@ def reduce_dict(input_dict, average=True):
         if average:
             values /= dist.get_world_size()
         return dict(zip(names, values))
+
+
+# ---- the engine's batch helpers (utils/dist.py:159-185) ------------------------------------------------------------
+def all_gather_dict(data):
+    """utils/dist.py:159-176: every tensor entry gathered from all ranks and concatenated on dimension 0 (the identity on one
+    rank or without a process group); other entries are passed through."""
+    assert isinstance(data, dict)
+    if not (dist.is_available() and dist.is_initialized()):
+        return dict(data)
+    gathered = {}
+    for key, value in data.items():
+        if isinstance(value, torch.Tensor):
+            value = value.contiguous()
+            parts = [torch.empty_like(value) for _ in range(dist.get_world_size())]
+            dist.all_gather(parts, value)
+            value = torch.cat(parts, dim=0)
+        gathered[key] = value
+    return gathered
+
+
+def batch_dict_to_cuda(batch_dict, local_rank="cuda:0"):
+    """utils/dist.py:178-185: tensors and lists of tensors of the batch moved to ``local_rank`` (a device), in place."""
+    for key, value in batch_dict.items():
+        if isinstance(value, torch.Tensor):
+            batch_dict[key] = value.to(local_rank)
+        elif isinstance(value, list) and len(value) > 0 and isinstance(value[0], torch.Tensor):
+            batch_dict[key] = [item.to(local_rank) for item in value]
+    return batch_dict
+
+
+def is_primary():
+    """utils/dist.py:14-21: rank 0, or no process group"""
+    return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+
+
+def barrier():
+    """utils/dist.py:30-33"""
+    if dist.is_available() and dist.is_initialized():
+        dist.barrier()
