@@ -743,10 +743,67 @@ typedef struct vdetr_adamw_sched_desc {
   double* lr_out;
 } vdetr_adamw_sched_desc;
 int vdetr_adamw_sched_f32(const vdetr_adamw_sched_desc* d, vdetr_stream_t stream);
+/* vdetr_adamw_sched_f32 behind a device flag (engine.py:100-107: `sys.exit(1)` on a non-finite loss, BEFORE backward and the step;
+ * here the host does not read the loss, so the decision not to step is taken on the device).  The fields of vdetr_adamw_sched_desc
+ * in the same order, then:
+ *   skip (device, required): one int32, read by every workgroup before anything else (vdetr_loss_meter_state.bad is one).
+ *     *skip != 0: every workgroup returns before it reads a gradient; param, both moments, *step, norm_out and lr_out keep every bit,
+ *       and no ticket is drawn (`ticket` stays zero: the next launch works).
+ *     *skip == 0: vdetr_adamw_sched_f32, bit for bit (one kernel body, instantiated with and without the read).
+ * A captured graph replays the pointer: the flag decides at every replay. */
+typedef struct vdetr_adamw_guard_desc {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t n;
+  float* step;
+  uint32_t* ticket;
+  const float* sumsq;
+  int32_t nsumsq;
+  float max_norm;
+  float norm_eps;
+  float* norm_out;
+  double lr, beta1, beta2, eps, weight_decay;
+  const double* lr_table;
+  int64_t n_lr;
+  int64_t lr_offset;
+  const uint32_t* decay_mask;
+  double* lr_out;
+  const int32_t* skip;
+} vdetr_adamw_guard_desc;
+int vdetr_adamw_guard_f32(const vdetr_adamw_guard_desc* d, vdetr_stream_t stream);
 /* partial[b] = sum of squares of slice b of g [n] (npartial = vdetr_sumsq_blocks(n)): the norm's first half where the flat gradient
  * changed after the pack (all-reduce, N > 1). */
 int vdetr_sumsq_blocks(long n);
 int vdetr_sumsq_f32(const float* g, long n, float* partial, int npartial, vdetr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * The training loop's loss meter on the device, one small launch per iteration (csrc/train_meter.hip).
+ * Reference: engine.py:74,100-102,109 (`SmoothedValue(window_size=10)`, utils/misc.py:40-91; `math.isfinite(loss_reduced.item())`).
+ * The reference reads the loss twice per iteration; this launch takes it as a device scalar and keeps what the reads fed:
+ *   bad already set       -> nothing changes (training has stopped: later losses do not enter the window)
+ *   loss NaN or +-inf     -> bad = 1, bad_iter = iter; ring, count and total stay (the reference exits before loss_avg.update)
+ *   otherwise             -> ring[count % window] = loss, total += (double)loss, count += 1
+ * `window` is device data: outside 1 .. VDETR_LOSS_METER_MAX_WINDOW the launch only sets bad = 2.  The deque, oldest first, is
+ * ring[0 .. count) while count <= window and ring[count % window ...] wrapped around afterwards.  `bad` is what
+ * vdetr_adamw_guard_f32 takes as `skip`.  One workgroup, on the caller's stream.
+ * ---------------------------------------------------------------------------------------------- */
+#define VDETR_LOSS_METER_MAX_WINDOW 64
+typedef struct vdetr_loss_meter_state {
+  double total;      /* SmoothedValue.total: sequential double adds of (double)loss, the order Python's `+=` takes them */
+  int64_t count;     /* SmoothedValue.count */
+  int64_t bad_iter;  /* iteration of the first non-finite loss, -1 while none */
+  int32_t bad;       /* sticky: 0, or 1 from the first non-finite loss on (2: `window` out of range) */
+  int32_t window;    /* 1 .. VDETR_LOSS_METER_MAX_WINDOW */
+  float ring[VDETR_LOSS_METER_MAX_WINDOW]; /* the deque: slot count % window */
+} vdetr_loss_meter_state;
+typedef struct vdetr_loss_meter_desc {
+  const float* loss;             /* device scalar */
+  vdetr_loss_meter_state* state; /* device, 8-B aligned */
+  int64_t iter;                  /* the host's curr_iter (>= 0) */
+} vdetr_loss_meter_desc;
+int vdetr_loss_meter_update_f32(const vdetr_loss_meter_desc* d, vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Z-order permutation of a scene's key points, one launch (ranks by counting, n / 64 workgroups per scene).  Replaces the tensor expression the

@@ -242,6 +242,28 @@ class AdamWSchedDesc(ctypes.Structure):
                                      ("decay_mask", c_void_p), ("lr_out", c_void_p)]
 
 
+class AdamWGuardDesc(ctypes.Structure):
+    """Mirror of ``vdetr_adamw_guard_desc``."""
+
+    _fields_ = AdamWSchedDesc._fields_ + [("skip", c_void_p)]
+
+
+VDETR_LOSS_METER_MAX_WINDOW = 64
+
+
+class LossMeterState(ctypes.Structure):
+    """Mirror of ``vdetr_loss_meter_state``."""
+
+    _fields_ = [("total", ctypes.c_double), ("count", ctypes.c_int64), ("bad_iter", ctypes.c_int64), ("bad", ctypes.c_int32),
+                ("window", ctypes.c_int32), ("ring", c_float * VDETR_LOSS_METER_MAX_WINDOW)]
+
+
+class LossMeterDesc(ctypes.Structure):
+    """Mirror of ``vdetr_loss_meter_desc``."""
+
+    _fields_ = [("loss", c_void_p), ("state", c_void_p), ("iter", ctypes.c_int64)]
+
+
 class PosMlpDesc(ctypes.Structure):
     """Mirror of ``vdetr_posmlp_desc``."""
 
@@ -523,6 +545,8 @@ _SIGNATURES = {
     "vdetr_pack_sumsq_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vdetr_adamw_clip_f32": (c_int, [ctypes.POINTER(AdamWDesc), c_void_p]),
     "vdetr_adamw_sched_f32": (c_int, [ctypes.POINTER(AdamWSchedDesc), c_void_p]),
+    "vdetr_adamw_guard_f32": (c_int, [ctypes.POINTER(AdamWGuardDesc), c_void_p]),
+    "vdetr_loss_meter_update_f32": (c_int, [ctypes.POINTER(LossMeterDesc), c_void_p]),
     "vdetr_cpb_tables_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3),
     "vdetr_sumsq_blocks": (c_int, [ctypes.c_long]),
     "vdetr_sumsq_f32": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_int, c_void_p]),

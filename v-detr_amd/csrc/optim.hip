@@ -148,8 +148,16 @@ struct AdamSchedArgs {
   double* lr_out;            // optional
 };
 
-__global__ __launch_bounds__(kOptThreads) void adamw_sched_kernel(AdamSchedArgs S) {
+// One body for vdetr_adamw_sched_f32 (kGuard false: `skip` is not read, the kernel is the one it was) and vdetr_adamw_guard_f32 (kGuard
+// true): there every workgroup reads *skip first and returns on a nonzero word before it touches a gradient, a moment, the step
+// count or the ticket -- the word is the same for the whole grid, so either every workgroup draws a ticket or none does, and the
+// ticket stays zero either way.  *skip is written by an EARLIER launch on the stream (the loss meter's `bad`), never by this one.
+template <bool kGuard>
+__device__ __forceinline__ void adamw_sched_body(const AdamSchedArgs& S, const int* __restrict__ skip) {
   __shared__ double red[4];
+  if (kGuard) {
+    if (*skip != 0) return;
+  }
   const AdamArgs& A = S.a;
   const float step0 = *A.step, step = step0 + 1.f;
   double lr = A.lr;
@@ -219,6 +227,14 @@ __global__ __launch_bounds__(kOptThreads) void adamw_sched_kernel(AdamSchedArgs 
   }
 }
 
+__global__ __launch_bounds__(kOptThreads) void adamw_sched_kernel(AdamSchedArgs S) {
+  adamw_sched_body<false>(S, nullptr);
+}
+
+__global__ __launch_bounds__(kOptThreads) void adamw_guard_kernel(AdamSchedArgs S, const int* __restrict__ skip) {
+  adamw_sched_body<true>(S, skip);
+}
+
 }  // namespace vdetr
 
 using namespace vdetr;
@@ -260,18 +276,20 @@ extern "C" int vdetr_adamw_clip_f32(const vdetr_adamw_desc* d, vdetr_stream_t st
   return check_launch("adamw_clip");
 }
 
-extern "C" int vdetr_adamw_sched_f32(const vdetr_adamw_sched_desc* d, vdetr_stream_t stream) {
-  VDETR_REQUIRE(d != nullptr, "adamw_sched: null descriptor");
-  VDETR_REQUIRE(d->param && d->grad && d->exp_avg && d->exp_avg_sq && d->step && d->ticket && d->n > 0, "adamw_sched: null pointer or empty buffer");
+// the checks, the kernel arguments and the grid of vdetr_adamw_sched_f32 / vdetr_adamw_guard_f32 (D: either descriptor; the guard's
+// has the same fields in front)
+template <typename D>
+static int adamw_sched_setup(const D* d, const char* op, AdamSchedArgs& S, long& blocks) {
+  VDETR_REQUIRE(d != nullptr, "%s: null descriptor", op);
+  VDETR_REQUIRE(d->param && d->grad && d->exp_avg && d->exp_avg_sq && d->step && d->ticket && d->n > 0, "%s: null pointer or empty buffer", op);
   VDETR_REQUIRE((((uintptr_t)d->param | (uintptr_t)d->grad | (uintptr_t)d->exp_avg | (uintptr_t)d->exp_avg_sq) & 15) == 0,
-                "adamw_sched: the four buffers must be 16-B aligned");
+                "%s: the four buffers must be 16-B aligned", op);
   VDETR_REQUIRE(d->lr >= 0.0 && d->beta1 >= 0.0 && d->beta1 < 1.0 && d->beta2 >= 0.0 && d->beta2 < 1.0 && d->eps >= 0.0 && d->weight_decay >= 0.0,
-                "adamw_sched: lr %g betas (%g, %g) eps %g weight_decay %g", d->lr, d->beta1, d->beta2, d->eps, d->weight_decay);
-  VDETR_REQUIRE(!d->sumsq || (d->nsumsq > 0 && d->max_norm > 0.f), "adamw_sched: %d partial sums, max_norm %g", d->nsumsq, d->max_norm);
-  VDETR_REQUIRE(d->lr_table ? d->n_lr > 0 : d->n_lr <= 0, "adamw_sched: lr_table %s with n_lr %ld", d->lr_table ? "given" : "null", (long)d->n_lr);
-  VDETR_REQUIRE(((uintptr_t)d->lr_table & 7) == 0 && ((uintptr_t)d->lr_out & 7) == 0, "adamw_sched: lr_table and lr_out must be 8-B aligned");
-  VDETR_REQUIRE(((uintptr_t)d->decay_mask & 3) == 0, "adamw_sched: decay_mask must be 4-B aligned");
-  AdamSchedArgs S;
+                "%s: lr %g betas (%g, %g) eps %g weight_decay %g", op, d->lr, d->beta1, d->beta2, d->eps, d->weight_decay);
+  VDETR_REQUIRE(!d->sumsq || (d->nsumsq > 0 && d->max_norm > 0.f), "%s: %d partial sums, max_norm %g", op, d->nsumsq, d->max_norm);
+  VDETR_REQUIRE(d->lr_table ? d->n_lr > 0 : d->n_lr <= 0, "%s: lr_table %s with n_lr %ld", op, d->lr_table ? "given" : "null", (long)d->n_lr);
+  VDETR_REQUIRE(((uintptr_t)d->lr_table & 7) == 0 && ((uintptr_t)d->lr_out & 7) == 0, "%s: lr_table and lr_out must be 8-B aligned", op);
+  VDETR_REQUIRE(((uintptr_t)d->decay_mask & 3) == 0, "%s: decay_mask must be 4-B aligned", op);
   AdamArgs& A = S.a;
   A.p = d->param; A.g = d->grad; A.m = d->exp_avg; A.v = d->exp_avg_sq;
   A.n = (long)d->n;
@@ -283,9 +301,26 @@ extern "C" int vdetr_adamw_sched_f32(const vdetr_adamw_sched_desc* d, vdetr_stre
   S.lr_table = d->lr_table; S.n_lr = (long)d->n_lr; S.lr_offset = (long)d->lr_offset;
   S.mask = d->decay_mask; S.lr_out = d->lr_out;
   const long n4 = A.n / 4;
-  long blocks = (n4 + kOptThreads * 4 - 1) / (kOptThreads * 4);  // the launch shape of vdetr_adamw_clip_f32
+  blocks = (n4 + kOptThreads * 4 - 1) / (kOptThreads * 4);  // the launch shape of vdetr_adamw_clip_f32
   const long cap = (long)device_cu_count() * 16;
   blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
+  return VDETR_OK;
+}
+
+extern "C" int vdetr_adamw_sched_f32(const vdetr_adamw_sched_desc* d, vdetr_stream_t stream) {
+  AdamSchedArgs S;
+  long blocks = 0;
+  if (const int status = adamw_sched_setup(d, "adamw_sched", S, blocks)) return status;
   hipLaunchKernelGGL(adamw_sched_kernel, dim3((unsigned)blocks), dim3(kOptThreads), 0, (hipStream_t)stream, S);
   return check_launch("adamw_sched");
+}
+
+extern "C" int vdetr_adamw_guard_f32(const vdetr_adamw_guard_desc* d, vdetr_stream_t stream) {
+  AdamSchedArgs S;
+  long blocks = 0;
+  if (const int status = adamw_sched_setup(d, "adamw_guard", S, blocks)) return status;
+  VDETR_REQUIRE(d->skip != nullptr, "adamw_guard: skip is NULL");
+  VDETR_REQUIRE(((uintptr_t)d->skip & 3) == 0, "adamw_guard: skip must be 4-B aligned (%p)", (const void*)d->skip);
+  hipLaunchKernelGGL(adamw_guard_kernel, dim3((unsigned)blocks), dim3(kOptThreads), 0, (hipStream_t)stream, S, (const int*)d->skip);
+  return check_launch("adamw_guard");
 }

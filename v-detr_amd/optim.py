@@ -8,7 +8,9 @@ reference's optimizer swaps one constructor.  The sum of squares behind the norm
 (``FlatParams.pack_grads``) where the flat gradient is final there, or out of one more launch where it was all-reduced afterwards.
 With a learning-rate table (engine.py:24-56) and / or a no-decay mask (optimizer.py:11-15, ``--filter_biases_wd``) the launch is
 ``vdetr_adamw_sched_f32``: the rate of every step is read on the device, indexed by the device-resident step count, so that a
-captured step follows the schedule.  GPU only, fp32 only: there is no CPU path.
+captured step follows the schedule.  ``step(skip=flag)`` is ``vdetr_adamw_guard_f32``: the same launch behind an int32 device word
+(the training loop's non-finite-loss flag, engine.LossMeter): nonzero, and the launch touches nothing.  GPU only, fp32 only: there is
+no CPU path.
 """
 import ctypes
 import math
@@ -155,17 +157,32 @@ class ClipAdamW(torch.optim.Optimizer):
         super().load_state_dict(state_dict)
         self._check_state()
 
+    @staticmethod
+    def _checked_skip(skip, dev):
+        if not (torch.is_tensor(skip) and skip.dtype == torch.int32):
+            raise ValueError(f"ClipAdamW: skip must be an int32 tensor, got {getattr(skip, 'dtype', type(skip))}")
+        if skip.numel() != 1:
+            raise ValueError(f"ClipAdamW: skip has {skip.numel()} elements, the launch reads one word")
+        if skip.device != dev:
+            raise ValueError(f"ClipAdamW: skip must be on {dev} (it is on {skip.device})")
+        return skip
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, skip=None):
+        """One launch.  ``skip``: an int32 device scalar (``engine.LossMeter.bad_flag``) that the launch reads first
+        (``vdetr_adamw_guard_f32``): nonzero leaves parameters, moments, step count, ``grad_norm`` and ``last_lr`` as they are; zero is
+        the step without ``skip``, bit for bit.  None: the unguarded launches."""
         if closure is not None:
             raise RuntimeError("ClipAdamW: closures are not supported")
         flat, lib = self.flat, L.lib()
+        if skip is not None:
+            skip = self._checked_skip(skip, flat.data.device)
         g = self.param_groups[0]
         st = self.state[flat.param]
         if st["step"].device != flat.data.device:
             raise RuntimeError(f"ClipAdamW: state['step'] is on {st['step'].device}, the kernel reads it on {flat.data.device}")
         sched = self.lr_schedule is not None or self.decay_mask is not None
-        d = L.AdamWSchedDesc() if sched else L.AdamWDesc()
+        d = L.AdamWGuardDesc() if skip is not None else L.AdamWSchedDesc() if sched else L.AdamWDesc()
         d.param, d.grad = flat.data.data_ptr(), flat.grad.data_ptr()
         d.exp_avg, d.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
         d.n = flat.data.numel()
@@ -185,7 +202,7 @@ class ClipAdamW(torch.optim.Optimizer):
             d.norm_out = self.grad_norm.data_ptr()
         d.lr, d.beta1, d.beta2 = float(g["lr"]), float(g["betas"][0]), float(g["betas"][1])
         d.eps, d.weight_decay = float(g["eps"]), float(g["weight_decay"])
-        if not sched:
+        if not sched and skip is None:
             L.check(lib.vdetr_adamw_clip_f32(ctypes.byref(d), L.stream_ptr()), "adamw_clip")
             return None
         if self.lr_schedule is not None:
@@ -193,5 +210,9 @@ class ClipAdamW(torch.optim.Optimizer):
         if self.decay_mask is not None:
             d.decay_mask = self.decay_mask.data_ptr()
         d.lr_out = self.last_lr.data_ptr()
+        if skip is not None:
+            d.skip = skip.data_ptr()
+            L.check(lib.vdetr_adamw_guard_f32(ctypes.byref(d), L.stream_ptr()), "adamw_guard")
+            return None
         L.check(lib.vdetr_adamw_sched_f32(ctypes.byref(d), L.stream_ptr()), "adamw_sched")
         return None
