@@ -1287,6 +1287,24 @@ int vdetr_det_append_f32(const vdetr_det_store* store, const uint8_t* keep, cons
 int vdetr_box3d_iou_max_idx_f64(const vdetr_det_store* store, int nboxes, int nscans, int ngt, int num_classes, double* ovmax,
                                 int32_t* jmax, int32_t* det_cls, float* det_score, vdetr_stream_t stream);
 
+/* The volume class of the size split of --test_size (utils/eval_det.py:62-67 box3d_vol_batch, :89-104): corners (n,8,3) f32 ->
+ * out (n) u8.  vol = (a * b) * c with a = sqrt((c0.z - c1.z)^2), b = sqrt((c1.x - c2.x)^2), c = sqrt((c0.y - c4.y)^2), every
+ * operation a rounded float32 operation as numpy does them, nothing contracted: for a rotated box this is NOT l w h, and it is
+ * the reference's number that is wanted.  With lo = (float)0.17 and hi = (float)0.44 (numpy compares a float32 array with a
+ * Python float in float32): 0 = S: vol < lo; 1 = M: lo < vol < hi; 2 = L: vol > hi; 3 = none: vol == lo, vol == hi or NaN. */
+int vdetr_box3d_size_class_f32(const float* corners, int n, uint8_t* out, vdetr_stream_t stream);
+
+/* vdetr_box3d_iou_max_idx_f64 restricted to the detection's own volume class: box_size (nboxes) u8 and gt_size (ngt) u8 are
+ * vdetr_box3d_size_class_f32 of the store's box_corners and gt_corners.  A ground-truth row g is a candidate of box row r only
+ * if gt_size[g] == box_size[r] (and of its class and scan, as before); a box of class 3 has none: ovmax = -inf, jmax = -1.
+ * This is a matching of its own, not a filter of the unrestricted one: a small detection whose best box overall is a medium
+ * one may still match a small box behind it.  One launch serves S, M and L, a detection belonging to at most one of them.
+ * Also -> det_size (P) u8 = box_size of the detection's row, in the same list order d.  Within the candidates it admits, the
+ * arithmetic and the first-of-equal-maxima rule are vdetr_box3d_iou_max_f64's, to the bit. */
+int vdetr_box3d_iou_max_size_f64(const vdetr_det_store* store, int nboxes, int nscans, int ngt, int num_classes,
+                                 const uint8_t* box_size, const uint8_t* gt_size, double* ovmax, int32_t* jmax, int32_t* det_cls,
+                                 float* det_score, uint8_t* det_size, vdetr_stream_t stream);
+
 /* Precision / recall curves and the VOC-12 average precision (utils/eval_det.py:23-56 voc_ap with use_07_metric=False,
  * :127-141) of C classes at T thresholds in one launch.  tp [T,P] u8: the true-positive flags in ranked order (class-major,
  * then descending score); seg [C+1] i32: class c owns ranks seg[c] .. seg[c+1]-1; npos [C] i32: its ground-truth boxes.

@@ -10,7 +10,11 @@ about 20 are present.  The queries cluster around 48 objects per scene (20 of th
   (b) ``compute_metrics`` over ``--batches`` such batches.
 
 The two paths alternate, ``--rounds`` times each; medians and the spread are printed.
-python tools/eval_loop_bench.py --steps 39 --warmup 5"""
+python tools/eval_loop_bench.py --steps 39 --warmup 5
+
+``--sizes`` runs one other leg instead: the S / M / L metrics of ``--test_size`` on the same batches, read-back of
+the store plus host path three times against one ``compute_metrics_by_size()``.
+python tools/eval_loop_bench.py --sizes"""
 import argparse
 import json
 import os
@@ -55,6 +59,63 @@ def make_batch(seed, dev):
     return {"outputs": {k: v.to(dev) for k, v in out.items()}}, {k: v.to(dev) for k, v in tgt.items()}
 
 
+def sizes_leg(a, make, batches):
+    """--sizes: the S / M / L metrics of --test_size over ``--batches`` batches in a resident calculator.
+    (a) the route taken before the device path existed: per size the store is read back, expanded into per-scan tuples and handed
+        to the host path (numpy filter, upload, vdetr_box3d_iou_max_f64, curves in numpy) — three times;
+    (b) one ``compute_metrics_by_size()``: one matching launch and one AP launch for all three, two host reads."""
+    from vdetr_amd.eval_store import expand_host, size_classes
+    sizes = ("S", "M", "L")
+    calc = make(True)
+    for i in range(a.batches):
+        calc.step_meter(*batches[i % len(batches)])
+    store = calc._store
+    kept = store.read_counters()
+    count = lambda corners, n: torch.bincount(size_classes(corners, n).long(), minlength=4).cpu().tolist()  # noqa: E731
+    det_sizes, gt_sizes = count(store.box_corners, kept[0]), count(store.gt_corners, kept[1])
+
+    def read_back():
+        host, ret = make(False), {}
+        for size in sizes:
+            host._flat_pred, host._flat_gt = expand_host(store.to_host(), calc._num_classes, calc._per_class)
+            host.scan_cnt = calc.scan_cnt
+            ret[size] = host.compute_metrics(size)
+        return ret
+
+    def one_pass():
+        calc._size_cache = None
+        return calc.compute_metrics_by_size()
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ret = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, ret
+
+    for _ in range(max(1, a.warmup // 5)):     # every shape once, untimed
+        read_back(), one_pass()
+    ms, rets = {"read_back": [], "one_pass": []}, {}
+    for _ in range(a.rounds):
+        for name, fn in (("read_back", read_back), ("one_pass", one_pass)):
+            t, rets[name] = timed(fn)
+            ms[name].append(t)
+    same = all(abs(float(rets["read_back"][s][t][k]) - float(rets["one_pass"][s][t][k])) <= 1e-6
+               for s in sizes for t in rets["read_back"][s] for k in rets["read_back"][s][t])
+    med = {n: statistics.median(v) for n, v in ms.items()}
+    span = lambda v: f"{min(v):.1f}-{max(v):.1f}"  # noqa: E731
+    print(f"eval_loop_bench --sizes: {B} scenes x {K} queries x {C} classes per batch, {a.batches} batches; {a.rounds} alternating rounds "
+          f"behind {max(1, a.warmup // 5)} untimed; wall time, synchronised at both ends")
+    print(f"store: {kept[0]} kept boxes, {kept[1]} ground-truth boxes, {kept[2]} scans; detections = boxes x {C} classes")
+    print(f"boxes in S / M / L / none: {det_sizes}; ground-truth boxes in S / M / L / none: {gt_sizes}")
+    print(f"(a) three compute_metrics(size), store read back + host path: median {med['read_back']:.1f} ms (rounds {span(ms['read_back'])})")
+    print(f"(b) one compute_metrics_by_size() on the device:              median {med['one_pass']:.1f} ms (rounds {span(ms['one_pass'])})")
+    print(f"(a) / (b) = {med['read_back'] / med['one_pass']:.1f}; metrics of the two routes agree to 1e-6: {same}")
+    print(json.dumps({"tool": "eval_loop_bench", "leg": "sizes", "batches": a.batches, "rounds": a.rounds, "kept_boxes": kept[0],
+                      "boxes_by_size": det_sizes, "gt_by_size": gt_sizes, "read_back_ms": med["read_back"], "one_pass_ms": med["one_pass"],
+                      "same_metrics": bool(same)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=39, help="timed batches per round of (a)")
@@ -62,6 +123,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--batches", type=int, default=39, help="batches behind compute_metrics in (b)")
     ap.add_argument("--forward-ms", type=float, default=2.0, help="device time of the stand-in forward in front of every step_meter")
+    ap.add_argument("--sizes", action="store_true", help="only the size-split leg: S / M / L metrics, store read-back against one device pass")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "eval_loop_bench needs a GPU"
     dev = torch.device("cuda")
@@ -69,6 +131,8 @@ def main():
     batches = [make_batch(s, dev) for s in range(4)]
     make = lambda resident: APCalculator(dataset_config=cfg_ds, ap_iou_thresh=[0.25, 0.5], resident=resident,  # noqa: E731
                                          ap_config_dict=get_ap_config_dict(dataset_config=cfg_ds, remove_empty_box=False))
+    if a.sizes:
+        return sizes_leg(a, make, batches)
 
     # the stand-in forward: as many 2048^2 products as take --forward-ms on this device
     w = torch.randn(2048, 2048, device=dev)

@@ -537,6 +537,8 @@ _SIGNATURES = {
     "vdetr_box3d_iou_pairs_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vdetr_det_append_f32": (c_int, [ctypes.POINTER(DetStore)] + [c_void_p] * 7 + [c_int] * 4 + [c_void_p]),
     "vdetr_box3d_iou_max_idx_f64": (c_int, [ctypes.POINTER(DetStore)] + [c_int] * 4 + [c_void_p] * 5),
+    "vdetr_box3d_size_class_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "vdetr_box3d_iou_max_size_f64": (c_int, [ctypes.POINTER(DetStore)] + [c_int] * 4 + [c_void_p] * 8),
     "vdetr_voc_ap_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vdetr_morton_sort_max": (c_int, []),
     "vdetr_morton_order_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -198,6 +198,7 @@ class APCalculator(object):
         self.scan_cnt = 0
         self._store = None       # eval_store.DetectionStore of a resident calculator (made by the first step: device, S)
         self._last_result = None  # [T,4,C] result buffer of the last resident compute_metrics
+        self._size_cache = None   # eval_store.evaluate_sizes of a resident calculator: S, M and L from one pass
 
     def make_gt_list(self, gt_box_corners, gt_box_sem_cls_labels, gt_box_present):
         return [[(gt_box_sem_cls_labels[i, j].item(), gt_box_corners[i, j]) for j in range(gt_box_corners.shape[1])
@@ -216,6 +217,7 @@ class APCalculator(object):
 
     def step(self, predicted_box_corners, sem_cls_probs, objectness_probs, angle_probs, point_cloud, gt_box_corners,
              gt_box_sem_cls_labels, gt_box_present, predicted_box_CSA):
+        self._size_cache = None
         if self.resident:
             return self._step_resident(predicted_box_corners, sem_cls_probs, objectness_probs, angle_probs, point_cloud,
                                        gt_box_corners, gt_box_sem_cls_labels, gt_box_present, predicted_box_CSA)
@@ -249,16 +251,14 @@ class APCalculator(object):
             raise ValueError("accumulate() takes host lists: a resident APCalculator keeps its detections on the device (use step / "
                              "step_meter, or resident=False)")
         assert len(batch_pred_map_cls) == len(batch_gt_map_cls)
+        self._size_cache = None
         for pred, gt in zip(batch_pred_map_cls, batch_gt_map_cls):
             self.gt_map_cls[self.scan_cnt] = gt
             self.pred_map_cls[self.scan_cnt] = pred
             self.scan_cnt += 1
 
     def _flat_arrays(self):
-        flat_pred, flat_gt = self._flat_pred, self._flat_gt
-        if self.resident and self._store is not None:    # the store read back, in the form step() keeps
-            from .eval_store import expand_host
-            flat_pred, flat_gt = expand_host(self._store.to_host(), self._num_classes, self._per_class)
+        flat_pred, flat_gt = self._flat_pred, self._flat_gt    # (a resident calculator never comes here: its store stays on the device)
         pc, pi, pk, ps, gc, gi, gk = [], [], [], [], [], [], []
         for scan in range(self.scan_cnt):
             if scan in flat_pred:
@@ -314,13 +314,45 @@ class APCalculator(object):
         self._last_result = res["result"]
         return res
 
+    SIZES = ("S", "M", "L")
+
+    def _resident_sizes(self, curves=False):
+        """S, M and L of a resident calculator from ONE pass (eval_store.evaluate_sizes), kept until the next step / reset"""
+        from .eval_store import evaluate_sizes
+        if self._store is None:
+            raise RuntimeError("compute_metrics on a resident APCalculator before the first step")
+        if self._size_cache is None or (curves and self._size_cache["rec"] is None):
+            self._size_cache = evaluate_sizes(self._store, list(self.ap_iou_thresh), self._num_classes, self._per_class, curves)
+        return self._size_cache
+
+    def _size_index(self, size):
+        if size not in self.SIZES:
+            raise ValueError(f"size must be '', 'S', 'M' or 'L', not {size!r}")
+        return self.SIZES.index(size)
+
+    def compute_metrics_by_size(self):
+        """OrderedDict("S", "M", "L") of ``compute_metrics(size)`` (main.py:462-480): one pass on a resident calculator."""
+        from collections import OrderedDict
+        return OrderedDict((size, self.compute_metrics(size)) for size in self.SIZES)
+
     def compute_metrics(self, size=""):
         """{threshold: {"<class> Average Precision", ..., "mAP", "<class> Recall", ..., "AR"}}.  A resident calculator computes
         them on the device with two host reads (the store's counters, then one [T,4,C] buffer).  ``size`` = "S" / "M" / "L" is a
-        numpy-precision volume filter (eval_det.py:64-69, :90): a resident calculator then reads its store back and takes the
-        host path."""
+        numpy-precision volume filter (eval_det.py:64-69, :90) of detections and ground truth; a resident calculator computes all
+        three on the first such call, again with two host reads, and serves the other two from that result.
+        The keys of a size's dictionary are those of the unfiltered data."""
         from collections import OrderedDict
         overall_ret = OrderedDict()
+        if self.resident and size != "":
+            k = self._size_index(size)
+            res = self._resident_sizes()
+            ndet_all, npos_all = res["present"]
+            keys = [c for c in range(len(ndet_all)) if ndet_all[c] > 0 or npos_all[c] > 0]
+            for t, thr in enumerate(self.ap_iou_thresh):
+                ap_row, rec_row, ndet, _ = res["result"][k][t]
+                overall_ret[thr] = self._metrics({c: ap_row[c] if ndet[c] > 0 else 0 for c in keys},
+                                                 {c: rec_row[c] if ndet[c] > 0 else 0 for c in keys})
+            return overall_ret
         if self.resident and size == "":
             result = self._resident_eval()["result"]
             for t, thr in enumerate(self.ap_iou_thresh):
@@ -335,26 +367,59 @@ class APCalculator(object):
             overall_ret[thr] = self._metrics(ap, last)
         return overall_ret
 
-    def _ranking(self):
+    def _ranking(self, size=""):
         """{threshold: (order, tp)}: the detections' indices (insertion order over all scans) ranked by (class, descending score,
-        insertion) and the true-positive flag of every rank — what the precision / recall curves are counted from (tests)."""
+        insertion) and the true-positive flag of every rank — what the precision / recall curves are counted from (tests).
+        Under a ``size`` only that size's detections are ranked; ``order`` still indexes the unfiltered list."""
+        if self.resident and size != "":
+            k, C = self._size_index(size), self._num_classes
+            res = self._resident_sizes()
+            seg = res["seg"].cpu().numpy()
+            ranks = slice(int(seg[k * C]), int(seg[(k + 1) * C]))
+            order, tp = res["order"].cpu().numpy()[ranks], res["tp"].cpu().numpy().astype(bool)[:, ranks]
+            return {thr: (order, tp[t]) for t, thr in enumerate(self.ap_iou_thresh)}
         if self.resident:
             res = self._resident_eval()
             order, tp = res["order"].cpu().numpy(), res["tp"].cpu().numpy().astype(bool)
             return {thr: (order, tp[t]) for t, thr in enumerate(self.ap_iou_thresh)}
         from .eval_det import match_detections
         pc, pi, pk, ps, gc, gi, gk = self._flat_arrays()
+        index = np.arange(len(ps))
+        if size != "":
+            from .eval_det import _size_filter, _volumes
+            self._size_index(size)
+            keep_p, keep_g = _size_filter(_volumes(pc), size), _size_filter(_volumes(gc), size)
+            pc, pi, pk, ps, gc, gi, gk, index = pc[keep_p], pi[keep_p], pk[keep_p], ps[keep_p], gc[keep_g], gi[keep_g], gk[keep_g], index[keep_p]
         g_order = np.argsort(gi, kind="stable")
         out = {}
         for thr in self.ap_iou_thresh:
-            order, tp = match_detections(pc, pi, pk, ps, gc[g_order], gi[g_order], gk[g_order], self.scan_cnt, thr)
-            out[thr] = (order, tp[order])
+            if len(ps):
+                order, tp = match_detections(pc, pi, pk, ps, gc[g_order], gi[g_order], gk[g_order], self.scan_cnt, thr)
+            else:
+                order, tp = np.zeros(0, np.int64), np.zeros(0, bool)
+            out[thr] = (index[order], tp[order])
         return out
 
-    def _curves(self):
+    def _curves(self, size=""):
         """{threshold: (rec, prec, ap)} keyed by integer class label, a class without detection holding 0 (tests)."""
         if not self.resident:
-            return self._host_curves()
+            return self._host_curves(size)
+        if size != "":
+            k, C = self._size_index(size), self._num_classes
+            res = self._resident_sizes(curves=True)
+            seg, rec_all, prec_all = res["seg"].cpu().numpy()[k * C:], res["rec"].cpu().numpy(), res["prec"].cpu().numpy()
+            ndet_all, npos_all = res["present"]
+            out = {}
+            for t, thr in enumerate(self.ap_iou_thresh):
+                ap_row, _, ndet, _ = res["result"][k][t]
+                rec, prec, ap = {}, {}, {}
+                for c in range(C):
+                    if ndet[c] > 0:
+                        rec[c], prec[c], ap[c] = rec_all[t, seg[c]:seg[c + 1]], prec_all[t, seg[c]:seg[c + 1]], ap_row[c]
+                    elif ndet_all[c] > 0 or npos_all[c] > 0:
+                        rec[c] = prec[c] = ap[c] = 0
+                out[thr] = (rec, prec, ap)
+            return out
         res = self._resident_eval(curves=True)
         seg, rec_all, prec_all = res["seg"].cpu().numpy(), res["rec"].cpu().numpy(), res["prec"].cpu().numpy()
         out = {}

@@ -5,7 +5,8 @@
 // the kept boxes as per-scan lists.  Here the kept boxes and the present ground-truth boxes of a batch are appended to a
 // store whose arrays AND cursors are device memory (vdetr_det_store), so that a step of the evaluation loop reads nothing
 // back; the matching over the store is vdetr_box3d_iou_max_idx_f64 (nms.hip, next to the clip routine) and the curves and
-// the average precision of every class and threshold are ONE launch here (vdetr_voc_ap_f64).
+// the average precision of every class and threshold are ONE launch here (vdetr_voc_ap_f64).  The size split of --test_size
+//  reuses that launch over 3C (size, class) segments; its volume classes and its matching are in nms.hip too.
 //
 // Append = two launches.  `rows`: grid (tiles of 256 boxes + tiles of 256 ground-truth boxes, B); a workgroup counts the
 // flags in front of its tile (all earlier scenes and the earlier tiles of its own: at most B*K bytes), adds the cursor it

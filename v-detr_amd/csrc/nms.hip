@@ -353,9 +353,16 @@ __global__ __launch_bounds__(128) void box3d_iou_max_kernel(const float* __restr
 // d = C box_begin[s] + c n_s + (r - box_begin[s]) of the reference's per-scan class-major list order, with its class and
 // score.  The loop over the scan's ground truth is box3d_iou_max_kernel's, expression for expression.  Everything read from
 // the store is device data: rows and scans outside the host's counts write nothing.
+//
+// kSized (vdetr_box3d_iou_max_size_f64): the size split of --test_size.  box_size / gt_size hold the volume class of
+// every box row and ground-truth row (box3d_size_class_kernel below); a ground-truth row is a candidate only if it is of the
+// box's class, a box of class 3 (on a bound, or NaN) has no candidate, and det_size[d] is the box's class.
+template <bool kSized>
 __global__ __launch_bounds__(128) void box3d_iou_max_idx_kernel(vdetr_det_store st, int nboxes, int nscans, int ngt, int C,
-                                                                double* __restrict__ ovmax, int* __restrict__ jmax,
-                                                                int* __restrict__ det_cls, float* __restrict__ det_score) {
+                                                                const uint8_t* __restrict__ box_size,
+                                                                const uint8_t* __restrict__ gt_size, double* __restrict__ ovmax,
+                                                                int* __restrict__ jmax, int* __restrict__ det_cls,
+                                                                float* __restrict__ det_score, uint8_t* __restrict__ det_size) {
   const int per = C > 0 ? C : 1;
   const long e = (long)blockIdx.x * 128 + threadIdx.x;
   if (e >= (long)nboxes * per) return;
@@ -372,9 +379,11 @@ __global__ __launch_bounds__(128) void box3d_iou_max_idx_kernel(vdetr_det_store 
   const double vol1 = box3d_vol64(c1);
   double best = -INFINITY;
   int arg = -1;
-  const int g0 = max(st.gt_begin[s], 0), g1 = min(st.gt_begin[s + 1], ngt);
+  const int size = kSized ? box_size[r] : 0;
+  const int g0 = max(st.gt_begin[s], 0), g1 = kSized && size > 2 ? g0 : min(st.gt_begin[s + 1], ngt);
   for (int g = g0; g < g1; ++g) {
     if (st.gt_cls[g] != cls) continue;
+    if (kSized && gt_size[g] != size) continue;
     float c2[24];
     for (int k = 0; k < 24; ++k) c2[k] = st.gt_corners[(size_t)g * 24 + k];
     const double area = footprint_intersection(c1, c2);
@@ -387,6 +396,22 @@ __global__ __launch_bounds__(128) void box3d_iou_max_idx_kernel(vdetr_det_store 
   jmax[d] = arg;
   det_cls[d] = cls;
   det_score[d] = st.box_scores[(size_t)r * st.S + (C > 0 ? c : 0)];
+  if (kSized) det_size[d] = (uint8_t)size;
+}
+
+// The volume class of the size split (utils/eval_det.py:62-67 box3d_vol_batch, :89-104): three axis differences of the float32
+// corners, every operation a rounded float32 operation as numpy does them (the library is built with -ffp-contract=off), compared
+// with the float32 bounds.  0 = S, 1 = M, 2 = L, 3 = none (a volume equal to a bound, or NaN).
+__global__ __launch_bounds__(256) void box3d_size_class_kernel(const float* __restrict__ corners, int n, uint8_t* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float* c = corners + (size_t)i * 24;
+  const float dz = c[2] - c[5], dx = c[3] - c[6], dy = c[1] - c[13];
+  // sqrtf is the correctly rounded square root here; HIP's __fsqrt_rn is the hardware approximation
+  const float a = sqrtf(dz * dz), b = sqrtf(dx * dx), h = sqrtf(dy * dy);
+  const float vol = (a * b) * h;
+  const float lo = (float)0.17, hi = (float)0.44;
+  out[i] = vol < lo ? 0 : (vol > lo && vol < hi) ? 1 : vol > hi ? 2 : 3;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -593,7 +618,36 @@ extern "C" int vdetr_box3d_iou_max_idx_f64(const vdetr_det_store* store, int nbo
   VDETR_REQUIRE(s.box_corners && s.box_scores && s.box_cls && s.box_scan && s.box_begin && s.gt_begin && ovmax && jmax &&
                     det_cls && det_score && (ngt == 0 || (s.gt_corners && s.gt_cls)),
                 "box3d_iou_max_idx: null pointer");
-  hipLaunchKernelGGL(box3d_iou_max_idx_kernel, dim3(ceil_div(P, 128)), dim3(128), 0, (hipStream_t)stream, s, nboxes, nscans, ngt,
-                     num_classes, ovmax, jmax, det_cls, det_score);
+  hipLaunchKernelGGL(box3d_iou_max_idx_kernel<false>, dim3(ceil_div(P, 128)), dim3(128), 0, (hipStream_t)stream, s, nboxes, nscans,
+                     ngt, num_classes, nullptr, nullptr, ovmax, jmax, det_cls, det_score, nullptr);
   return check_launch("box3d_iou_max_idx");
+}
+
+extern "C" int vdetr_box3d_iou_max_size_f64(const vdetr_det_store* store, int nboxes, int nscans, int ngt, int num_classes,
+                                            const uint8_t* box_size, const uint8_t* gt_size, double* ovmax, int32_t* jmax,
+                                            int32_t* det_cls, float* det_score, uint8_t* det_size, vdetr_stream_t stream) {
+  VDETR_REQUIRE(store, "box3d_iou_max_size: null store");
+  const vdetr_det_store& s = *store;
+  VDETR_REQUIRE(nboxes >= 0 && nscans >= 0 && ngt >= 0 && num_classes >= 0, "box3d_iou_max_size: negative count");
+  VDETR_REQUIRE(nboxes <= s.box_capacity && nscans <= s.scan_capacity && ngt <= s.gt_capacity,
+                "box3d_iou_max_size: %d boxes, %d scans, %d ground-truth boxes exceed the store's %d, %d, %d", nboxes, nscans, ngt,
+                s.box_capacity, s.scan_capacity, s.gt_capacity);
+  VDETR_REQUIRE(s.S >= (num_classes > 0 ? num_classes : 1), "box3d_iou_max_size: %d scores per box < %d classes", s.S, num_classes);
+  const long P = (long)nboxes * (num_classes > 0 ? num_classes : 1);
+  VDETR_REQUIRE(P < ((long)1 << 31), "box3d_iou_max_size: %ld detections >= 2^31", P);
+  if (P == 0) return VDETR_OK;
+  VDETR_REQUIRE(s.box_corners && s.box_scores && s.box_cls && s.box_scan && s.box_begin && s.gt_begin && box_size && ovmax && jmax &&
+                    det_cls && det_score && det_size && (ngt == 0 || (s.gt_corners && s.gt_cls && gt_size)),
+                "box3d_iou_max_size: null pointer");
+  hipLaunchKernelGGL(box3d_iou_max_idx_kernel<true>, dim3(ceil_div(P, 128)), dim3(128), 0, (hipStream_t)stream, s, nboxes, nscans,
+                     ngt, num_classes, box_size, gt_size, ovmax, jmax, det_cls, det_score, det_size);
+  return check_launch("box3d_iou_max_size");
+}
+
+extern "C" int vdetr_box3d_size_class_f32(const float* corners, int n, uint8_t* out, vdetr_stream_t stream) {
+  VDETR_REQUIRE(n >= 0, "box3d_size_class: negative count");
+  if (n == 0) return VDETR_OK;
+  VDETR_REQUIRE(corners && out, "box3d_size_class: null pointer");
+  hipLaunchKernelGGL(box3d_size_class_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, corners, n, out);
+  return check_launch("box3d_size_class");
 }

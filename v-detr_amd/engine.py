@@ -1,5 +1,5 @@
-"""The reference's control plane (engine.py:24-193): ``train_one_epoch``, ``evaluate`` — what ``--test_only`` runs on a checkpoint —
-and the learning-rate helpers.  Both loops are eager; a captured (hipGraph) training step is NOT built here.
+"""The reference's control plane (engine.py:24-193): ``train_one_epoch``, ``evaluate``, ``test_model`` (main.py:437-480: what
+``--test_only`` runs on a checkpoint, with the S / M / L metrics of ``--test_size``) and the learning-rate helpers.  Both loops are eager; a captured (hipGraph) training step is NOT built here.
 
 ``evaluate`` is the reference's loop, statement for statement: batch to the model's device, ``model(inputs)`` on the three input
 keys, the loss when a criterion is given, ``sigmoid`` for the focal-loss heads, ``all_gather_dict`` on outputs and batch, the
@@ -19,6 +19,7 @@ import ctypes
 import datetime
 import logging
 import math
+import os
 import sys
 import time
 from collections import deque
@@ -286,3 +287,28 @@ def evaluate(args, curr_epoch, model, criterion, dataset_config, dataset_loader,
     # the one read of the losses: the float32 mean of the window, on the host as SmoothedValue.avg takes it
     loss_avg = torch.stack(list(last_losses)).to(torch.float32).cpu().mean().item() if last_losses else 0.0
     return ap_calculator, loss_avg, loss_dict_reduced
+
+
+def test_model(args, model, model_no_ddp, criterion, dataset_config, dataloaders):
+    """main.py:437-480, same arguments: the ``--test_only`` entry.  Loads ``args.test_ckpt`` (the layout of utils/io.py:23-29:
+    model, optimizer, epoch, args, best_val_metrics) into ``model_no_ddp``, runs ``evaluate`` on ``dataloaders["test"]`` without
+    a criterion and prints the metrics, and with ``args.test_size`` those of the S, M and L volume classes, which come from one
+    device pass (``APCalculator.compute_metrics_by_size``).  -> {"": metrics, "S": ..., "M": ..., "L": ...} as
+    printed (the reference returns None)."""
+    if args.test_ckpt is None or not os.path.isfile(args.test_ckpt):
+        print(f"Please specify a test checkpoint using --test_ckpt. Found invalid value {args.test_ckpt}")
+        sys.exit(1)
+    # the reference's checkpoints carry an argparse.Namespace and the numpy scalars of best_val_metrics: a full unpickle, as
+    # the reference does it; a checkpoint is trusted like the code that reads it
+    sd = torch.load(args.test_ckpt, map_location=torch.device("cpu"), weights_only=False)
+    model_no_ddp.load_state_dict(sd["model"], strict=False)
+    ap_calculator, _, _ = evaluate(args, -1, model, None, dataset_config, dataloaders["test"], 0)   # no loss, for speed
+    ret = {"": ap_calculator.compute_metrics()}
+    if getattr(args, "test_size", False):
+        ret.update(ap_calculator.compute_metrics_by_size())
+    for size, metrics in ret.items():
+        if is_primary():
+            print("==" * 10)
+            print(f"Test model{' ' + size if size else ''}; Metrics {ap_calculator.metrics_to_str(metrics)}")
+            print("==" * 10)
+    return ret

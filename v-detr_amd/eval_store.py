@@ -12,6 +12,10 @@ the launches) and one ``[T, 4, C]`` buffer of results.  In between: ONE matching
 jmax do not depend on the threshold), the ranking by two stable library sorts and the claim rule by a scatter-min as in
 ``eval_det.match_detections`` (written without boolean indexing, which would read a count back), and one
 ``vdetr_voc_ap_f64`` launch.  GPU only: there is no CPU path.
+
+``evaluate_sizes`` is the same for the size split of ``--test_size``: every stored box gets its volume class on the
+device (``vdetr_box3d_size_class_f32``), ONE size-restricted matching launch serves S, M and L (``vdetr_box3d_iou_max_size_f64``) and
+``vdetr_voc_ap_f64`` runs once over ``3C`` (size, class) segments — again two host reads, and no read-back of the store.
 """
 import ctypes
 
@@ -116,7 +120,7 @@ class DetectionStore:
                                f"small ({counts[0]} were kept)")
 
     def to_host(self):
-        """The store's rows as numpy arrays (the size-split metrics and the tests read it back):
+        """The store's rows as numpy arrays (tests and tools/eval_loop_bench.py read it back; no metric does):
         dict(counts, box_corners, box_scores, box_cls, box_scan, box_begin, gt_corners, gt_cls, gt_begin)."""
         counts = self.read_counters()
         self.require_complete(counts)
@@ -196,9 +200,92 @@ def evaluate(store, thresholds, num_classes, per_class, curves=False):
     return dict(result=out.cpu().numpy(), order=order, tp=tp, rec=rec, prec=prec, seg=seg)        # host read 2
 
 
+def size_classes(corners, n):
+    """vdetr_box3d_size_class_f32 of the first n rows of corners [.,8,3] f32 -> [n] u8: 0 = S, 1 = M, 2 = L, 3 = none (the
+    reference's box3d_vol_batch in float32 against float32(0.17) and float32(0.44); a volume on a bound belongs to no size)."""
+    assert corners.dtype == torch.float32 and corners.is_contiguous() and corners.shape[0] >= n and corners.shape[1:] == (8, 3)
+    out = torch.empty(n, dtype=torch.uint8, device=corners.device)
+    L.check(L.lib().vdetr_box3d_size_class_f32(L.ptr(corners), n, L.ptr(out), L.stream_ptr()), "box3d_size_class")
+    return out
+
+
+def match_store_sizes(store, nboxes, nscans, ngt, num_classes, box_size, gt_size):
+    """vdetr_box3d_iou_max_size_f64: ``match_store`` with every detection competing for the ground truth of its own volume class
+    only -> (ovmax, jmax, class, score, size class [P] u8)."""
+    global MATCH_LAUNCHES
+    P = nboxes * max(num_classes, 1)
+    dev = store.device
+    ovmax = torch.empty(P, dtype=torch.float64, device=dev)
+    jmax = torch.empty(P, dtype=torch.int32, device=dev)
+    det_cls = torch.empty(P, dtype=torch.int32, device=dev)
+    det_score = torch.empty(P, dtype=torch.float32, device=dev)
+    det_size = torch.empty(P, dtype=torch.uint8, device=dev)
+    MATCH_LAUNCHES += 1
+    L.check(L.lib().vdetr_box3d_iou_max_size_f64(ctypes.byref(store.desc()), nboxes, nscans, ngt, num_classes, L.ptr(box_size),
+                                                 L.ptr(gt_size), L.ptr(ovmax), L.ptr(jmax), L.ptr(det_cls), L.ptr(det_score),
+                                                 L.ptr(det_size), L.stream_ptr()), "box3d_iou_max_size")
+    return ovmax, jmax, det_cls, det_score, det_size
+
+
+def evaluate_sizes(store, thresholds, num_classes, per_class, curves=False):
+    """``evaluate`` under the reference's size split (``--test_size``), S, M and L in one pass: segment k * C + c of the ranking
+    holds size class k (0 = S, 1 = M, 2 = L), class c.  -> dict(result [3,T,4,C] numpy f64 = per size AP, last recall, number of
+    detections, npos; present [2,C] numpy f64 = detections and ground-truth boxes of every class BEFORE the filter (the keys of
+    every size's dictionary, eval_det.py:259-299); order [P], tp [T,P], seg [3C+1], rec / prec as ``evaluate`` gives them, the
+    detections of no size ranked behind seg[3C]).  Host reads: the counters, then one buffer holding result and present."""
+    counts = store.read_counters()                                          # host read 1
+    store.require_complete(counts)
+    nboxes, ngt, nscans, _ = counts
+    dev, C, T = store.device, int(num_classes), len(thresholds)
+    P = nboxes * (C if per_class else 1)
+    classes = torch.arange(C + 1, dtype=torch.int32, device=dev)
+    keys = torch.arange(3 * C + 1, dtype=torch.int32, device=dev)
+    in_range = lambda cls: (cls >= 0) & (cls < C)  # noqa: E731
+    gt_cls = store.gt_cls[:ngt]
+    gt_size = size_classes(store.gt_corners, ngt)
+    gseg = torch.searchsorted(torch.sort(gt_cls)[0], classes)
+    gkey = torch.where((gt_size < 3) & in_range(gt_cls), gt_size.to(torch.int32) * C + gt_cls, 3 * C)   # no size: behind 3C
+    gkseg = torch.searchsorted(torch.sort(gkey)[0], keys)
+    npos = (gkseg[1:] - gkseg[:-1]).to(torch.int32)
+    if per_class:       # every box is a detection of every class
+        ndet_all = torch.full((C,), float(nboxes), dtype=torch.float64, device=dev)
+    else:
+        bseg = torch.searchsorted(torch.sort(store.box_cls[:nboxes])[0], classes)
+        ndet_all = (bseg[1:] - bseg[:-1]).to(torch.float64)
+    if P > 0:
+        box_size = size_classes(store.box_corners, nboxes)
+        ovmax, jmax, det_cls, det_score, det_size = match_store_sizes(store, nboxes, nscans, ngt, C if per_class else 0, box_size,
+                                                                      gt_size)                 # once for all sizes and thresholds
+        dkey = torch.where((det_size < 3) & in_range(det_cls), det_size.to(torch.int32) * C + det_cls, 3 * C)
+        o1 = torch.sort(-det_score, stable=True)[1]          # rank: (size, class)-major, then as ``evaluate``
+        key_sorted, o2 = torch.sort(dkey[o1], stable=True)
+        order = o1[o2]
+        rank = torch.empty(P, dtype=torch.int64, device=dev)
+        rank[order] = torch.arange(P, device=dev)
+        seg = torch.searchsorted(key_sorted, keys).to(torch.int32)
+        j = jmax.long()
+        tps = []
+        for thr in thresholds:   # a box and the detections that can claim it are of one size: the claim rule needs no change
+            hit = ovmax > thr
+            slot = torch.where(hit, j, ngt)
+            claim = torch.full((ngt + 1,), P, dtype=torch.int64, device=dev)
+            claim.scatter_reduce_(0, slot, torch.where(hit, rank, P), reduce="amin")
+            tps.append((hit & (claim[slot] == rank))[order])
+        tp = torch.stack(tps).view(torch.uint8)
+    else:
+        order = torch.zeros(0, dtype=torch.int64, device=dev)
+        tp = torch.zeros((T, 0), dtype=torch.uint8, device=dev)
+        seg = torch.zeros(3 * C + 1, dtype=torch.int32, device=dev)
+    out, rec, prec = voc_ap(tp, seg, npos, curves)                          # [T,4,3C]
+    packed = torch.cat((out.reshape(-1), ndet_all, (gseg[1:] - gseg[:-1]).to(torch.float64))).cpu().numpy()   # host read 2
+    result = np.ascontiguousarray(packed[:T * 4 * 3 * C].reshape(T, 4, 3, C).transpose(2, 0, 1, 3))
+    return dict(result=result, present=packed[T * 4 * 3 * C:].reshape(2, C), order=order, tp=tp, rec=rec, prec=prec, seg=seg)
+
+
 def expand_host(host, num_classes, per_class):
     """``DetectionStore.to_host()`` -> per scan the tuples ``ap_calculator.detections_flat`` makes (corners [n,8,3], classes [m],
-    box index [m], scores [m]) and (ground-truth classes [g], corners [g,8,3])."""
+    box index [m], scores [m]) and (ground-truth classes [g], corners [g,8,3]): what a host calculator's ``_flat_pred`` / ``_flat_gt``
+    hold.  The size split went this way before ``evaluate_sizes``; tools/eval_loop_bench.py --sizes still times it."""
     preds, gts = {}, {}
     bb, gb = host["box_begin"], host["gt_begin"]
     for s in range(host["counts"][2]):
