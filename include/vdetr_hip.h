@@ -1516,6 +1516,72 @@ typedef struct vdetr_sp_take_rows_desc {
 } vdetr_sp_take_rows_desc;
 int vdetr_sp_take_rows_f32(const vdetr_sp_take_rows_desc* d, vdetr_stream_t stream);
 
+/* Voxelisation: raw points -> the sites of tensor stride 1 with the maps of the quantisation modes.
+ *
+ * Keys, one launch.  points != NULL: packed points [N, >= 3] f32 with `stride` floats per row, offsets [B + 1] i32 on the device
+ * (scene b holds rows offsets[b] .. offsets[b+1]; empty scenes allowed), 1 <= B <= 32768.  The voxel index of a coordinate is
+ * floorf(p * (float)(1.0 / voxel_size)), the reciprocal taken in double and rounded to float32 once on the host: bit for bit what
+ * torch.floor(p / voxel_size).to(torch.int32) gives on the device for a Python-float divisor.  coords != NULL (points NULL):
+ * ready integer rows [N, 4] i32 (batch, x, y, z), 16-byte aligned; offsets / B / stride / voxel_size are not read.
+ * keys [N] i64 are the keys of vdetr_sp_kernel_map_i32.  A row that no key holds — an index outside -32768 .. 32767, a NaN or an
+ * infinite coordinate, a batch index outside 0 .. 32767 or a row outside every scene — gets the key -1: every legal key is
+ * non-negative, so the range flag travels in the keys and vdetr_sp_voxel_sites_i64 reports it.  No memset, no atomics. */
+typedef struct vdetr_sp_voxel_keys_desc {
+  int32_t N, B, stride;
+  double voxel_size; /* as the caller's Python float: the reciprocal is taken in double and rounded to float32 once */
+  const float* points;
+  const int32_t* offsets;
+  const int32_t* coords;
+  int64_t* keys;
+} vdetr_sp_voxel_keys_desc;
+int vdetr_sp_voxel_tile(void);
+int vdetr_sp_voxel_keys_f32(const vdetr_sp_voxel_keys_desc* d, vdetr_stream_t stream);
+
+/* Sites: from the keys sorted ascending by a STABLE sort and that sort's permutation `order` [N] i64 to
+ *   sites [M] i64 ascending and unique; inverse [N] i32 = the site row of every input row; first [M] i64 = the lowest input row of
+ *   each site; order32 [N] = the permutation as i32; seg [M + 1] i32 = the run starts in sorted order (seg[M] = N);
+ *   count[0] = M, count[1] = -1 if a key is negative (the range flag of vdetr_sp_voxel_keys_f32), else the highest batch
+ *   index + 1 (the last key holds it): the eight bytes a caller reads back.
+ * sites and first are allocated at the bound N, seg at N + 1.  Two launches (run heads and one count per tile of
+ * vdetr_sp_voxel_tile() keys; scan and fill), nothing waits between them; no atomics, no memset.  Runs may cross tiles and be
+ * longer than one.  Equal to np.unique(keys, return_index, return_inverse, return_counts).  N == 0: no-op (count untouched). */
+typedef struct vdetr_sp_voxel_sites_desc {
+  int32_t N;
+  const int64_t *sorted, *order;
+  int64_t *sites, *first;
+  int32_t *inverse, *order32, *seg;
+  int32_t* count; /* [2] */
+  void* workspace;
+} vdetr_sp_voxel_sites_desc;
+size_t vdetr_sp_voxel_sites_workspace_bytes(int N);
+int vdetr_sp_voxel_sites_i64(const vdetr_sp_voxel_sites_desc* d, vdetr_stream_t stream);
+
+/* y [M, C] = the fold of x [N, C] over the points of every site, in ascending input-row order, float32, any C >= 1:
+ *   SUM    +0 plus the rows, one add each        AVG   that sum, then ONE division by the count
+ *   MAX    np.maximum: a NaN wins, a tie keeps the lower row; arg [M, C] i32 = the winning input row
+ *   FIRST  the lowest row of the site (RANDOM_SUBSAMPLE)
+ * One lane per (site, channel); no atomics: two runs give the same bits.  order = order32, seg as written by the sites entry.
+ * The gradient is a gather through `inverse` [N]: dx[i] = dy[inverse[i]] (SUM), / count (AVG), dy where arg names row i and an
+ * exact zero elsewhere (MAX), dy on the site's first row and zero elsewhere (FIRST).  x / y are not read by it. */
+#define VDETR_VOXEL_SUM 0
+#define VDETR_VOXEL_AVG 1
+#define VDETR_VOXEL_MAX 2
+#define VDETR_VOXEL_FIRST 3
+typedef struct vdetr_sp_voxel_reduce_desc {
+  int32_t M, N, C, mode;
+  const float* x;
+  const int32_t *order, *seg;
+  float* y;
+  int32_t* arg; /* [M, C], MAX only */
+} vdetr_sp_voxel_reduce_desc;
+int vdetr_sp_voxel_reduce_f32(const vdetr_sp_voxel_reduce_desc* d, vdetr_stream_t stream);
+int vdetr_sp_voxel_reduce_grad_f32(const vdetr_sp_voxel_reduce_desc* d, const float* dy, const int32_t* inverse, float* dx,
+                                   vdetr_stream_t stream);
+
+/* out [M] i32: the label that all points of a site share, ignore_label where they differ (ME.utils.sparse_quantize). */
+int vdetr_sp_voxel_labels_i32(const int32_t* labels, const int32_t* order, const int32_t* seg, int M, int N, int ignore_label,
+                              int32_t* out, vdetr_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Fixed coordinate embeddings — PositionEmbeddingCoordsSine (models/position_embedding.py:21-148); one launch each.
  *   xyz (b,n,3); range_min / range_max (b,3) = the scene extent for `normalize=True` (shift_scale_points,

@@ -451,6 +451,29 @@ class SpTakeRowsDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("nrows", "nsrc", "C", "sign")] + [(n, c_void_p) for n in ("x", "idx", "y")]
 
 
+class SpVoxelKeysDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_voxel_keys_desc``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("N", "B", "stride")] + [("voxel_size", ctypes.c_double)] +
+                [(n, c_void_p) for n in ("points", "offsets", "coords", "keys")])
+
+
+class SpVoxelSitesDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_voxel_sites_desc``."""
+
+    _fields_ = [("N", ctypes.c_int32)] + [(n, c_void_p) for n in ("sorted", "order", "sites", "first", "inverse", "order32", "seg",
+                                                                  "count", "workspace")]
+
+
+class SpVoxelReduceDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_voxel_reduce_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("M", "N", "C", "mode")] + [(n, c_void_p) for n in ("x", "order", "seg", "y", "arg")]
+
+
+VDETR_VOXEL_SUM, VDETR_VOXEL_AVG, VDETR_VOXEL_MAX, VDETR_VOXEL_FIRST = 0, 1, 2, 3
+
+
 class DetStore(ctypes.Structure):
     """Mirror of ``vdetr_det_store``."""
 
@@ -602,6 +625,13 @@ _SIGNATURES = {
     "vdetr_sp_prune_map_i64": (c_int, [ctypes.POINTER(SpPruneMapDesc), c_void_p]),
     "vdetr_sp_union_add_f32": (c_int, [ctypes.POINTER(SpUnionAddDesc), c_void_p]),
     "vdetr_sp_take_rows_f32": (c_int, [ctypes.POINTER(SpTakeRowsDesc), c_void_p]),
+    "vdetr_sp_voxel_tile": (c_int, []),
+    "vdetr_sp_voxel_keys_f32": (c_int, [ctypes.POINTER(SpVoxelKeysDesc), c_void_p]),
+    "vdetr_sp_voxel_sites_workspace_bytes": (c_size_t, [c_int]),
+    "vdetr_sp_voxel_sites_i64": (c_int, [ctypes.POINTER(SpVoxelSitesDesc), c_void_p]),
+    "vdetr_sp_voxel_reduce_f32": (c_int, [ctypes.POINTER(SpVoxelReduceDesc), c_void_p]),
+    "vdetr_sp_voxel_reduce_grad_f32": (c_int, [ctypes.POINTER(SpVoxelReduceDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vdetr_sp_voxel_labels_i32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vdetr_rb_transpose_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vdetr_rb_qkv_f32": (c_int, [ctypes.POINTER(RbQkvDesc), c_void_p]),
     "vdetr_rb_proj_q_f32": (c_int, [ctypes.POINTER(RbProjQDesc), c_void_p]),

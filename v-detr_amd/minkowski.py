@@ -16,7 +16,9 @@ MinkowskiEngine is NOT under /root/reference (un-vendored): semantics follow its
   * ``a + b`` / ``a - b`` of tensors on DIFFERENT key sets (the skip add behind a generative convolution) live on the union of the
     sites, a side without a site counting as zero; ``MinkowskiUnion`` folds ``+``; ``MinkowskiPruning`` keeps the rows of a bool
     mask in order (DESIGN 6.11: this package's own statement);
-  * duplicated input coordinates keep one feature row (here: the first in input order), sites are held in key order.
+  * duplicated input coordinates keep one feature row (here: the first in input order) under the default
+    ``SparseTensorQuantizationMode.RANDOM_SUBSAMPLE``; UNWEIGHTED_AVERAGE / UNWEIGHTED_SUM / MAX_POOL fold the rows of a site in
+    ascending input order; sites are held in key order, which is also the row order of ``sparse_quantize``.
 The ORDER of the sites of a MinkowskiEngine tensor is an implementation detail of its hash map; here it is ascending
 (batch, x, y, z).  Parity against the MinkowskiEngine binary is unpinned; ``oracle/sparse_oracle.py`` pins the arithmetic
 against torch's dense convolutions.
@@ -196,6 +198,44 @@ def _kernel_offsets(kernel):
     return KernelGenerator(kernel, dimension=3).scaled_offsets()
 
 
+class SparseTensorQuantizationMode(enum.Enum):
+    """ME.SparseTensorQuantizationMode: what becomes of the feature rows of points that share a voxel"""
+    RANDOM_SUBSAMPLE = 0            # one row per site: here the first in input order
+    UNWEIGHTED_AVERAGE = 1
+    UNWEIGHTED_SUM = 2
+    NO_QUANTIZATION = 3             # not built
+    MAX_POOL = 4
+    SPLAT_LINEAR_INTERPOLATION = 5  # not built
+
+
+_VOXEL_MODE = {SparseTensorQuantizationMode.RANDOM_SUBSAMPLE: "first", SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE: "average",
+               SparseTensorQuantizationMode.UNWEIGHTED_SUM: "sum", SparseTensorQuantizationMode.MAX_POOL: "max"}
+
+
+def _quantization_mode(mode):
+    """a SparseTensorQuantizationMode, or its name in either case ("unweighted_average": args.quantization_mode) -> the member;
+    the two modes that are not built raise NotImplementedError"""
+    if isinstance(mode, str):
+        try:
+            mode = SparseTensorQuantizationMode[mode.upper()]
+        except KeyError:
+            raise ValueError(f"quantization_mode {mode!r}: one of {[m.name.lower() for m in SparseTensorQuantizationMode]}") from None
+    mode = SparseTensorQuantizationMode(mode)
+    if mode not in _VOXEL_MODE:
+        raise NotImplementedError(f"SparseTensorQuantizationMode.{mode.name} is not built: RANDOM_SUBSAMPLE, UNWEIGHTED_AVERAGE, "
+                                  "UNWEIGHTED_SUM and MAX_POOL are")
+    return mode
+
+
+def _quantized_features(features, cm, mode):
+    """the feature rows of the sites that ``cm.insert_points`` / ``insert_cloud`` made of the points behind ``features``"""
+    if mode is SparseTensorQuantizationMode.RANDOM_SUBSAMPLE:
+        return features[cm.unique_index]  # one row per site, in site (key) order
+    if cm.voxel_map is None:
+        S.L.require_gpu(features, "features")
+    return S.voxel_reduce(features.contiguous(), cm.voxel_map, _VOXEL_MODE[mode])
+
+
 class CoordinateManager:
     """Sites per tensor stride + cached kernel maps of one batch (geometry only: no gradients flow through it)."""
 
@@ -204,10 +244,25 @@ class CoordinateManager:
         self.keys = {}    # tensor_stride -> canonical sorted int64 keys of that stride
         self.maps = {}    # (in key set, out key set, strides, kernel offsets, transposed) -> (nbr [K,Nout], inv [K,Nin], plan)
         self.num_scenes = None  # batch size: read once, with the coordinate range, when the points are inserted
+        self.voxel_map = None   # sparse_ops.VoxelMap of the inserted points (device tensors)
+
+    def _take_voxel_map(self, vmap):
+        self.voxel_map = vmap
+        self.num_scenes = vmap.num_scenes
+        self.keys[1], self.unique_index, self.inverse_mapping = vmap.sites, vmap.first, vmap.inverse
+
+    def insert_cloud(self, points, offsets, voxel_size):
+        """packed raw points [N, >= 3] fp32 on the device and their B + 1 scene offsets -> the sites of tensor stride 1, as
+        ``insert_points`` of ``batch_sparse_collate`` of the scenes' ``p[:, :3] / voxel_size`` makes them (sparse_ops.voxel_map)"""
+        self._take_voxel_map(S.voxel_map(points, offsets, voxel_size))
 
     def insert_points(self, coordinates):
         """raw integer coordinates [N,4] -> the sites of tensor stride 1 (+ ``unique_index``: the input row kept per site:
-        the first occurrence in input order; MinkowskiEngine: RANDOM_SUBSAMPLE)"""
+        the first occurrence in input order; MinkowskiEngine: RANDOM_SUBSAMPLE; ``inverse_mapping``: the site row of every input
+        row).  Device tensors: sparse_ops.voxel_map_coords, one host read.  CPU tensors (geometry passes of the CPU tests):
+        the tensor expressions the device path is tested against."""
+        if coordinates.is_cuda and not coordinates.is_floating_point():
+            return self._take_voxel_map(S.voxel_map_coords(coordinates))
         keys_in = S.pack_keys(coordinates)
         # (pack_keys has just read the coordinate range back: the one place where the scene count may be read as well)
         self.num_scenes = int(coordinates[:, 0].max()) + 1 if coordinates.shape[0] else 0
@@ -216,6 +271,7 @@ class CoordinateManager:
         first.scatter_reduce_(0, inverse, torch.arange(keys_in.shape[0], device=keys.device), reduce="amin")
         self.keys[1] = keys
         self.unique_index = first
+        self.inverse_mapping = inverse.to(torch.int32)
 
     @staticmethod
     def _strided_keys(keys, new_ts):
@@ -382,12 +438,16 @@ class _PendingConv:
 class SparseTensor:
     """features [N, C] on the sites ``coordinates`` [N, 4] = (batch, x, y, z) (MinkowskiEngine's SparseTensor)."""
 
-    def __init__(self, features, coordinates=None, tensor_stride=1, coordinate_manager=None, keys=None):
+    def __init__(self, features, coordinates=None, tensor_stride=1, coordinate_manager=None, keys=None,
+                 quantization_mode=SparseTensorQuantizationMode.RANDOM_SUBSAMPLE):
+        self.quantization_mode = _quantization_mode(quantization_mode)
+        self.unique_index = self.inverse_mapping = None
         if coordinate_manager is None:
             assert coordinates is not None and tensor_stride == 1
             coordinate_manager = CoordinateManager(features.device)
             coordinate_manager.insert_points(coordinates)
-            features = features[coordinate_manager.unique_index]  # one row per site, in site (key) order
+            features = _quantized_features(features, coordinate_manager, self.quantization_mode)
+            self.unique_index, self.inverse_mapping = coordinate_manager.unique_index, coordinate_manager.inverse_mapping
         self._F, self._pending = features, None
         self.tensor_stride = tensor_stride
         self.coordinate_manager = coordinate_manager
@@ -453,6 +513,20 @@ class SparseTensor:
             return self._on_union(other, -1)
         return self if _geometry_only() else self._like(self.F - other.F)
 
+    def slice(self, field):
+        """ME.SparseTensor.slice: this tensor's features on the points of ``field`` (a TensorField whose ``sparse()`` made this
+        tensor's sites) -> a TensorField with F = self.F[field.inverse_mapping].  One gather launch; its backward is the sum of
+        the point gradients of every site in ascending input-row order."""
+        if not isinstance(field, TensorField):
+            raise ValueError(f"slice: a TensorField is expected, not {type(field).__name__}")
+        if field.coordinate_manager is not self.coordinate_manager or field._vmap is None:
+            raise ValueError("slice: the field must be the one whose sparse() built this tensor's coordinate manager")
+        if self.tensor_stride != 1 or self.keys is not self.coordinate_manager.keys[1]:
+            raise ValueError("slice: only a tensor on the field's own sites (tensor stride 1) can be sliced")
+        out = TensorField(S.voxel_slice(self.F.contiguous(), field._vmap), field.C, quantization_mode=field.quantization_mode)
+        out.coordinate_manager, out._vmap = field.coordinate_manager, field._vmap
+        return out
+
     def decomposed(self):
         """per batch element: (coordinates [n,3] int32, features [n,C]) — key order keeps the scenes contiguous"""
         counts = self.coordinate_manager.scene_counts(self.keys)
@@ -461,6 +535,90 @@ class SparseTensor:
             out.append((coords[s:s + n, 1:], self.F[s:s + n]))
             s += n
         return out
+
+
+class TensorField:
+    """ME.TensorField(features [N, C], coordinates [N, 4] = (batch, x, y, z)): features on POINTS, several of which may share a
+    voxel.  ``sparse()`` quantises them into a SparseTensor (``quantization_mode``; ME's default for a field is the average) and
+    keeps the inverse map, so that ``SparseTensor.slice(field)`` brings site features back to the points.  Float coordinates are
+    floored.  ``cat_slice`` and the interpolating modes are not built."""
+
+    def __init__(self, features, coordinates, quantization_mode=SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE):
+        self.quantization_mode = _quantization_mode(quantization_mode)
+        S.L.require_gpu(features, "features")
+        S.L.require_gpu(coordinates, "coordinates")
+        if coordinates.dim() != 2 or coordinates.shape[1] != 4 or coordinates.shape[0] != features.shape[0]:
+            raise ValueError(f"TensorField: coordinates must be [{features.shape[0]}, 4] (batch, x, y, z), got {tuple(coordinates.shape)}")
+        if coordinates.is_floating_point():
+            coordinates = torch.floor(coordinates).to(torch.int32)
+        self.F, self.C = features, coordinates
+        self.coordinate_manager = self._vmap = None
+
+    @property
+    def inverse_mapping(self):
+        if self._vmap is None:
+            raise RuntimeError("TensorField.inverse_mapping: call sparse() first")
+        return self._vmap.inverse
+
+    def sparse(self, quantization_mode=None):
+        """the SparseTensor of this field's voxels (rows in key order); the field remembers the map for ``slice``"""
+        mode = self.quantization_mode if quantization_mode is None else _quantization_mode(quantization_mode)
+        x = SparseTensor(self.F, coordinates=self.C, quantization_mode=mode)
+        self.coordinate_manager, self._vmap = x.coordinate_manager, x.coordinate_manager.voxel_map
+        return x
+
+
+def sparse_quantize(coordinates, features=None, labels=None, ignore_label=-100, return_index=False, return_inverse=False,
+                    return_maps_only=False, quantization_size=None):
+    """ME.utils.sparse_quantize on the device: coordinates [N, 3] (or [N, 4] with a leading batch column) -> one row per voxel,
+    floor(coordinates / quantization_size) (a float or one per axis).  Returns, in MinkowskiEngine's order: the voxel coordinates
+    int32 [M, 3 or 4]; ``features[index]`` if features are given; the voxel labels if labels are given (the label all points of
+    the voxel share, ``ignore_label`` where they differ); ``index`` [M] int64 (the lowest input row of each voxel) with
+    ``return_index``; ``inverse`` [N] int64 (the voxel row of every input row) with ``return_inverse``.  ``return_maps_only``:
+    only index (and inverse).  The rows are in ascending (batch, x, y, z) order — MinkowskiEngine's order is its hash map's and
+    unspecified.  Device tensors in, device tensors out; one host read of eight bytes."""
+    S.L.require_gpu(coordinates, "coordinates")
+    if coordinates.dim() != 2 or coordinates.shape[1] not in (3, 4):
+        raise ValueError(f"sparse_quantize: coordinates must be [N, 3] or [N, 4] (batch first), got {tuple(coordinates.shape)}")
+    n, batched = coordinates.shape[0], coordinates.shape[1] == 4
+    for name, t in (("features", features), ("labels", labels)):
+        if t is not None:
+            S.L.require_gpu(t, name)
+            if t.shape[0] != n:
+                raise ValueError(f"sparse_quantize: {name} has {t.shape[0]} rows, coordinates {n}")
+    scalar = isinstance(quantization_size, (int, float, np.integer, np.floating))
+    if quantization_size is not None and not scalar:
+        quantization_size = [float(q) for q in quantization_size]
+        if len(quantization_size) != 3:
+            raise ValueError("sparse_quantize: quantization_size must be a number or one per axis (3)")
+    if scalar and not batched and coordinates.dtype == torch.float32:
+        points = coordinates if coordinates.stride(1) == 1 else coordinates.contiguous()
+        vmap = S.voxel_map(points, [0, n], float(quantization_size))  # the keys launch floors p / size itself
+    else:
+        c = coordinates
+        if quantization_size is not None:
+            q = quantization_size if scalar else torch.tensor(quantization_size, dtype=torch.float32, device=c.device)
+            xyz = torch.floor(c[:, -3:].to(torch.float32) / q).to(torch.int32)
+            c = torch.cat((c[:, :1].to(torch.int32), xyz), 1) if batched else xyz
+        elif c.is_floating_point():
+            c = torch.floor(c).to(torch.int32)
+        if not batched:
+            c = torch.cat((torch.zeros((n, 1), dtype=c.dtype, device=c.device), c), 1)
+        vmap = S.voxel_map_coords(c)
+    index, inverse = vmap.first, vmap.inverse.to(torch.int64)
+    if return_maps_only:
+        return (index, inverse) if return_inverse else index
+    sites = S.unpack_keys(vmap.sites)
+    out = [sites if batched else sites[:, 1:]]
+    if features is not None:
+        out.append(features[index])
+    if labels is not None:
+        out.append(S.voxel_labels(labels, vmap, ignore_label))
+    if return_index:
+        out.append(index)
+    if return_inverse:
+        out.append(inverse)
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 class MinkowskiConvolution(nn.Module):

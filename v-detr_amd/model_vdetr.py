@@ -72,6 +72,9 @@ class ModelVDETR(nn.Module):
         self.use_color = bool(getattr(args, "use_color", False))
         self.xyz_color = bool(getattr(args, "xyz_color", False))
         self.sparse_backbone = isinstance(pre_encoder, MinkResNet)
+        # what becomes of the feature columns of points that share a voxel (ME.SparseTensorQuantizationMode by name; absent: the
+        # first point's row, as before)
+        self.quantization_mode = ME._quantization_mode(getattr(args, "quantization_mode", None) or "random_subsample")
         if self.sparse_backbone:
             depth = int(getattr(args, "depth", 34))
             channels = [(4 if depth > 34 else 1) * inplane * 2 ** i for i in range(num_stages)]
@@ -128,20 +131,20 @@ class ModelVDETR(nn.Module):
         undefined name (:259); the evident intent — xyz as the input features — is what runs here."""
         ME.clear_last_paths()
         clouds = inputs["point_clouds"]
-        if self.use_color:
-            data = [(p[:, :3] / self.voxel_size, p[:, :] if self.xyz_color else p[:, 3:]) for p in clouds]
-        else:
-            data = [(p[:, :3] / self.voxel_size, p[:, :3]) for p in clouds]
-        coordinates, features = ME.batch_sparse_collate(data)
         # the coordinate manager (sites per stride, kernel maps, compacted row lists) depends on the point COORDINATES only:
         # like the FPS indices it may be built ahead of time (``prepare_geometry``) and handed in as inputs["geometry"]
         geometry = inputs.get("geometry")
+        packed = self._packed_clouds(clouds)
         if geometry is None:
-            x = ME.SparseTensor(features.contiguous(), coordinates=coordinates)
+            geometry = self._voxelise(clouds, packed)
+        elif packed.is_cuda:
+            geometry.use_on()  # built on another stream (loader thread / side stream): this stream reads it from here on
+        if self.use_color:
+            features = packed if self.xyz_color else packed[:, 3:]
         else:
-            if features.is_cuda:
-                geometry.use_on()  # built on another stream (loader thread / side stream): this stream reads it from here on
-            x = ME.SparseTensor(features[geometry.unique_index].contiguous(), coordinate_manager=geometry)
+            features = packed[:, :3]
+        # with a prepared manager the step launches only this: a row gather (default mode) or the fold of the mode
+        x = ME.SparseTensor(ME._quantized_features(features, geometry, self.quantization_mode).contiguous(), coordinate_manager=geometry)
         stages = self.pre_encoder(x)
         x = stages[-1]
         out = None
@@ -164,12 +167,32 @@ class ModelVDETR(nn.Module):
         must first wait for the producing stream (event / wait_stream); the manager's memory is then tied to the consuming
         stream by ``backbone_forward`` itself (``CoordinateManager.use_on``), so it may be dropped right after the step."""
         clouds = inputs["point_clouds"]
-        coordinates, _ = ME.batch_sparse_collate([(p[:, :3] / self.voxel_size, p[:, :0]) for p in clouds])
-        cm = ME.CoordinateManager(clouds[0].device)
-        cm.insert_points(coordinates)
+        cm = self._voxelise(clouds, self._packed_clouds(clouds))
         with ME.geometry_only():  # the layers only register their sites / maps / pair lists: no feature arithmetic
             self.backbone_forward(dict(inputs, geometry=cm))
         return cm.finalize()
+
+    @staticmethod
+    def _packed_clouds(clouds):
+        """the clouds — a list of [n_i, W] tensors or one [B, n, W] batch — as one packed [N, W] tensor (one ``torch.cat``; a
+        single cloud and a batch tensor are used as they are)"""
+        if torch.is_tensor(clouds):
+            return clouds.reshape(-1, clouds.shape[-1])
+        return clouds[0] if len(clouds) == 1 else torch.cat(list(clouds))
+
+    def _voxelise(self, clouds, packed):
+        """the coordinate manager of the clouds' voxels at ``voxel_size``: on the device one keys launch over the packed points
+        with host-known offsets (sparse_ops.voxel_map); CPU tensors (geometry passes of the CPU tests) take the tensor expressions"""
+        cm = ME.CoordinateManager(packed.device)
+        if packed.is_cuda and packed.dtype == torch.float32:
+            offsets = [0]
+            for p in clouds:
+                offsets.append(offsets[-1] + p.shape[0])
+            cm.insert_cloud(packed.detach() if packed.stride(1) == 1 else packed.detach().contiguous(), offsets, self.voxel_size)
+        else:
+            coordinates, _ = ME.batch_sparse_collate([(p[:, :3] / self.voxel_size, p[:, :0]) for p in clouds])
+            cm.insert_points(coordinates)
+        return cm
 
     def _scenes(self, inputs):
         return self.backbone_forward(inputs) if self.sparse_backbone else self.pre_encoder(inputs)

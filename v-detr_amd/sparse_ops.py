@@ -976,6 +976,239 @@ def union_add(fa, fb, row_a, row_b, src_a, src_b, sign=1):
     return _UnionAddFn.apply(fa, fb, row_a, row_b, src_a, src_b, sign)
 
 
+# ---- voxelisation: keys, sites and the quantisation modes (csrc/sparse_voxel.hip) ------------------------------------
+VOXEL_MODES = {"sum": L.VDETR_VOXEL_SUM, "average": L.VDETR_VOXEL_AVG, "max": L.VDETR_VOXEL_MAX, "first": L.VDETR_VOXEL_FIRST}
+RANGE_MESSAGE = "voxel coordinates outside the 16-bit key range"
+
+
+def voxel_tile():
+    """sorted keys per workgroup of the sites pass (the tests place their edge cases on its multiples)"""
+    return int(L.lib().vdetr_sp_voxel_tile())
+
+
+class VoxelMap(tuple):
+    """(sites [M] int64 ascending unique keys, inverse [N] int32 = the site row of every input row, first [M] int64 = the lowest
+    input row of each site, seg [M + 1] int32 = the run starts in sorted order, order [N] int32 = the stable sort's permutation).
+    ``num_scenes`` is the B of the offsets; for ready coordinates the highest batch index + 1, which rides with the one host read."""
+    num_scenes = None
+
+    sites, inverse, first, seg, order = (property(lambda self, i=i: self[i]) for i in range(5))
+
+
+def _voxel_sites(keys, num_scenes):
+    """the shared second half of ``voxel_map`` / ``voxel_map_coords``: stable sort, the two sites launches, the ONE host read"""
+    N, dev = keys.shape[0], keys.device
+    sites = torch.empty(N, dtype=torch.int64, device=dev)
+    first = torch.empty(N, dtype=torch.int64, device=dev)
+    inverse, order32 = (torch.empty(N, dtype=torch.int32, device=dev) for _ in range(2))
+    seg = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    if N == 0:
+        seg.zero_()
+        vm = VoxelMap((sites, inverse, first, seg, order32))
+        vm.num_scenes = num_scenes or 0
+        return vm
+    sorted_keys, order = torch.sort(keys, stable=True)
+    lib = L.lib()
+    count = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = L.workspace(lib.vdetr_sp_voxel_sites_workspace_bytes(N), dev)
+    d = L.SpVoxelSitesDesc()
+    d.N, d.sorted, d.order = N, sorted_keys.data_ptr(), order.data_ptr()
+    d.sites, d.first, d.inverse, d.order32, d.seg = (t.data_ptr() for t in (sites, first, inverse, order32, seg))
+    d.count, d.workspace = count.data_ptr(), ws.data_ptr()
+    L.check(lib.vdetr_sp_voxel_sites_i64(ctypes.byref(d), L.stream_ptr()), "sp_voxel_sites")
+    # the number of sites is data: the one host read (eight bytes).  The range flag rides with it as -1; otherwise the word
+    # is the highest batch index + 1, the scene count of a map built from ready coordinates
+    M, scenes = count.tolist()
+    if scenes < 0:
+        raise ValueError(f"{RANGE_MESSAGE} (a voxel index outside [{-KEY_BIAS}, {KEY_BIAS - 1}], a non-finite coordinate or a "
+                         f"batch index outside [0, 32767])")
+    vm = VoxelMap((sites[:M], inverse, first[:M], seg[:M + 1], order32))
+    vm.num_scenes = scenes if num_scenes is None else num_scenes
+    return vm
+
+
+def voxel_map(points, offsets, voxel_size):
+    """Packed points [N, >= 3] fp32 on the device (unit column stride; only the first three columns are read), offsets [B + 1]
+    (host sequence, or an int32 device tensor) and the voxel size (a Python float) -> ``VoxelMap``.  The voxel index of a point is,
+    bit for bit, ``torch.floor(points[:, :3] / voxel_size).to(torch.int32)`` on the device.  One keys launch, a stable library
+    sort, two sites launches and ONE host read of eight bytes (the site count and the range flag); a raised flag is the
+    ValueError of ``pack_keys``."""
+    L.require_float(points, "points")
+    if points.dim() != 2 or points.shape[1] < 3 or (points.shape[0] > 1 and points.stride(0) < 3) or \
+            (points.shape[0] > 0 and points.stride(1) != 1):
+        raise RuntimeError(f"points must be [N, 3 or more columns] with unit column stride (it is {tuple(points.shape)})")
+    voxel_size = float(voxel_size)
+    if not (voxel_size > 0.0 and voxel_size < float("inf")):
+        raise ValueError(f"voxel_map: voxel_size {voxel_size!r} must be positive and finite")
+    L.require_gpu(points, "points")
+    N, dev = points.shape[0], points.device
+    if N >= 2 ** 31:
+        raise RuntimeError(f"voxel_map: {N} points are more than 31 bits hold")
+    if torch.is_tensor(offsets):
+        L.require_int(offsets, "offsets")
+        L.require_contiguous(offsets, "offsets")
+        if offsets.dim() != 1 or offsets.shape[0] < 2:
+            raise ValueError("offsets must hold B + 1 row offsets")
+        off_dev = offsets if offsets.is_cuda else offsets.to(dev, non_blocking=True)
+    else:
+        off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int64)
+        if off.ndim != 1 or len(off) < 2:
+            raise ValueError("offsets must hold B + 1 row offsets")
+        if off[0] != 0 or off[-1] != N or (np.diff(off) < 0).any():
+            raise ValueError(f"offsets run from {off[0]} to {off[-1]}, points has {N} rows")
+        off_dev = torch.from_numpy(off.astype(np.int32)).to(dev, non_blocking=True)
+    B = off_dev.shape[0] - 1
+    if B > 32768:
+        raise ValueError(f"{RANGE_MESSAGE}: {B} scenes")
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    if N:
+        d = L.SpVoxelKeysDesc()
+        d.N, d.B, d.stride, d.voxel_size = N, B, points.stride(0) if N > 1 else points.shape[1], voxel_size
+        d.points, d.offsets, d.coords, d.keys = points.data_ptr(), off_dev.data_ptr(), None, keys.data_ptr()
+        L.check(L.lib().vdetr_sp_voxel_keys_f32(ctypes.byref(d), L.stream_ptr()), "sp_voxel_keys")
+    return _voxel_sites(keys, B)
+
+
+def voxel_map_coords(coords):
+    """Ready integer coordinates [N, 4] (batch, x, y, z) on the device -> ``VoxelMap`` (see ``voxel_map``)."""
+    if coords.dim() != 2 or coords.shape[1] != 4:
+        raise RuntimeError(f"coords must be [N, 4] (batch, x, y, z) (it is {tuple(coords.shape)})")
+    if coords.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+        raise RuntimeError(f"coords must be an integer tensor (it is {coords.dtype})")
+    L.require_gpu(coords, "coords")
+    if coords.dtype != torch.int32:
+        # (what no key holds stays outside after the clamp)
+        coords = coords.clamp(-(1 << 20), 1 << 20).to(torch.int32) if coords.dtype == torch.int64 else coords.to(torch.int32)
+    coords = coords.contiguous()
+    N, dev = coords.shape[0], coords.device
+    if N >= 2 ** 31:
+        raise RuntimeError(f"voxel_map_coords: {N} points are more than 31 bits hold")
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    if N:
+        d = L.SpVoxelKeysDesc()
+        d.N, d.points, d.offsets, d.coords, d.keys = N, None, None, coords.data_ptr(), keys.data_ptr()
+        L.check(L.lib().vdetr_sp_voxel_keys_f32(ctypes.byref(d), L.stream_ptr()), "sp_voxel_keys")
+    return _voxel_sites(keys, None)
+
+
+def _require_vmap(vmap, n=None):
+    if not isinstance(vmap, tuple) or len(vmap) != 5:
+        raise RuntimeError("vmap must be the (sites, inverse, first, seg, order) of voxel_map / voxel_map_coords")
+    sites, inverse, first, seg, order = vmap
+    _require_keys(sites, "sites")
+    _require_index(inverse, "inverse", n)
+    _require_index(order, "order", inverse.shape[0])
+    _require_index(seg, "seg", sites.shape[0] + 1)
+    return sites.shape[0], inverse.shape[0]
+
+
+def _voxel_reduce_launch(x, order, seg, M, mode):
+    N, C = x.shape
+    y = torch.empty((M, C), dtype=torch.float32, device=x.device)
+    arg = torch.empty((M, C), dtype=torch.int32, device=x.device) if mode == L.VDETR_VOXEL_MAX else None
+    d = L.SpVoxelReduceDesc()
+    d.M, d.N, d.C, d.mode = M, N, C, mode
+    d.x, d.order, d.seg, d.y, d.arg = L.ptr(x).value, L.ptr(order).value, L.ptr(seg).value, L.ptr(y).value, L.ptr(arg).value
+    L.check(L.lib().vdetr_sp_voxel_reduce_f32(ctypes.byref(d), L.stream_ptr()), "sp_voxel_reduce")
+    return y, arg
+
+
+class _VoxelReduceFn(Function):
+    """y [M, C] = the fold of x [N, C] over the points of every site (csrc/sparse_voxel.hip); dx is a gather through ``inverse``."""
+
+    @staticmethod
+    def forward(ctx, x, inverse, seg, order, M, mode):
+        y, arg = _voxel_reduce_launch(x, order, seg, M, mode)
+        ctx.save_for_backward(inverse, seg, order, arg)
+        ctx.cfg = (M, x.shape[0], x.shape[1], mode)
+        if arg is None:
+            return y, None
+        ctx.mark_non_differentiable(arg)
+        return y, arg
+
+    @staticmethod
+    def backward(ctx, dy, _darg):
+        inverse, seg, order, arg = ctx.saved_tensors
+        M, N, C, mode = ctx.cfg
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        dy = dy.contiguous()
+        dx = torch.empty((N, C), dtype=torch.float32, device=dy.device)
+        d = L.SpVoxelReduceDesc()
+        d.M, d.N, d.C, d.mode = M, N, C, mode
+        d.order, d.seg, d.arg = L.ptr(order).value, L.ptr(seg).value, L.ptr(arg).value
+        L.check(L.lib().vdetr_sp_voxel_reduce_grad_f32(ctypes.byref(d), L.ptr(dy), L.ptr(inverse), L.ptr(dx), L.stream_ptr()),
+                "sp_voxel_reduce_grad")
+        return dx, None, None, None, None, None
+
+
+def voxel_reduce(features, vmap, mode, return_arg=False):
+    """The features of the sites of a ``VoxelMap``: features [N, C] contiguous fp32 on the device (any C >= 1), mode "sum" |
+    "average" | "max" | "first" -> [M, C].  A site's value is the float32 fold of its points in ascending input-row order
+    (average: one division by the count behind the sum; max: np.maximum, a NaN wins, ties keep the lower row; first: the lowest
+    row, MinkowskiEngine's RANDOM_SUBSAMPLE): two runs agree bit for bit.  One launch forward, one backward (a gather); no atomics.
+    ``return_arg``: also the winning input row per (site, channel) [M, C] int32 (max; None otherwise)."""
+    _require_table(features, "features")
+    if mode not in VOXEL_MODES:
+        raise ValueError(f"voxel_reduce: mode {mode!r} (sum, average, max, first)")
+    M, N = _require_vmap(vmap, features.shape[0])
+    if features.shape[1] < 1:
+        raise RuntimeError(f"features must be a feature table [N, C] with C >= 1 (it is {tuple(features.shape)})")
+    _, inverse, _, seg, order = vmap
+    y, arg = _VoxelReduceFn.apply(features, inverse, seg, order, M, VOXEL_MODES[mode])
+    return (y, arg) if return_arg else y
+
+
+class _VoxelSliceFn(Function):
+    """y [N, C] = x[inverse] (site features back on the points); backward: the sum fold of dy over every site's points."""
+
+    @staticmethod
+    def forward(ctx, x, inverse, seg, order):
+        ctx.save_for_backward(inverse, seg, order)
+        ctx.M = x.shape[0]
+        N, C = inverse.shape[0], x.shape[1]
+        dx = torch.empty((N, C), dtype=torch.float32, device=x.device)
+        d = L.SpVoxelReduceDesc()  # the sum mode's gradient launch IS the row gather through `inverse`, at any width
+        d.M, d.N, d.C, d.mode = ctx.M, N, C, L.VDETR_VOXEL_SUM
+        d.seg = L.ptr(seg).value
+        L.check(L.lib().vdetr_sp_voxel_reduce_grad_f32(ctypes.byref(d), L.ptr(x), L.ptr(inverse), L.ptr(dx), L.stream_ptr()),
+                "sp_voxel_reduce_grad")
+        return dx
+
+    @staticmethod
+    def backward(ctx, dy):
+        inverse, seg, order = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        return _voxel_reduce_launch(dy.contiguous(), order, seg, ctx.M, L.VDETR_VOXEL_SUM)[0], None, None, None
+
+
+def voxel_slice(site_features, vmap):
+    """[N, C] = site_features[inverse]: the features of every point's site (site_features [M, C] contiguous fp32 on the device).
+    One gather launch; the backward is the sum fold in the fixed order of ``voxel_reduce``."""
+    _require_table(site_features, "site_features")
+    M, _ = _require_vmap(vmap)
+    if site_features.shape[0] != M:
+        raise RuntimeError(f"voxel_slice: site_features has {site_features.shape[0]} rows, the map {M} sites")
+    _, inverse, _, seg, order = vmap
+    return _VoxelSliceFn.apply(site_features, inverse, seg, order)
+
+
+def voxel_labels(labels, vmap, ignore_label=-100):
+    """[M] the label all points of a site share, ``ignore_label`` where they differ (labels [N] integer, on the device; the
+    result has the labels' dtype).  One launch."""
+    if labels.dtype not in (torch.int32, torch.int64) or labels.dim() != 1:
+        raise RuntimeError(f"labels must be a one-dimensional int32 or int64 tensor (it is {labels.dtype}, {tuple(labels.shape)})")
+    L.require_gpu(labels, "labels")
+    M, N = _require_vmap(vmap, labels.shape[0])
+    _, _, _, seg, order = vmap
+    lab = labels.to(torch.int32).contiguous()
+    out = torch.empty(M, dtype=torch.int32, device=labels.device)
+    L.check(L.lib().vdetr_sp_voxel_labels_i32(L.ptr(lab), L.ptr(order), L.ptr(seg), M, N, int(ignore_label), L.ptr(out), L.stream_ptr()),
+            "sp_voxel_labels")
+    return out.to(labels.dtype)
+
+
 _MODE = os.environ.get("VDETR_SP_MODE", "pairs")  # pairs (fused kernels) | plan (batched library GEMMs) | im2col
 _IM2COL = _MODE == "im2col" or os.environ.get("VDETR_SP_IM2COL", "0") == "1"  # A/B switch: one dense im2col GEMM per layer instead of the plan
 
