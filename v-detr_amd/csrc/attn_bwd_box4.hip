@@ -16,7 +16,15 @@
 //     then consecutive slots (a bucket may hold two groups: that costs a flush, never a wrong cell, because group ends are
 //     found by comparing the signatures of neighbouring slots).  box2's ballot / mbcnt loop was ~150 instructions per chunk.
 //   * nothing is padded: a quad of slots is one v_mfma_f32_16x16x4_f32 (rows: the 8 products w_z w_y, columns: the 16
-//     products w_x dS, K = 4 pairs), a quad that holds a group end is issued once per segment with the other slots' rows zeroed
+//     products w_x dS, K = 4 pairs) however its groups fall.  The tile has 16 rows and a group needs 8, so rows 0..7 hold the
+//     sums of the groups of even parity and rows 8..15 those of odd parity (parity = the group ends in front of a slot in its
+//     chunk, mod 2: a prefix XOR of the end mask, wave-uniform).  A lane's A operand of a slot is U[m & 7] in the half of the
+//     slot's parity and 0 in the other, so the group that begins behind an end inside a quad accumulates beside the one that
+//     ends there; the flush of a group is done by the 32 lanes that hold its half and zeroes only their registers.  Only a
+//     quad with two or three ends among its slots 0..2 is cut (two instructions): groups g and g + 2 would share a half.
+//     The routing is in box4_walk.h, checked on the host (tests/box4_walk_check.cpp).  A row sees the same products and the
+//     same zeros in the same K positions as with one instruction per segment of a quad (the form before, rows 8..15 idle):
+//     bit-identical sums, 340 -> 281 us at 190 workgroups, 261 -> 216 at 256 (profiles/table_grad_quads.txt)
 //   * exact fp32 products (no bf16 split: one multiply per operand and quad), operands of the chunk's 16 quads read from the
 //     wave's record strip in one burst (3 LDS reads per lane and quad, 16-byte parts XOR-swizzled by the slot)
 //   * a group's 128 sums leave with four ds_add_u32 per lane whose addresses come from a signature that is stored as the
@@ -24,6 +32,7 @@
 // The rank a lane reads back from its LDS add follows the lane order inside the instruction, so the slot order — and with
 // it the order of the float additions inside the matrix unit — is the same in every run: results are bit-reproducible.
 #include "attn_common.h"
+#include "box4_walk.h"
 
 #include <stdlib.h>
 
@@ -97,8 +106,9 @@ __global__ __launch_bounds__(kB4Threads) void attn_bwd_box4_kernel(AttnParams P)
   int taken = 1;
 
   const int kk = lane >> 4, c15 = lane & 15;
-  // A role (row m = c15 of the matrix instruction): U[m], m = (cy, cz, yi), for m < 8; rows 8..15 stay zero.  Part p of slot s
-  // sits at 16 (p ^ (s & 3)); a lane's slots are 4 i + kk, so s & 3 = kk.
+  // A role (row m = c15 of the matrix instruction): U[m & 7], m & 7 = (cy, cz, yi); rows 0..7 take it for the slots of even
+  // parity, rows 8..15 for those of odd parity (the walk below).  Part p of slot s sits at 16 (p ^ (s & 3)); a lane's slots
+  // are 4 i + kk, so s & 3 = kk.
   const int a_off = (((c15 >> 2) & 1) ^ kk) * 16 + (c15 & 3) * 4;
   // B role (column n = c15 = (xi, cx, h)): wx[2 cx + xi] in part 2, dS[h] in part 3
   const int b_offx = (2 ^ kk) * 16 + (2 * ((c15 >> 2) & 1) + (c15 >> 3)) * 4, b_offd = (3 ^ kk) * 16 + (c15 & 3) * 4;
@@ -206,17 +216,20 @@ __global__ __launch_bounds__(kB4Threads) void attn_bwd_box4_kernel(AttnParams P)
 #pragma unroll
       for (int i = 0; i < kWave / 4; ++i) {
         // (Slots past the chunk's last pair hold older records: finite, and never inside a segment.  Rows 8..15 of the tile read
-        // U[m & 7] like rows 0..7: a row of the result depends on its own row of A only, and rows 8..15 are never flushed.)
+        // U[m & 7] like rows 0..7: a row of the result depends on its own row of A only.)
         u[i] = *reinterpret_cast<const b4_rec1_t*>(rq + i * 4 * kB4RecBytes + a_off);
         t[i] = *reinterpret_cast<const b4_rec1_t*>(rq + i * 4 * kB4RecBytes + b_offx) *
                *reinterpret_cast<const b4_rec1_t*>(rq + i * 4 * kB4RecBytes + b_offd);
       }
       const unsigned long long emask = __ballot(valid && Jm != Jn);  // slot is the last of its group
+      // A group's sums live in the half of the tile that its parity names (box4_walk.h): rows 0..7 = lanes 0..31 of the
+      // result, rows 8..15 = lanes 32..63.  Wave-uniform, once per chunk.
+      const unsigned long long par = b4_parity_word(emask);
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      auto flush = [&](int slot) {  // the group that ends in `slot`: 128 sums -> histogram
+      auto flush_half = [&](int slot, int half) {  // the group that ends in `slot`: 128 sums -> histogram, by the lanes of its half
         const int Jg = __builtin_amdgcn_readlane(Jm, slot);
         const int cell0 = Jg & 1023, cell1 = (Jg >> 10) & 1023;  // (z T + y) T of yi = 0 / 1
-        if (lane < 32) {  // rows 0..7 of the tile
+        if ((lane >> 5) == half) {  // (o_lane takes cy from kk & 1: both halves address the same bins)
           const int xb = (int)__builtin_amdgcn_ubfe((unsigned)Jg, (unsigned)o_xshift, 4u);
           char* bin0 = reinterpret_cast<char*>(tab) + ((cell0 + xb) << 4) + o_c0;
           char* bin1 = reinterpret_cast<char*>(tab) + ((cell1 + xb) << 4) + o_c1;
@@ -224,54 +237,42 @@ __global__ __launch_bounds__(kB4Threads) void attn_bwd_box4_kernel(AttnParams P)
           atomicAdd(reinterpret_cast<int*>(bin1), b4_round(acc[1]));                    // r = 1: cz = 0, yi = 1
           atomicAdd(reinterpret_cast<int*>(bin0 + T * T * 16), b4_round(acc[2]));       // r = 2: cz = 1, yi = 0
           atomicAdd(reinterpret_cast<int*>(bin1 + T * T * 16), b4_round(acc[3]));       // r = 3: cz = 1, yi = 1
+          acc = f32x4{0.f, 0.f, 0.f, 0.f};  // (the other half keeps the sums of the group that has just begun)
         }
-        acc = f32x4{0.f, 0.f, 0.f, 0.f};
       };
+      auto flush = [&](int slot) { flush_half(slot, b4_half_of_slot(par, slot)); };
       // (Measured alternatives of this walk, all bit-identical: a rolled loop over the quads with the operands fetched one quad
       // ahead, 330 us; the same conditions handed to the compiler as exec-masked regions — which keeps the accumulator in one
       // register quad, where scalar branches make it copy the four registers behind the wait states of a matrix result at every
       // merge —, 319 us; the matrix instruction as asm with the accumulator tied in place: the compiler still copies it right
-      // behind the asm, where nothing pads the hazard.  The form below is the one with the fewest instructions: 299 us.)
+      // behind the asm, where nothing pads the hazard; one instruction per segment of a quad in straight-line code, rows 8..15
+      // idle: 299 us then, 261 us on 256 workgroups as the step's other kernels stand now.  The form below, one instruction per
+      // quad: 216 us — profiles/table_grad_quads.txt.)
       if (ns == kWave) {  // a full chunk (every chunk when nK is a multiple of 64): no bounds in the walk
+        const unsigned long long keep = b4_keep_word(par, c15, kk);  // bit 4 i: this lane's row takes slot 4 i + kk
+        const unsigned keep_lo = (unsigned)keep, keep_hi = (unsigned)(keep >> 32);
 #pragma unroll
         for (int i = 0; i < kWave / 4; ++i) {
+          // the row's operand: U[m & 7] in the half of the slot's group, 0 in the other (-1 / 0 from the keep bit, one AND)
+          const int km = __builtin_amdgcn_sbfe((int)(i < 8 ? keep_lo : keep_hi), (unsigned)(4 * i & 31), 1u);
+          const float ua = __int_as_float(__float_as_int(u[i]) & km);
           const unsigned eb = (unsigned)(emask >> (4 * i)) & 0xFu;
-          if (eb == 0u) {  // the quad lies inside one group: one matrix instruction, nothing else
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(u[i], t[i], acc, 0, 0, 0);
-          } else if (eb == 8u) {  // ... or ends one with its last slot
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(u[i], t[i], acc, 0, 0, 0);
-            flush(4 * i + 3);
-          } else {
-            // a group ends inside the quad (slot e0 < 3): its slots' rows first, flush, then the rows of the slots behind it —
-            // which belong to the next group(s).  One more end at slot 3 or none: straight-line; two ends inside: the loop.
-            const int e0 = __builtin_ctz(eb);
-            const bool head = kk <= e0;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(head ? u[i] : 0.f, t[i], acc, 0, 0, 0);
-            flush(4 * i + e0);
-            unsigned rest = eb & (eb - 1u);
-            if ((rest & 7u) == 0u) {
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(head ? 0.f : u[i], t[i], acc, 0, 0, 0);
-              if (rest) flush(4 * i + 3);
-            } else {
-              int s = e0 + 1;
-              do {
-                const int e = rest ? __builtin_ctz(rest) : 3;
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kk >= s && kk <= e ? u[i] : 0.f, t[i], acc, 0, 0, 0);
-                if (rest) {
-                  flush(4 * i + e);
-                  rest &= rest - 1u;
-                }
-                s = e + 1;
-              } while (s < 4);
-            }
-          }
+          b4_walk_quad(
+              eb, 4 * i,
+              [&](int lo, int hi) {  // (0, 3): the whole quad, nothing masked; a cut quad: the slots lo .. hi
+                const float a = (lo == 0 && hi == 3) || (kk >= lo && kk <= hi) ? ua : 0.f;
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, t[i], acc, 0, 0, 0);
+              },
+              flush);
         }
-      } else {  // the last, partly filled chunk of a key count that is not a multiple of 64
+      } else {  // the last, partly filled chunk of a key count that is not a multiple of 64: one instruction per segment, every
+                // group in half 0.  On purpose unlike the full chunk: rows 8..15 get a zero operand and stay zero, so that
+                // flush_half(.., 0), which zeroes the registers of lanes 0..31 only, leaves nothing behind in the others
         for (int i = 0; 4 * i < ns; ++i) {
           unsigned eb = (unsigned)(emask >> (4 * i)) & 0xFu;
           const int nq = min(4, ns - 4 * i);
           // (u / t of quad i: re-read, this loop is not unrolled)
-          const float ui = *reinterpret_cast<const b4_rec1_t*>(rq + i * 4 * kB4RecBytes + a_off);
+          const float ui = c15 < 8 ? *reinterpret_cast<const b4_rec1_t*>(rq + i * 4 * kB4RecBytes + a_off) : 0.f;
           const float ti = *reinterpret_cast<const b4_rec1_t*>(rq + i * 4 * kB4RecBytes + b_offx) *
                            *reinterpret_cast<const b4_rec1_t*>(rq + i * 4 * kB4RecBytes + b_offd);
           int s = 0;
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(kB4Threads) void attn_bwd_box4_kernel(AttnParams P)
             const int e = eb ? __builtin_ctz(eb) : 3;
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kk >= s && kk <= e ? ui : 0.f, ti, acc, 0, 0, 0);
             if (eb) {
-              flush(4 * i + e);
+              flush_half(4 * i + e, 0);
               eb &= eb - 1u;
             }
             s = e + 1;
