@@ -173,6 +173,36 @@ def test_resident_equals_the_host_path(name):
             assert abs(float(got_ap[c]) - float(ap[c])) <= (npos + 1) * 2.0 ** -52, (thr, c)
 
 
+def test_voc_ap_walks_long_segments_backwards_in_chunks():
+    """vdetr_voc_ap_f64 alone on segments longer than its chunk of 2048 ranks: three chunks with a partial last one, exactly one
+    chunk, no rank at all; a class without ground truth among the long ones.  Against the curve and the VOC-12 AP of the host
+    path (eval_det.evaluate_flat's cumsums and eval_det.voc_ap): curves, last recall and counts equal, AP within the bound of
+    two summation orders."""
+    from vdetr_amd import eval_det, eval_store
+    chunk = 2048
+    lengths = (2 * chunk + 37, 0, chunk, 2 * chunk + 37)
+    seg = np.concatenate(([0], np.cumsum(lengths))).astype(np.int32)
+    rng = np.random.default_rng(11)
+    tp = rng.random((2, seg[-1])) < np.array([[0.3], [0.05]])              # T = 2: many and few true positives
+    npos = np.array([int(tp[:, seg[c]:seg[c + 1]].sum(1).max()) + 7 for c in range(len(lengths))], np.int32)
+    npos[3] = 0
+    to_dev = lambda a: torch.from_numpy(a).to(DEV)  # noqa: E731
+    out, rec, prec = eval_store.voc_ap(to_dev(tp.astype(np.uint8)), to_dev(seg), to_dev(npos), curves=True)
+    out, rec, prec = out.cpu().numpy(), rec.cpu().numpy(), prec.cpu().numpy()
+    for t in range(2):
+        for c, n in enumerate(lengths):
+            sel = tp[t, seg[c]:seg[c + 1]]
+            tpc, fpc = np.cumsum(sel.astype(np.float64)), np.cumsum((~sel).astype(np.float64))
+            r = tpc / float(npos[c]) if npos[c] else np.zeros_like(tpc)
+            p = tpc / np.maximum(tpc + fpc, np.finfo(np.float64).eps)
+            ap = eval_det.voc_ap(r, p) if n else 0.0
+            assert np.array_equal(rec[t, seg[c]:seg[c + 1]], r) and np.array_equal(prec[t, seg[c]:seg[c + 1]], p), (t, c)
+            assert out[t, 1, c] == (r[-1] if n else 0.0) and out[t, 2, c] == n and out[t, 3, c] == npos[c], (t, c)
+            print(f"thr {t} class {c}: AP {float(out[t, 0, c])!r} host {float(ap)!r} npos {npos[c]}")
+            assert abs(float(out[t, 0, c]) - float(ap)) <= (int(npos[c]) + 1) * 2.0 ** -52, (t, c)
+            assert (ap > 0) == (n > 0 and npos[c] > 0)
+
+
 def _rows(B, Kq, Gq, rng, keep_p, present_p):
     f = lambda *shape: torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(DEV)  # noqa: E731
     keep = torch.from_numpy(rng.random((B, Kq)) < keep_p).to(DEV)

@@ -113,6 +113,22 @@ def test_ragged_batch_equals_the_single_calls_and_the_restatement(ragged, donotc
     assert got["instance_bboxes"].shape == (4, Kmax, 7) and int(got["box_counts"][2]) == 0
 
 
+def test_more_tiles_than_one_pass_of_the_tile_scan():
+    """a scene of 1025 tiles: the one workgroup that scans the tiles' kept counts has 1024 lanes, so it runs twice with a carry;
+    the one-vertex scene behind it is placed at the big scene's kept count.  About half of the label ids are dropped."""
+    from vdetr_amd import _lib
+    from test_scan_export_restatement import LABEL_MAP
+    rng = np.random.default_rng(34)
+    n = 1024 * _lib.VDETR_EXPORT_TILE + 1
+    scans = [make_scan(rng, n, 24, cover=0.9, seg_size=300), make_scan(rng, 1, 1, labels=["bed"])]
+    donotcare = tuple(i for i in sorted(set(LABEL_MAP.values())) if i % 2 == 1)
+    got = export(scans, donotcare)
+    want = want_of(scans, donotcare, 24)
+    kept = int(want["offsets"][1])
+    assert n // 4 < kept < 3 * n // 4 and want["offsets"][2] == kept + 1   # the big scene is compacted, the single vertex stays
+    assert_equal(got, want, "1025 tiles")
+
+
 def test_two_runs_give_the_same_bits(ragged):
     a, b = export(ragged, (1, 2)), export(ragged, (1, 2))
     for k in FLOAT_KEYS:

@@ -12,6 +12,7 @@
 // and vdetr_cuboid_compose_i32 one: choices[b, j] = kept_rows[b][drawn[b, j]].  Partials go out with ordinary stores: no
 // atomics, no ticket, nothing that depends on scheduling (README "Two findings about the chip"), so two runs give the same
 // bits.  Every decision is a comparison of exactly defined values (include/vdetr_hip.h), -ffp-contract=off as everywhere.
+#include "block_scan.h"
 #include "scene_tiles.h"
 
 namespace vdetr {
@@ -271,12 +272,8 @@ __global__ __launch_bounds__(kTile) void cuboid_compact_kernel(vdetr_cuboid_desc
     const float x = src[0], y = src[1], z = src[2];
     in = (double)x <= q[0] && (double)y <= q[1] && (double)z <= q[2] && (double)x >= q[3] && (double)y >= q[4] && (double)z >= q[5];
   }
-  const unsigned long long mask = __ballot(in);
-  const int lane = tid & (kWave - 1), wave = tid / kWave;
-  if (lane == 0) wave_count[wave] = __popcll(mask);
-  __syncthreads();
-  int to = tile_base[t] + __popcll(mask & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) to += wave_count[w];
+  int in_tile;
+  const int to = tile_base[t] + block_rank<kTile>(in, wave_count, in_tile);
   if (in && to < kept_rows && to < rows) d.kept_rows[begin + to] = j;   // the counts and this test agree: the bound is a guard
 }
 

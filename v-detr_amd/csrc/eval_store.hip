@@ -13,37 +13,28 @@
 // reads from the store and compacts its tile with a ballot, so the rows land in (scene, ascending index) order whatever
 // order the workgroups run in.  `cursors`: one workgroup recounts every scene and writes box_begin / gt_begin, the cursors
 // and the dropped-row count.  Counting is integer arithmetic and every row has exactly one writer: two runs, same bits.
-#include "common.h"
+#include "block_scan.h"
 
 namespace vdetr {
 namespace {
 
 constexpr int kTile = 256;
 
-// number of non-zero flags in f[0 .. n), the same value in every thread of a 256-thread workgroup
-__device__ int block_count(const uint8_t* __restrict__ f, long n, int* sh) {
-  int c = 0;
-  for (long i = threadIdx.x; i < n; i += kTile) c += f[i] != 0;
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-  __syncthreads();  // (sh may still be read by the previous call)
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+typedef int WaveRow[kTile / kWave];
+
+// number of non-zero flags in f[0 .. n), the same value in every thread of the workgroup
+__device__ int flag_count(const uint8_t* __restrict__ f, long n, WaveRow& sh) {
+  return block_sum<kTile>(n, [&](long i) { return (int)(f[i] != 0); }, sh);
 }
 
 // Rows i of tile `tile` of scene b with flag[b,i] != 0 -> positions base + (number of flags in front), in ascending order.
 // Returns the row's position or -1 (not flagged, or outside [0, capacity): the store's cursor is device data).
-__device__ long tile_position(const uint8_t* __restrict__ flag, int b, int n, int tile, long base, int capacity, int* sh) {
-  const long front = block_count(flag, (long)b * n + (long)tile * kTile, sh);
-  const int i = tile * kTile + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__device__ long tile_position(const uint8_t* __restrict__ flag, int b, int n, int tile, long base, int capacity, WaveRow& sh) {
+  const long front = flag_count(flag, (long)b * n + (long)tile * kTile, sh);
+  const int i = tile * kTile + threadIdx.x;
   const bool on = i < n && flag[(size_t)b * n + i] != 0;
-  const unsigned long long m = __ballot(on);
-  __syncthreads();
-  if (lane == 0) sh[wave] = __popcll(m);
-  __syncthreads();
-  int before = __popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) before += sh[w];
-  const long pos = base + front + before;
+  int in_tile;
+  const long pos = base + front + block_rank<kTile>(on, sh, in_tile);
   return on && pos >= 0 && pos < capacity ? pos : -1;
 }
 
@@ -52,7 +43,7 @@ __global__ __launch_bounds__(kTile) void det_append_rows_kernel(vdetr_det_store 
                                                                 const int32_t* __restrict__ cls, const float* __restrict__ gt_corners,
                                                                 const int32_t* __restrict__ gt_cls, const uint8_t* __restrict__ present,
                                                                 int K, int G, int box_tiles, int scan_base) {
-  __shared__ int sh[4];
+  __shared__ WaveRow sh;
   const int b = blockIdx.y;
   if ((int)blockIdx.x < box_tiles) {
     const long pos = tile_position(keep, b, K, blockIdx.x, st.counters[0], st.box_capacity, sh);
@@ -81,13 +72,13 @@ __device__ __forceinline__ long beyond(long start, long end, long capacity) {
 __global__ __launch_bounds__(kTile) void det_append_cursors_kernel(vdetr_det_store st, const uint8_t* __restrict__ keep,
                                                                    const uint8_t* __restrict__ present, int B, int K, int G,
                                                                    int scan_base) {
-  __shared__ int sh[4];
+  __shared__ WaveRow sh;
   const long box0 = st.counters[0], gt0 = st.counters[1];
   long box = box0, gt = gt0;
   for (int b = 0; b < B; ++b) {  // (scan_base + B <= scan_capacity: checked on the host, both are host values)
     if (threadIdx.x == 0) st.box_begin[scan_base + b] = (int)box, st.gt_begin[scan_base + b] = (int)gt;
-    box += block_count(keep + (size_t)b * K, K, sh);
-    if (G > 0) gt += block_count(present + (size_t)b * G, G, sh);
+    box += flag_count(keep + (size_t)b * K, K, sh);
+    if (G > 0) gt += flag_count(present + (size_t)b * G, G, sh);
   }
   if (threadIdx.x == 0) {
     st.box_begin[scan_base + B] = (int)box;
@@ -109,28 +100,12 @@ __global__ __launch_bounds__(kTile) void det_append_cursors_kernel(vdetr_det_sto
 // adds (1 - rec) * 0.
 constexpr int kApItems = 8, kApChunk = kTile * kApItems;
 
-// exclusive scan over the threads in ascending order + the total, Hillis-Steele in LDS
-template <typename T, typename Op>
-__device__ T block_exscan(T v, T identity, Op op, T* sh, T* total) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < kTile; o <<= 1) {
-    const T add = t >= o ? sh[t - o] : identity;
-    __syncthreads();
-    sh[t] = op(add, sh[t]);
-    __syncthreads();
-  }
-  *total = sh[kTile - 1];
-  return t > 0 ? sh[t - 1] : identity;
-}
-
 __global__ __launch_bounds__(kTile) void voc_ap_kernel(const uint8_t* __restrict__ tp, const int* __restrict__ seg,
                                                        const int* __restrict__ npos, int P, int C, double* __restrict__ out,
                                                        double* __restrict__ rec, double* __restrict__ prec) {
-  __shared__ int s_i[kTile];
-  __shared__ double s_d[kTile];
+  __shared__ WaveRow row_i;
+  __shared__ double row_d[kTile / kWave];
+  __shared__ double s_acc[kTile];  // the final sum of acc
   const int c = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
   int lo = seg[c], hi = seg[c + 1];  // device data: clamped to the flags that exist
   lo = lo < 0 ? 0 : (lo > P ? P : lo);
@@ -140,12 +115,9 @@ __global__ __launch_bounds__(kTile) void voc_ap_kernel(const uint8_t* __restrict
   const uint8_t* __restrict__ f = tp + (size_t)t * P + lo;
   double* r_out = rec ? rec + (size_t)t * P + lo : nullptr;
   double* p_out = prec ? prec + (size_t)t * P + lo : nullptr;
-  auto plus = [](int a, int b) { return a + b; };
   auto vmax = [](double a, double b) { return fmax(a, b); };
 
-  int mine = 0, total = 0;
-  for (int i = tid; i < n; i += kTile) mine += f[i] != 0;
-  block_exscan(mine, 0, plus, s_i, &total);
+  const int total = flag_count(f, n, row_i);
 
   int behind = 0;      // true positives behind the chunk
   double env = 0.0;    // envelope behind the chunk; voc_ap's mpre ends in 0
@@ -160,7 +132,7 @@ __global__ __launch_bounds__(kTile) void voc_ap_kernel(const uint8_t* __restrict
       cnt += fl[k];
     }
     int chunk_cnt;
-    int later = behind + block_exscan(cnt, 0, plus, s_i, &chunk_cnt);
+    int later = behind + block_exclusive_sum<kTile>(cnt, row_i, chunk_cnt);
     int tpc[kApItems];
     double pr[kApItems], mx = 0.0;
 #pragma unroll
@@ -171,7 +143,7 @@ __global__ __launch_bounds__(kTile) void voc_ap_kernel(const uint8_t* __restrict
       mx = fmax(mx, pr[k]);
     }
     double chunk_max;
-    double e = fmax(env, block_exscan(mx, 0.0, vmax, s_d, &chunk_max));
+    double e = fmax(env, block_exclusive_scan<kTile>(mx, 0.0, vmax, row_d, chunk_max));
 #pragma unroll
     for (int k = 0; k < kApItems; ++k) {
       if (first - k < 0) continue;
@@ -184,15 +156,15 @@ __global__ __launch_bounds__(kTile) void voc_ap_kernel(const uint8_t* __restrict
     env = fmax(env, chunk_max);
   }
   __syncthreads();
-  s_d[tid] = acc;
+  s_acc[tid] = acc;
   __syncthreads();
   for (int o = kTile / 2; o > 0; o >>= 1) {
-    if (tid < o) s_d[tid] = s_d[tid] + s_d[tid + o];
+    if (tid < o) s_acc[tid] = s_acc[tid] + s_acc[tid + o];
     __syncthreads();
   }
   if (tid == 0) {
     double* o = out + (size_t)t * 4 * C;
-    o[c] = n > 0 ? s_d[0] : 0.0;
+    o[c] = n > 0 ? s_acc[0] : 0.0;
     o[C + c] = n > 0 && np > 0 ? (double)total / dnp : 0.0;
     o[2 * C + c] = (double)n;
     o[3 * C + c] = dnp;

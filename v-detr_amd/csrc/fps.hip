@@ -25,6 +25,7 @@
 //             any reduction shape reproduces it.
 // Work drops from n*(m-1) distance evaluations to roughly 4 n ln m; the per-round cost is a few L2
 // round trips instead of a 640 KB sweep.
+#include "block_scan.h"
 #include "fps.h"
 #include "workspace.h"
 
@@ -164,12 +165,7 @@ __global__ __launch_bounds__(kFpsThreads) void fps_kernel(FpsParams Pin) {
     int v[kPer], sum = 0;
 #pragma unroll
     for (int i = 0; i < kPer; ++i) { v[i] = s_hist[tid * kPer + i]; sum += v[i]; }
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const int o = __shfl_up(incl, off);
-      if (lane >= off) incl += o;
-    }
+    const int incl = wave_inclusive_sum(sum);  // (block_scan.h; the wave sums stay written out: the kernel's code is pinned)
     if (lane == kWave - 1) s_wsum[w] = incl;
     __syncthreads();
     int base = 0;

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(W * kWave) void fps_rows_kernel(RowsParams Pin) {
   {
     int sum = 0;
     for (int i = 0; i < kPer; ++i) sum += s_hist[hidx(tid * kPer + i)];
-    int incl = sum;
+    int incl = sum;  // wave_inclusive_sum of block_scan.h, written out: calling it moves this kernel's code
 #pragma unroll
     for (int off = 1; off < kWave; off <<= 1) {
       const int o = __shfl_up(incl, off);
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(W * kWave) void fps_rows_kernel(RowsParams Pin) {
       s_leaf[c] = nbk;
       sum += nbk;
     }
-    int incl = sum;
+    int incl = sum;  // (written out as above)
 #pragma unroll
     for (int off = 1; off < kWave; off <<= 1) {
       const int o = __shfl_up(incl, off);

@@ -17,6 +17,7 @@
 // scene is never followed: the face's weight is NaN and only its in-range corners are listed.  -ffp-contract=off as everywhere:
 // every product, difference and sum below is one IEEE float32 operation; `/` and sqrtf are the correctly rounded forms (no
 // fast-math, not the native sqrt), float32 subnormals are kept (the compiler's default mode for kernels).
+#include "block_scan.h"
 #include "scene_tiles.h"
 
 namespace vdetr {
@@ -99,23 +100,6 @@ __global__ __launch_bounds__(kTile) void normals_face_kernel(vdetr_normals_desc 
     if (ok[c]) atomicAdd(&k.count[vbegin + (int)idx[c]], 1);
 }
 
-// exclusive scan of one value per lane over the 256 lanes of the workgroup; `total` is the workgroup's sum
-__device__ __forceinline__ int block_exclusive(int s, int* lds, int& total) {
-  const int tid = threadIdx.x;
-  lds[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const int below = tid >= o ? lds[tid - o] : 0;
-    __syncthreads();
-    lds[tid] += below;
-    __syncthreads();
-  }
-  total = lds[255];
-  const int mine = lds[tid] - s;
-  __syncthreads();
-  return mine;
-}
-
 __device__ __forceinline__ int lane_counts(const Work& k, int tile, int (&c)[kScanRows]) {
   const long first = (long)tile * kScanTile + (long)threadIdx.x * kScanRows;
   int s = 0;
@@ -128,28 +112,22 @@ __device__ __forceinline__ int lane_counts(const Work& k, int tile, int (&c)[kSc
 }
 
 __global__ __launch_bounds__(256) void normals_tile_sum_kernel(Work k) {
-  __shared__ int lds[256];
-  int c[kScanRows], total;
-  block_exclusive(lane_counts(k, blockIdx.x, c), lds, total);
+  __shared__ int wave_sums[256 / kWave];
+  int c[kScanRows];
+  int total;
+  block_exclusive_sum<256>(lane_counts(k, blockIdx.x, c), wave_sums, total);
   if (threadIdx.x == 0) k.tile_sum[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void normals_top_scan_kernel(Work k) {   // one workgroup
-  __shared__ int lds[256];
-  int carry = 0;
-  for (int base = 0; base < k.tiles; base += 256) {
-    const int t = base + threadIdx.x;
-    int total;
-    const int before = block_exclusive(t < k.tiles ? k.tile_sum[t] : 0, lds, total);
-    if (t < k.tiles) k.tile_sum[t] = carry + before;
-    carry += total;
-  }
+  __shared__ int wave_sums[256 / kWave];
+  block_exclusive_sum_array<256>(k.tile_sum, k.tile_sum, k.tiles, wave_sums);
 }
 
 __global__ __launch_bounds__(256) void normals_starts_kernel(Work k) {
-  __shared__ int lds[256];
+  __shared__ int wave_sums[256 / kWave];
   int c[kScanRows], total;
-  int at = k.tile_sum[blockIdx.x] + block_exclusive(lane_counts(k, blockIdx.x, c), lds, total);
+  int at = k.tile_sum[blockIdx.x] + block_exclusive_sum<256>(lane_counts(k, blockIdx.x, c), wave_sums, total);
   const long first = (long)blockIdx.x * kScanTile + (long)threadIdx.x * kScanRows;
 #pragma unroll
   for (int r = 0; r < kScanRows; ++r) {

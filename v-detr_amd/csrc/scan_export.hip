@@ -13,6 +13,7 @@
 //     scan_export_compact_kernel  drop table only: one workgroup per tile moves its kept rows and labels up, order kept
 // Min and max do not depend on the order of their operands and only integers go through atomics: two runs give the same bits.
 // -ffp-contract=off as everywhere: the alignment is three products and three sums, each one IEEE float64 operation.
+#include "block_scan.h"
 #include "scene_tiles.h"
 
 namespace vdetr {
@@ -54,22 +55,6 @@ __device__ __forceinline__ int scene_objects(const vdetr_scan_export_desc& d, in
 
 __device__ __forceinline__ bool dropped(const vdetr_scan_export_desc& d, int sem) {
   return sem >= 0 && sem < d.drop_table_len && d.drop_table[sem] != 0;
-}
-
-// rows of the workgroup's tile that `keep` holds in lower lanes, and their number over the tile
-__device__ __forceinline__ int rank_in_tile(bool keep, int (&wave_kept)[kTile / kWave], int& total) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const unsigned long long mask = __ballot(keep);
-  if (lane == 0) wave_kept[wave] = __popcll(mask);
-  __syncthreads();
-  int before = __popcll(mask & ((1ull << lane) - 1ull));
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kTile / kWave; ++w) {
-    if (w < wave) before += wave_kept[w];
-    total += wave_kept[w];
-  }
-  return before;
 }
 
 __global__ __launch_bounds__(kTile) void scan_export_points_kernel(vdetr_scan_export_desc d, int total_rows, Work w) {
@@ -122,7 +107,7 @@ __global__ __launch_bounds__(kTile) void scan_export_points_kernel(vdetr_scan_ex
   for (int i = tid; i < K * 6; i += kTile) out[i] = table[i];
   if (d.drop_table_len > 0) {
     int total;
-    rank_in_tile(keep, wave_kept, total);
+    block_rank<kTile>(keep, wave_kept, total);
     if (tid == 0) w.tile_kept[t] = total;
   }
 }
@@ -130,8 +115,7 @@ __global__ __launch_bounds__(kTile) void scan_export_points_kernel(vdetr_scan_ex
 __global__ __launch_bounds__(kBoxLanes) void scan_export_boxes_kernel(vdetr_scan_export_desc d, int num_tiles, Work w) {
   __shared__ unsigned merged[kMaxK * 6];
   __shared__ int wave_count[kBoxLanes / kWave];
-  __shared__ int scan[kBoxLanes];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int rows = d.offsets[b + 1] - d.offsets[b];
   const int first = first_tile(d.offsets, b, kTile), nt = tiles_of(rows, kTile);
   const int K = scene_objects(d, b);
@@ -185,15 +169,9 @@ __global__ __launch_bounds__(kBoxLanes) void scan_export_boxes_kernel(vdetr_scan
       if (label >= 0 && label < d.class_table_len) cls = d.class_table[label];
     }
     const bool keep = k < K && cls >= 0;                                      // a row of zeros has label 0, as in the reference
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0) wave_count[wave] = __popcll(mask);
-    __syncthreads();
-    int to = kept + __popcll(mask & ((1ull << lane) - 1ull));
-#pragma unroll
-    for (int i = 0; i < kBoxLanes / kWave; ++i) {
-      if (i < wave) to += wave_count[i];
-      kept += wave_count[i];
-    }
+    int kept_here;
+    const int to = kept + block_rank<kBoxLanes>(keep, wave_count, kept_here);
+    kept += kept_here;
     if (keep && to < d.Kmax) {
       float* o = d.boxes + ((size_t)b * d.Kmax + to) * 6;
 #pragma unroll
@@ -201,7 +179,6 @@ __global__ __launch_bounds__(kBoxLanes) void scan_export_boxes_kernel(vdetr_scan
       d.box_nyu40[(size_t)b * d.Kmax + to] = label;
       d.box_classes[(size_t)b * d.Kmax + to] = cls;
     }
-    __syncthreads();
   }
   for (int g = kept + tid; g < d.Kmax; g += kBoxLanes) {
     float* o = d.boxes + ((size_t)b * d.Kmax + g) * 6;
@@ -212,22 +189,7 @@ __global__ __launch_bounds__(kBoxLanes) void scan_export_boxes_kernel(vdetr_scan
   }
   if (tid == 0) d.box_counts[b] = kept;
   if (d.drop_table_len > 0) {                                                 // uniform: exclusive scan of the tiles' kept rows
-    int carry = 0;
-    for (int base = 0; base < n; base += kBoxLanes) {
-      const int i = base + tid;
-      const int mine = i < n ? w.tile_kept[first + i] : 0;
-      scan[tid] = mine;
-      __syncthreads();
-      for (int o = 1; o < kBoxLanes; o <<= 1) {
-        const int below = tid >= o ? scan[tid - o] : 0;
-        __syncthreads();
-        scan[tid] += below;
-        __syncthreads();
-      }
-      if (i < n) w.tile_base[first + i] = carry + scan[tid] - mine;
-      carry += scan[kBoxLanes - 1];
-      __syncthreads();
-    }
+    const int carry = block_exclusive_sum_array<kBoxLanes>(w.tile_kept + first, w.tile_base + first, n, wave_count);
     if (tid == 0) d.kept_counts[b] = carry;
   }
 }
@@ -246,7 +208,7 @@ __global__ __launch_bounds__(kTile) void scan_export_compact_kernel(vdetr_scan_e
   const int sem = in ? d.semantic[r] : 0;
   const bool keep = in && !dropped(d, sem);
   int total;
-  const long to = base + rank_in_tile(keep, wave_kept, total);
+  const long to = base + block_rank<kTile>(keep, wave_kept, total);
   if (keep && to < total_rows) {                                              // the counts and this test agree: the bound is a guard
     const float* src = d.out_vertices + (size_t)r * d.W;
     float* dst = d.kept_vertices + (size_t)to * d.W;

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
+#include "block_scan.h"
 #include "bn_common.h"
 
 namespace vdetr {
@@ -72,37 +73,28 @@ __global__ __launch_bounds__(256) void sp_inverse_map_kernel(const int* __restri
 // pairs sorted by (offset k, output row u): pass 1 counts the occupied neighbours per (k, block of 256 rows), pass 2 scans the
 // block counts, pass 3 writes pin / pout / slot / islot at block offset + rank in the block.  Deterministic (no atomics).
 __global__ __launch_bounds__(256) void sp_plan_count_kernel(const int* __restrict__ nbr, int nout, int nb, int* __restrict__ bc) {
-  __shared__ int w[4];
+  __shared__ int w[256 / kWave];
   const int b = blockIdx.x, k = blockIdx.y, u = b * 256 + threadIdx.x;
   const bool v = u < nout && nbr[(size_t)k * nout + u] >= 0;
-  const unsigned long long m = __ballot(v);
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) bc[k * nb + b] = w[0] + w[1] + w[2] + w[3];
+  int total;
+  block_rank<256>(v, w, total);
+  if (threadIdx.x == 0) bc[k * nb + b] = total;
 }
 
 __global__ __launch_bounds__(1024) void sp_plan_scan_kernel(int* __restrict__ bc, int n, int nb, int K, int* __restrict__ counts) {
-  __shared__ int part[1024];
+  __shared__ int w[1024 / kWave];
   const int t = threadIdx.x, per = (n + 1023) / 1024;
   const int lo = min(t * per, n), hi = min(lo + per, n);
   int s = 0;
   for (int i = lo; i < hi; ++i) s += bc[i];
-  part[t] = s;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const int v = t >= d ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int run = part[t] - s;
+  int total;
+  int run = block_exclusive_sum<1024>(s, w, total);
   for (int i = lo; i < hi; ++i) {
     const int c = bc[i];
     bc[i] = run;  // exclusive offset of block i in (k, b) order
     run += c;
   }
   __syncthreads();
-  const int total = part[1023];
   if (t < K) counts[t] = (t + 1 < K ? bc[(t + 1) * nb] : total) - bc[t * nb];
   if (t == 0) counts[K] = total;
 }
@@ -110,15 +102,12 @@ __global__ __launch_bounds__(1024) void sp_plan_scan_kernel(int* __restrict__ bc
 __global__ __launch_bounds__(256) void sp_plan_fill_kernel(const int* __restrict__ nbr, int nout, int nin, int nb,
                                                           const int* __restrict__ boff, int* __restrict__ pin,
                                                           int* __restrict__ pout, int* __restrict__ slot, int* __restrict__ islot) {
-  __shared__ int w[4];
-  const int b = blockIdx.x, k = blockIdx.y, u = b * 256 + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  __shared__ int w[256 / kWave];
+  const int b = blockIdx.x, k = blockIdx.y, u = b * 256 + threadIdx.x;
   const int i = u < nout ? nbr[(size_t)k * nout + u] : -1;
   const bool v = i >= 0;
-  const unsigned long long m = __ballot(v);
-  if (lane == 0) w[wv] = __popcll(m);
-  __syncthreads();
-  int p = boff[k * nb + b] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int j = 0; j < wv; ++j) p += w[j];
+  int total;
+  const int p = boff[k * nb + b] + block_rank<256>(v, w, total);
   if (v) {
     pin[p] = i;
     pout[p] = u;

@@ -6,11 +6,7 @@
 // commented `self.pruning = ME.MinkowskiPruning()` beside it.  MinkowskiEngine is un-vendored: the semantics are this package's
 // own, DESIGN 6.11.
 //
-// Geometry.  Both maps are the same two-launch compaction; nothing waits between the launches:
-//   launch 1  one workgroup per tile of kUnionTile keys flags its keys and writes ONE count per tile with an ordinary store
-//   launch 2  every workgroup adds up the counts of the tiles before its own (T <= a few hundred words), scans its own flags and
-//             writes its rows of every output; the workgroup of the last tile writes the total
-// No "last workgroup adds up" ticket (README round 6: 43-68 us against 6 us for two launches on this chip), no atomics, no memset.
+// Geometry.  Both maps are the two-launch compaction of block_scan.h over tiles of kUnionTile keys.
 // The outputs are allocated at their bound (na + nb, N) and the total is the ONE 4-byte word the host reads, after launch 2.
 //
 // Union of A [na] and B [nb] (sorted, unique), symmetric in the two sides.  With q(i) = |{j : B[j] < A[i]}| (a binary search) and
@@ -22,6 +18,7 @@
 //
 // Features.  Whole-row gathers as in sparse_pool.hip: a thread owns one row's channel quad (16 bytes).  A missing operand is
 // SELECTED as zero, not multiplied away: an infinity on a row the other side lacks stays an infinity.
+#include "block_scan.h"
 #include "workspace.h"
 
 namespace vdetr {
@@ -31,38 +28,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kUnionThreads = 256;
 constexpr int kUnionItems = 4;                             // consecutive keys per thread
 constexpr int kUnionTile = kUnionThreads * kUnionItems;    // keys per workgroup (vdetr_sp_union_tile)
-
-// exclusive prefix of v over the workgroup's threads (+ the workgroup's total).  Every thread calls it.
-__device__ __forceinline__ int block_exclusive_scan(int v, int (&wave_sums)[kUnionThreads / kWave], int& total) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int o = __shfl_up(inc, d, kWave);
-    if (lane >= d) inc += o;
-  }
-  if (lane == kWave - 1) wave_sums[wave] = inc;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kUnionThreads / kWave; ++w) {
-    const int s = wave_sums[w];
-    if (w < wave) before += s;
-    total += s;
-  }
-  __syncthreads();  // (the caller may scan again)
-  return before + inc - v;
-}
-
-// sum of counts[0 .. n) over the workgroup; every thread calls it and gets the sum
-__device__ __forceinline__ int block_sum_of(const int* counts, int n, int (&wave_sums)[kUnionThreads / kWave]) {
-  int s = 0;
-  for (int i = threadIdx.x; i < n; i += kUnionThreads) s += counts[i];
-  int total;
-  block_exclusive_scan(s, wave_sums, total);
-  return total;
-}
 
 __device__ __forceinline__ int lower_bound_i64(const int64_t* keys, int n, int64_t key) {
   int lo = 0, hi = n;
@@ -103,7 +68,7 @@ __global__ __launch_bounds__(kUnionThreads) void union_search_kernel(UnionParams
     matches += found ? 1 : 0;
   }
   int total;
-  block_exclusive_scan(matches, wave_sums, total);
+  block_exclusive_sum<kUnionThreads>(matches, wave_sums, total);
   if (threadIdx.x == 0) P.tile_matches[blockIdx.x] = total;
 }
 
@@ -118,7 +83,8 @@ __global__ __launch_bounds__(kUnionThreads) void union_fill_kernel(UnionParams P
   int* src_x = side_a ? P.src_a : P.src_b;
   int* src_y = side_a ? P.src_b : P.src_a;
   const int cap = P.na + P.nb;
-  const int before = block_sum_of(P.tile_matches + (side_a ? 0 : P.ta), tile, wave_sums);  // matches in this side's earlier tiles
+  const int* counts = P.tile_matches + (side_a ? 0 : P.ta);  // matches in this side's earlier tiles
+  const int before = block_sum<kUnionThreads>(tile, [&](int i) { return counts[i]; }, wave_sums);
   const int first = tile * kUnionTile + (int)threadIdx.x * kUnionItems;
   unsigned w[kUnionItems];
   int matches = 0;
@@ -128,7 +94,7 @@ __global__ __launch_bounds__(kUnionThreads) void union_fill_kernel(UnionParams P
     matches += (int)(w[e] >> 31);
   }
   int total;
-  int m = before + block_exclusive_scan(matches, wave_sums, total);
+  int m = before + block_exclusive_sum<kUnionThreads>(matches, wave_sums, total);
 #pragma unroll
   for (int e = 0; e < kUnionItems; ++e) {
     const int i = first + e;
@@ -164,13 +130,13 @@ __global__ __launch_bounds__(kUnionThreads) void prune_count_kernel(PruneParams 
   for (int e = 0; e < kUnionItems; ++e)
     if (first + e < P.n) keep += P.mask[first + e] ? 1 : 0;
   int total;
-  block_exclusive_scan(keep, wave_sums, total);
+  block_exclusive_sum<kUnionThreads>(keep, wave_sums, total);
   if (threadIdx.x == 0) P.tile_counts[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kUnionThreads) void prune_fill_kernel(PruneParams P) {
   __shared__ int wave_sums[kUnionThreads / kWave];
-  const int before = block_sum_of(P.tile_counts, (int)blockIdx.x, wave_sums);
+  const int before = block_sum<kUnionThreads>((int)blockIdx.x, [&](int i) { return P.tile_counts[i]; }, wave_sums);
   const int first = (int)blockIdx.x * kUnionTile + (int)threadIdx.x * kUnionItems;
   bool k[kUnionItems];
   int keep = 0;
@@ -180,7 +146,7 @@ __global__ __launch_bounds__(kUnionThreads) void prune_fill_kernel(PruneParams P
     keep += k[e] ? 1 : 0;
   }
   int total;
-  int rank = before + block_exclusive_scan(keep, wave_sums, total);
+  int rank = before + block_exclusive_sum<kUnionThreads>(keep, wave_sums, total);
 #pragma unroll
   for (int e = 0; e < kUnionItems; ++e) {
     const int i = first + e;

@@ -13,18 +13,18 @@
 // the key -1: legal keys are non-negative, so after the sort ONE comparison of the first sorted key is the range flag.  No memset,
 // no atomics, every thread writes only its own key.
 //
-// Sites.  The same two-launch compaction as sparse_union.hip, over the SORTED keys and the sort's permutation:
-//   launch 1  a workgroup per tile of kVoxelTile sorted keys counts its run heads (key[i] != key[i - 1]) into ONE word per tile
-//   launch 2  every workgroup adds up the counts of the tiles before its own, scans its heads and writes, per sorted position i
-//             of site row r: inverse[order[i]] = r, order32[i]; per head: sites[r], first[r] = order[i] (the stable sort makes the
-//             head the lowest input row of the run), seg[r] = i.  The workgroup of the last tile writes seg[M], M and the flag
-//             (or, in its place, the highest batch index + 1: the last key holds it).
+// Sites.  The two-launch compaction of block_scan.h over tiles of kVoxelTile SORTED keys and the sort's permutation.  What is
+// counted are the run heads (key[i] != key[i - 1]).  Launch 2 writes, per sorted position i of site row r: inverse[order[i]] = r,
+// order32[i]; per head: sites[r], first[r] = order[i] (the stable sort makes the head the lowest input row of the run),
+// seg[r] = i.  The workgroup of the last tile writes seg[M], M and the flag (or, in its place, the highest batch index + 1: the
+// last key holds it).
 // A run may cross tiles or be longer than one: the site row is a global prefix of the heads, nothing is per tile but the count.
 //
 // Features.  One lane per (site, channel) folds the run in ascending input-row order in float32: two runs agree bit for bit and
 // np.add.at / np.maximum.at restate it.  Adjacent lanes read adjacent channels of one row.  A run of L points costs L dependent
 // loads on its lanes while the other lanes of the wave idle: L = N (every point in one voxel) is one workgroup's serial walk of
 // the whole table.  Real clouds at 1-5 cm voxels have runs of 1-8.  The gradients are gathers through `inverse`.
+#include "block_scan.h"
 #include "workspace.h"
 
 namespace vdetr {
@@ -85,29 +85,6 @@ __global__ __launch_bounds__(256) void coord_keys_kernel(CoordKeysParams P) {
 }
 
 // ---- sites -------------------------------------------------------------------------------------------------------------------------
-// exclusive prefix of v over the workgroup's threads (+ the workgroup's total).  Every thread calls it.
-__device__ __forceinline__ int voxel_block_scan(int v, int (&wave_sums)[kVoxelThreads / kWave], int& total) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int o = __shfl_up(inc, d, kWave);
-    if (lane >= d) inc += o;
-  }
-  if (lane == kWave - 1) wave_sums[wave] = inc;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kVoxelThreads / kWave; ++w) {
-    const int s = wave_sums[w];
-    if (w < wave) before += s;
-    total += s;
-  }
-  __syncthreads();  // (the caller scans again)
-  return before + inc - v;
-}
-
 struct VoxelSitesParams {
   int N, tiles;
   const int64_t* sorted;   // [N] ascending
@@ -131,16 +108,14 @@ __global__ __launch_bounds__(kVoxelThreads) void voxel_heads_kernel(VoxelSitesPa
   for (int e = 0; e < kVoxelItems; ++e)
     if (first + e < P.N) heads += run_head(P.sorted, first + e) ? 1 : 0;
   int total;
-  voxel_block_scan(heads, wave_sums, total);
+  block_exclusive_sum<kVoxelThreads>(heads, wave_sums, total);
   if (threadIdx.x == 0) P.tile_counts[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kVoxelThreads) void voxel_fill_kernel(VoxelSitesParams P) {
   __shared__ int wave_sums[kVoxelThreads / kWave];
-  int s = 0;
-  for (int t = threadIdx.x; t < (int)blockIdx.x; t += kVoxelThreads) s += P.tile_counts[t];
-  int before;
-  voxel_block_scan(s, wave_sums, before);  // heads in the earlier tiles
+  // heads in the earlier tiles
+  const int before = block_sum<kVoxelThreads>((int)blockIdx.x, [&](int t) { return P.tile_counts[t]; }, wave_sums);
   const int first = (int)blockIdx.x * kVoxelTile + (int)threadIdx.x * kVoxelItems;
   bool h[kVoxelItems];
   int heads = 0;
@@ -150,7 +125,7 @@ __global__ __launch_bounds__(kVoxelThreads) void voxel_fill_kernel(VoxelSitesPar
     heads += h[e] ? 1 : 0;
   }
   int total;
-  int rank = before + voxel_block_scan(heads, wave_sums, total);  // heads before this thread's keys
+  int rank = before + block_exclusive_sum<kVoxelThreads>(heads, wave_sums, total);  // heads before this thread's keys
 #pragma unroll
   for (int e = 0; e < kVoxelItems; ++e) {
     const int i = first + e;
