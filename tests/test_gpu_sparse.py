@@ -232,7 +232,11 @@ def test_pair_kernels_every_dispatch_arm(geom, cin, cout, multi):
 
 @pytest.mark.parametrize("n,c,act,res,training", [(5000, 64, "relu", True, True), (777, 256, "elu", False, True),
                                                   (130, 16, None, True, True), (3000, 512, "relu", False, False), (1, 8, "relu", False, True),
-                                                  (2554, 512, "relu", True, True), (300, 1024, "elu", False, True)])
+                                                  (2554, 512, "relu", True, True), (300, 1024, "elu", False, True),
+                                                  # channel counts that leave 256 % (c / 4) threads idle (csrc/table_moments.h):
+                                                  (130, 20, "relu", True, True),    # 51 row lanes, 1 idle; 9 tiles, the last ragged
+                                                  (4099, 12, None, False, True),    # 257 partials: the finalize loops' second round
+                                                  (50, 24, "elu", True, False)])    # eval arm, 4 idle; workgroup 0 saves mean / invstd
 def test_fused_batchnorm_activation(n, c, act, res, training):
     """csrc/sp_bn.hip against nn.BatchNorm1d + residual + activation in float64: outputs, all gradients, running statistics"""
     from vdetr_amd import sparse_ops as S

@@ -27,6 +27,7 @@
 // consecutive tokens — one float4 of the channel-major tensors the backward reads.
 #include "attn_common.h"
 #include "bn_common.h"
+#include "pos_bn.h"
 
 namespace vdetr {
 
@@ -521,14 +522,16 @@ __global__ __launch_bounds__(kHdThreads) void heads_infer_kernel(HiArgs A) {
 // lane per quad through LDS, the wave that owns a moment sums its 64 values); (2) thread = hidden channel: mean and variance of
 // w . x from the moments (fp64: 6 + 21 terms), the affine map, the channel's 16 hidden values; (3) the second convolution on the
 // matrix unit.  Everything phase 2 reads from global memory is requested before phase 1 starts.
+// rb_qkv_pos_kernel (rowblock_pos.hip) runs the same phases 1 and 2 on its row blocks; what the two share as code is pos_bn.h.
 typedef vdetr_posmlp_desc PmArgs;
 constexpr int kPmMaxIn = 8;
+static_assert(kHdThreads == kPosThreads, "pos_bn.h: thread = hidden channel, 256 of them");
 
 // INFER: the inference form (vdetr_pos_mlp_infer_f32) — the BatchNorm of the running statistics, phases 1 and the bookkeeping of
 // phase 2 drop out, and only `out` is written.
 template <int CIN, bool INFER>
 __global__ __launch_bounds__(kHdThreads) void pos_mlp_kernel(PmArgs A) {
-  constexpr int kMom = CIN + CIN * (CIN + 1) / 2;  // sums + upper triangle of the second moments
+  constexpr int kMom = pos_nmom(CIN);
   __shared__ __attribute__((aligned(16))) float xs[kHdTok3 * kHdStride];
   __shared__ float momq[kMom][64];
   __shared__ float mom[kMom];
@@ -550,7 +553,7 @@ __global__ __launch_bounds__(kHdThreads) void pos_mlp_kernel(PmArgs A) {
   for (int t = 0; t < kHdTok3; ++t)
 #pragma unroll
     for (int i = 0; i < CIN; ++i) xt[t][i] = A.x[((size_t)b * A.N + q0 + t) * CIN + i];  // (wave-uniform addresses: scalar loads)
-  // ---- phase 1 ----
+  // ---- phase 1 (twin: rowblock_pos.hip, rb_qkv_pos_kernel: same arithmetic, same order) ----
   if constexpr (!INFER) {
   double s[kMom];
 #pragma unroll
@@ -585,8 +588,9 @@ __global__ __launch_bounds__(kHdThreads) void pos_mlp_kernel(PmArgs A) {
   __syncthreads();
   }
   // ---- phase 2 ----
-  if constexpr (INFER) {  // relu(((W1 x + b1 - running_mean) * rsqrt(running_var + eps)) * gamma + beta) (torch's eval order)
-    const float rm = A.running_mean[ch], invstd = rsqrtf(A.running_var[ch] + A.eps);
+  if constexpr (INFER) {
+    float rm, invstd;
+    pos_infer_stats(A, rm, invstd);
 #pragma unroll
     for (int i = 0; i < kHdTok3; ++i) {
       float h = 0.f;
@@ -594,7 +598,7 @@ __global__ __launch_bounds__(kHdThreads) void pos_mlp_kernel(PmArgs A) {
       for (int k = 0; k < CIN; ++k) h = fmaf(xt[i][k], wv[k], h);
       xs[i * kHdStride + ch] = fmaxf(((h + bias1) - rm) * invstd * gam + bet, 0.f);
     }
-  } else {
+  } else {  // (the channel's statistics, down to sh: twin in rowblock_pos.hip)
     const double inv = 1.0 / (double)T;
     double mu[CIN];  // mean offset from the reference token
 #pragma unroll
@@ -615,16 +619,7 @@ __global__ __launch_bounds__(kHdThreads) void pos_mlp_kernel(PmArgs A) {
     const float meanf = (float)mean, varf = (float)var;
     const float invstd = rsqrtf(varf + A.eps);
     const float a = gam * invstd, sh = bet - meanf * a;
-    if (blockIdx.x == 0) {
-      A.save_mean[ch] = meanf;
-      A.save_invstd[ch] = invstd;
-      if (A.running_mean) {
-        const float m = A.momentum, n = (float)T;
-        A.running_mean[ch] = (1.f - m) * A.running_mean[ch] + m * (meanf + bias1);
-        A.running_var[ch] = (1.f - m) * A.running_var[ch] + m * varf * (n / (n > 1.f ? n - 1.f : 1.f));
-      }
-      if (tid == 0 && A.counter) A.counter[0] += 1;
-    }
+    if (blockIdx.x == 0) pos_store_stats(A, T, meanf, varf, invstd, bias1);
     f32x4 hp[4], ha[4];
 #pragma unroll
     for (int i = 0; i < kHdTok3; ++i) {
@@ -696,16 +691,7 @@ template <bool INFER>
 static int pos_mlp_launch(const vdetr_posmlp_desc* d, vdetr_stream_t stream, const char* op) {
   const dim3 grid(d->B * d->N / kHdTok3), block(kHdThreads);
   hipStream_t st = (hipStream_t)stream;
-  switch (d->cin) {
-    case 1: hipLaunchKernelGGL((pos_mlp_kernel<1, INFER>), grid, block, 0, st, *d); break;
-    case 2: hipLaunchKernelGGL((pos_mlp_kernel<2, INFER>), grid, block, 0, st, *d); break;
-    case 3: hipLaunchKernelGGL((pos_mlp_kernel<3, INFER>), grid, block, 0, st, *d); break;  // (key positions: pos_for_key)
-    case 4: hipLaunchKernelGGL((pos_mlp_kernel<4, INFER>), grid, block, 0, st, *d); break;
-    case 5: hipLaunchKernelGGL((pos_mlp_kernel<5, INFER>), grid, block, 0, st, *d); break;
-    case 6: hipLaunchKernelGGL((pos_mlp_kernel<6, INFER>), grid, block, 0, st, *d); break;  // (box centre + size: the decoder's query position)
-    case 7: hipLaunchKernelGGL((pos_mlp_kernel<7, INFER>), grid, block, 0, st, *d); break;
-    default: hipLaunchKernelGGL((pos_mlp_kernel<8, INFER>), grid, block, 0, st, *d); break;
-  }
+  dispatch_cin(d->cin, [&](auto cin) { hipLaunchKernelGGL((pos_mlp_kernel<cin(), INFER>), grid, block, 0, st, *d); });
   return check_launch(op);
 }
 

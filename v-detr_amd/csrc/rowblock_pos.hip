@@ -1,22 +1,25 @@
 // rowblock_pos.hip — rb_qkv with the learned query position computed on the way in (vdetr_rb_qkv_pos_f32).
 // Its own translation unit: the position MLP's scalar first convolution must be compiled without SLP vectorisation (build.py NO_SLP:
 // the packed-fma op_sel form the vectoriser makes of it), which rowblock.hip's epilogues want to keep.
+#include "pos_bn.h"
 #include "rowblock.h"
 
 namespace vdetr {
+
+static_assert(kRbThreads == kPosThreads, "pos_bn.h: thread = hidden channel, 256 of them");
 
 // ---- rb_qkv_pos_kernel: rb_qkv_kernel whose `pos` rows are computed on the way in (round 6) -------------------------------------
 // The learned query position (PositionEmbeddingLearned, helpers.py:17-33; heads.hip: pos_mlp_kernel) was a launch of its own in front
 // of every decoder layer: 15 us on the forward chain for a [16 x 256] x [256 x 256] product per workgroup behind a BatchNorm whose batch
 // statistics every workgroup derives itself from the coordinates' mean and covariance (heads.hip).  Its tiles are the row blocks of
-// rb_qkv: the q and k workgroups (blockIdx.y = 0, 1) now form their own 16 rows of it — same arithmetic, same order as pos_mlp_kernel —,
+// rb_qkv: the q and k workgroups (blockIdx.y = 0, 1) now form their own 16 rows of it — same arithmetic, same order as pos_mlp_kernel (pos_bn.h) —,
 // add them to the rows of norm1(tgt) in LDS and go on as before; the q workgroups write everything the position MLP's launch wrote
 // (pos, the hidden pre-/activations, the saved statistics; workgroup (0, 0) the running statistics).  The v workgroups are rb_qkv's.
 // INFER (vdetr_rb_qkv_pos_infer_f32): the position MLP's BatchNorm uses the running statistics (heads.hip: pos_mlp_kernel<., true>);
 // no moments, no bookkeeping, and of the position MLP's tensors only `out` is written.
 template <int CIN, bool INFER>
 __global__ __launch_bounds__(kRbThreads) void rb_qkv_pos_kernel(RbQkvArgs A, vdetr_posmlp_desc M) {
-  constexpr int kMom = CIN + CIN * (CIN + 1) / 2;  // sums + upper triangle of the second moments
+  constexpr int kMom = pos_nmom(CIN);
   __shared__ __attribute__((aligned(16))) float xs[kRbRows * kRbStride];
   __shared__ float momq[kMom][64];
   __shared__ float mom[kMom];
@@ -53,7 +56,8 @@ __global__ __launch_bounds__(kRbThreads) void rb_qkv_pos_kernel(RbQkvArgs A, vde
 #pragma unroll
       for (int i = 0; i < CIN; ++i) xt[t][i] = M.x[((size_t)b * M.N + q) * CIN + i];
     }
-    // ---- the coordinates' first and second moments over all B N tokens (heads.hip: pos_mlp_kernel, phase 1) ----
+    // ---- the coordinates' first and second moments over all B N tokens (twin: heads.hip, pos_mlp_kernel, phase 1:
+    // same arithmetic, same order) ----
     if constexpr (!INFER) {
     double sm[kMom];
 #pragma unroll
@@ -88,8 +92,9 @@ __global__ __launch_bounds__(kRbThreads) void rb_qkv_pos_kernel(RbQkvArgs A, vde
     __syncthreads();
     }
     // ---- BatchNorm of this thread's channel, relu(bn(W1 x)) of the 16 tokens into the tile (phase 2) ----
-    if constexpr (INFER) {  // relu(((W1 x + b1 - running_mean) * rsqrt(running_var + eps)) * gamma + beta) (torch's eval order)
-      const float rm = M.running_mean[ch], invstd = rsqrtf(M.running_var[ch] + M.eps);
+    if constexpr (INFER) {
+      float rm, invstd;
+      pos_infer_stats(M, rm, invstd);
 #pragma unroll
       for (int i = 0; i < kRbRows; ++i) {
         float h = 0.f;
@@ -97,7 +102,7 @@ __global__ __launch_bounds__(kRbThreads) void rb_qkv_pos_kernel(RbQkvArgs A, vde
         for (int k = 0; k < CIN; ++k) h = fmaf(xt[i][k], wv[k], h);
         xs[i * kRbStride + ch] = fmaxf(((h + bias1) - rm) * invstd * gam + bet, 0.f);
       }
-    } else {
+    } else {  // (the channel's statistics, down to sh: twin in heads.hip)
       const double inv = 1.0 / (double)T;
       double mu[CIN];
 #pragma unroll
@@ -118,16 +123,7 @@ __global__ __launch_bounds__(kRbThreads) void rb_qkv_pos_kernel(RbQkvArgs A, vde
       const float meanf = (float)mean, varf = (float)var;
       const float invstd = rsqrtf(varf + M.eps);
       const float sc = gam * invstd, sh = bet - meanf * sc;
-      if (blockIdx.x == 0 && which == 0) {
-        M.save_mean[ch] = meanf;
-        M.save_invstd[ch] = invstd;
-        if (M.running_mean) {
-          const float m = M.momentum, n = (float)T;
-          M.running_mean[ch] = (1.f - m) * M.running_mean[ch] + m * (meanf + bias1);
-          M.running_var[ch] = (1.f - m) * M.running_var[ch] + m * varf * (n / (n > 1.f ? n - 1.f : 1.f));
-        }
-        if (tid == 0 && M.counter) M.counter[0] += 1;
-      }
+      if (blockIdx.x == 0 && which == 0) pos_store_stats(M, T, meanf, varf, invstd, bias1);
       float hp[kRbRows], ha[kRbRows];
 #pragma unroll
       for (int i = 0; i < kRbRows; ++i) {
@@ -205,16 +201,7 @@ template <bool INFER>
 static int rb_qkv_pos_launch(const vdetr_rb_qkv_desc* d, const vdetr_posmlp_desc* m, vdetr_stream_t stream, const char* op) {
   const dim3 grid(d->rows / kRbRows, 3), block(kRbThreads);
   hipStream_t st = (hipStream_t)stream;
-  switch (m->cin) {
-    case 1: hipLaunchKernelGGL((rb_qkv_pos_kernel<1, INFER>), grid, block, 0, st, *d, *m); break;
-    case 2: hipLaunchKernelGGL((rb_qkv_pos_kernel<2, INFER>), grid, block, 0, st, *d, *m); break;
-    case 3: hipLaunchKernelGGL((rb_qkv_pos_kernel<3, INFER>), grid, block, 0, st, *d, *m); break;
-    case 4: hipLaunchKernelGGL((rb_qkv_pos_kernel<4, INFER>), grid, block, 0, st, *d, *m); break;
-    case 5: hipLaunchKernelGGL((rb_qkv_pos_kernel<5, INFER>), grid, block, 0, st, *d, *m); break;
-    case 6: hipLaunchKernelGGL((rb_qkv_pos_kernel<6, INFER>), grid, block, 0, st, *d, *m); break;  // (box centre + size: the decoder's query position)
-    case 7: hipLaunchKernelGGL((rb_qkv_pos_kernel<7, INFER>), grid, block, 0, st, *d, *m); break;
-    default: hipLaunchKernelGGL((rb_qkv_pos_kernel<8, INFER>), grid, block, 0, st, *d, *m); break;
-  }
+  dispatch_cin(m->cin, [&](auto cin) { hipLaunchKernelGGL((rb_qkv_pos_kernel<cin(), INFER>), grid, block, 0, st, *d, *m); });
   return check_launch(op);
 }
 

@@ -4,18 +4,18 @@
 // and in the residual blocks by `out += residual; relu` (models/mink_resnet.py:38-84 via MinkowskiEngine's BasicBlock;
 // models/model_vdetr.py:141-176).  ATen's channels-last statistics kernels take ~41 us per call on a [36k, 64] table (9 MB:
 // 2 us of HBM time) and the block needs 4-6 launches; here
-//   forward : stats partials (a workgroup per 128 rows: mean and sum of squared deviations from ITS mean, two sweeps over
-//             rows that stay in cache) -> apply (every workgroup merges the partials with Chan's formula in a fixed order —
+//   forward : stats partials (a workgroup per bn_rows(N) rows, 16 to 128: mean and sum of squared deviations from ITS mean, two
+//             sweeps over rows that stay in cache) -> apply (every workgroup merges the partials with Chan's formula in a fixed order —
 //             deterministic — and writes y = act(xhat * gamma + beta + residual); workgroup 0 also stores mean / invstd
 //             and updates the running statistics)
 //   backward: partials of sum(g), sum(g * xhat) with g = dy * act'(y) -> apply dx = gamma * invstd * (g - mean(g) -
 //             xhat * mean(g xhat)), dresidual = g; workgroup 0 stores dgamma / dbeta.
 // Pure HBM streams: x (and residual) read twice / once, y written once.
 #include "bn_common.h"
+#include "table_moments.h"
 
 namespace vdetr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBnRowsMin = 16, kBnRowsMax = 128;  // rows per workgroup: chosen so that a table gives >= ~1000 workgroups
 static inline int bn_rows(int N) { int r = N / 1024; r = r < kBnRowsMin ? kBnRowsMin : r > kBnRowsMax ? kBnRowsMax : r; return (r + 15) / 16 * 16; }
 
@@ -31,53 +31,13 @@ __device__ __forceinline__ f32x4 bn_act_grad(f32x4 dy, f32x4 y, int act) {
   return dy;
 }
 
-// thread layout: c4 = tid % C4 owns 4 channels, rs = tid / C4 walks rows rs, rs + RPI, ... of the workgroup's 128 rows
+// thread layout and partials: table_moments.h.  A workgroup takes bn_rows(N) rows, 16 to 128.
 // partial [nblk][3][C]: count, mean, M2   (forward)   /   [nblk][2][C]: sum g, sum g xhat   (backward)
 __global__ __launch_bounds__(256) void sp_bn_stats_kernel(const float* __restrict__ x, int N, int C, int kBnRows, float* __restrict__ part) {
   __shared__ f32x4 red[256];
-  const int C4 = C >> 2, tid = threadIdx.x, c4 = tid % C4, rs = tid / C4, rpi = 256 / C4;
+  const RowLanes L = row_lanes(C);
   const int r0 = blockIdx.x * kBnRows, r1 = min(N, r0 + kBnRows);
-  const bool act = rs < rpi;  // 256 % C4 leftover threads idle
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (act)
-    for (int r = r0 + rs; r < r1; r += rpi) s += reinterpret_cast<const f32x4*>(x)[(size_t)r * C4 + c4];
-  red[tid] = s;
-  __syncthreads();
-  f32x4 tot = {0.f, 0.f, 0.f, 0.f};
-  for (int j = 0; j < rpi; ++j) tot += red[j * C4 + c4];  // fixed order
-  const float cnt = (float)(r1 - r0);
-  const f32x4 mean = tot / cnt;
-  __syncthreads();
-  f32x4 m2 = {0.f, 0.f, 0.f, 0.f};
-  if (act)
-    for (int r = r0 + rs; r < r1; r += rpi) {
-      const f32x4 d = reinterpret_cast<const f32x4*>(x)[(size_t)r * C4 + c4] - mean;
-      m2 += d * d;
-    }
-  red[tid] = m2;
-  __syncthreads();
-  if (rs == 0) {
-    f32x4 t2 = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < rpi; ++j) t2 += red[j * C4 + c4];
-    float* p = part + (size_t)blockIdx.x * 3 * C;
-    reinterpret_cast<f32x4*>(p)[c4] = f32x4{cnt, cnt, cnt, cnt};
-    reinterpret_cast<f32x4*>(p + C)[c4] = mean;
-    reinterpret_cast<f32x4*>(p + 2 * C)[c4] = t2;
-  }
-}
-
-// Chan et al.: merge of (count, mean, M2) aggregates
-struct BnAgg {
-  float n;
-  f32x4 mu, m2;
-};
-__device__ __forceinline__ void bn_agg_add(BnAgg& a, float nb, const f32x4& mb, const f32x4& sb) {
-  if (nb <= 0.f) return;
-  const float nn = a.n + nb;
-  const f32x4 d = mb - a.mu;
-  a.mu += d * (nb / nn);
-  a.m2 += sb + d * d * (a.n * nb / nn);
-  a.n = nn;
+  rows_to_moments(L, x, C, r0, r1, part, red);
 }
 
 struct SpBnParams {
@@ -95,11 +55,8 @@ struct SpBnParams {
 __global__ __launch_bounds__(256) void sp_bn_finalize_kernel(SpBnParams P) {
   __shared__ float lds[4][9];
   const int c4 = blockIdx.x, tid = threadIdx.x;
-  BnAgg a{0.f, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  for (int b = tid; b < P.nblk; b += 256) {
-    const float* p = P.part + (size_t)b * 3 * P.C;
-    bn_agg_add(a, p[c4 * 4], reinterpret_cast<const f32x4*>(p + P.C)[c4], reinterpret_cast<const f32x4*>(p + 2 * P.C)[c4]);
-  }
+  Moments a{0.f, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  for (int b = tid; b < P.nblk; b += 256) moments_add_partial(a, P.part, b, P.C, c4);
   // fixed merge tree (deterministic): inside a wave through lane shuffles (no barrier), then the 4 wave aggregates through LDS.
   // (The first version merged all 256 aggregates through LDS: 8 levels, 16 barriers, 7.8 us for a few KB.)
 #pragma unroll
@@ -108,20 +65,12 @@ __global__ __launch_bounds__(256) void sp_bn_finalize_kernel(SpBnParams P) {
     f32x4 omu, om2;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { omu[e] = __shfl_down(a.mu[e], off); om2[e] = __shfl_down(a.m2[e], off); }
-    if ((tid & 63) < off) bn_agg_add(a, on, omu, om2);
+    if ((tid & 63) < off) moments_add(a, on, omu, om2);
   }
-  if ((tid & 63) == 0) {
-    float* o = lds[tid >> 6];
-    o[0] = a.n;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[1 + e] = a.mu[e]; o[5 + e] = a.m2[e]; }
-  }
+  if ((tid & 63) == 0) moments_store_lds(lds[tid >> 6], a);
   __syncthreads();
   if (tid == 0) {
-    for (int w2 = 1; w2 < 4; ++w2) {
-      const float* o = lds[w2];
-      bn_agg_add(a, o[0], f32x4{o[1], o[2], o[3], o[4]}, f32x4{o[5], o[6], o[7], o[8]});
-    }
+    for (int w2 = 1; w2 < 4; ++w2) moments_add_lds(a, lds[w2]);
   }
   if (tid == 0) {
     const f32x4 mean = a.mu, var = a.m2 / a.n;
@@ -142,7 +91,7 @@ __global__ __launch_bounds__(256) void sp_bn_finalize_kernel(SpBnParams P) {
 }
 
 __global__ __launch_bounds__(256) void sp_bn_apply_kernel(SpBnParams P) {
-  const int C4 = P.C >> 2, tid = threadIdx.x, c4 = tid % C4, rs = tid / C4, rpi = 256 / C4;
+  const auto [C4, c4, rs, rpi] = row_lanes(P.C);
   if (rs >= rpi) return;
   f32x4 mean, invstd;
   if (P.training) {  // left by sp_bn_finalize_kernel
@@ -178,63 +127,26 @@ struct SpBnGrads {
 // partial [nblk][2][C]: sum g, sum g * xhat
 __global__ __launch_bounds__(256) void sp_bn_bwd_stats_kernel(SpBnParams P, SpBnGrads G) {
   __shared__ f32x4 red[2][256];
-  const int C4 = P.C >> 2, tid = threadIdx.x, c4 = tid % C4, rs = tid / C4, rpi = 256 / C4;
+  const RowLanes L = row_lanes(P.C);
   const int r0 = blockIdx.x * P.rows, r1 = min(P.N, r0 + P.rows);
-  f32x4 sg = {0.f, 0.f, 0.f, 0.f}, sgx = {0.f, 0.f, 0.f, 0.f};
-  if (rs < rpi) {
-    const f32x4 mean = reinterpret_cast<const f32x4*>(P.save_mean)[c4], invstd = reinterpret_cast<const f32x4*>(P.save_invstd)[c4];
-    for (int r = r0 + rs; r < r1; r += rpi) {
-      const size_t i = (size_t)r * C4 + c4;
-      const f32x4 g = bn_act_grad(reinterpret_cast<const f32x4*>(G.dy)[i], reinterpret_cast<const f32x4*>(P.y)[i], P.act);
-      const f32x4 xh = (reinterpret_cast<const f32x4*>(P.x)[i] - mean) * invstd;
-      sg += g;
-      sgx += g * xh;
-    }
-  }
-  red[0][tid] = sg;
-  red[1][tid] = sgx;
-  __syncthreads();
-  if (rs == 0) {
-    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < rpi; ++j) { a += red[0][j * C4 + c4]; b += red[1][j * C4 + c4]; }
-    float* p = P.part + (size_t)blockIdx.x * 2 * P.C;
-    reinterpret_cast<f32x4*>(p)[c4] = a;
-    reinterpret_cast<f32x4*>(p + P.C)[c4] = b;
-  }
+  const auto grad = [&](size_t i) { return bn_act_grad(reinterpret_cast<const f32x4*>(G.dy)[i], reinterpret_cast<const f32x4*>(P.y)[i], P.act); };
+  rows_to_grad_sums(L, P.x, P.C, r0, r1, P.save_mean, P.save_invstd, grad, P.part, red);
 }
 
 // one workgroup per 4 channels: sums of the partials (thread t: partials t, t + 256, ...; fixed tree) -> sums, dgamma, dbeta
 __global__ __launch_bounds__(256) void sp_bn_bwd_finalize_kernel(SpBnParams P, SpBnGrads G) {
   __shared__ f32x4 red[2][4];
-  const int c4 = blockIdx.x, tid = threadIdx.x;
-  f32x4 sg = {0.f, 0.f, 0.f, 0.f}, sgx = {0.f, 0.f, 0.f, 0.f};
-  for (int b = tid; b < P.nblk; b += 256) {
-    const float* p = P.part + (size_t)b * 2 * P.C;
-    sg += reinterpret_cast<const f32x4*>(p)[c4];
-    sgx += reinterpret_cast<const f32x4*>(p + P.C)[c4];
-  }
-  // fixed tree: lane shuffles inside a wave, the 4 wave sums through LDS (one barrier instead of 16)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float a = __shfl_down(sg[e], off), b = __shfl_down(sgx[e], off);
-      if ((tid & 63) < off) { sg[e] += a; sgx[e] += b; }
-    }
-  }
-  if ((tid & 63) == 0) { red[0][tid >> 6] = sg; red[1][tid >> 6] = sgx; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w2 = 1; w2 < 4; ++w2) { sg += red[0][w2]; sgx += red[1][w2]; }
+  const int c4 = blockIdx.x;
+  partials_sum2(P.part, P.nblk, P.C, c4, red, [&](const f32x4& sg, const f32x4& sgx) {
     reinterpret_cast<f32x4*>(P.sums)[c4] = sg;
     reinterpret_cast<f32x4*>(P.sums + P.C)[c4] = sgx;
     if (G.dgamma) reinterpret_cast<f32x4*>(G.dgamma)[c4] = sgx;
     if (G.dbeta) reinterpret_cast<f32x4*>(G.dbeta)[c4] = sg;
-  }
+  });
 }
 
 __global__ __launch_bounds__(256) void sp_bn_bwd_apply_kernel(SpBnParams P, SpBnGrads G) {
-  const int C4 = P.C >> 2, tid = threadIdx.x, c4 = tid % C4, rs = tid / C4, rpi = 256 / C4;
+  const auto [C4, c4, rs, rpi] = row_lanes(P.C);
   if (rs >= rpi) return;
   const f32x4 sg = reinterpret_cast<const f32x4*>(P.sums)[c4], sgx = reinterpret_cast<const f32x4*>(P.sums + P.C)[c4];
   const f32x4 mean = reinterpret_cast<const f32x4*>(P.save_mean)[c4], invstd = reinterpret_cast<const f32x4*>(P.save_invstd)[c4];

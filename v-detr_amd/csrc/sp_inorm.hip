@@ -4,7 +4,8 @@
 // channel, y = (x - mean) * rsqrt(var + eps) * gamma + beta with the biased variance over the scene's sites.  Key order keeps a
 // scene's rows contiguous: scene s is the rows seg[s] .. seg[s+1] (seg on the device; nothing here is read back by the host).
 //
-// The structure is sp_bn.hip's with the partials cut at scene boundaries:
+// The structure is sp_bn.hip's with the partials cut at scene boundaries; the thread layout, the partials of a row range, Chan's
+// merge and the sum of all partials are the functions of table_moments.h that sp_bn.hip calls:
 //   forward : stats (a workgroup per chunk of one scene: count, mean, M2 about ITS mean, two sweeps over rows that stay in cache)
 //             -> apply (every workgroup merges the partials of ITS scene with Chan's formula in index order — deterministic — and
 //             writes y; the first workgroup of a scene stores mean / invstd)
@@ -14,11 +15,9 @@
 // host knows without the scene sizes; workgroup b finds its scene by walking seg (nseg is a batch size: tens).  The stats chunks
 // are large (about 64 per table: a workgroup of the second launch re-reads its scene's partials from L2, and 64 x C x 3 floats is
 // what keeps that below the rows it streams), the apply chunks small (HBM streams over the whole chip).
-#include "bn_common.h"
+#include "table_moments.h"
 
 namespace vdetr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int inorm_round16(int r) { return (r + 15) / 16 * 16; }
 static inline int inorm_stat_rows(int N) { const int r = (N + 63) / 64; return inorm_round16(r < 16 ? 16 : r); }
@@ -76,48 +75,7 @@ __global__ __launch_bounds__(256) void sp_in_stats_kernel(SpInParams P) {
   __shared__ f32x4 red[256];
   int s, r0, r1;
   if (!in_locate(P, P.rows_s, blockIdx.x, s, r0, r1)) return;  // (uniform)
-  const int C4 = P.C >> 2, tid = threadIdx.x, c4 = tid % C4, rs = tid / C4, rpi = 256 / C4;
-  const bool act = rs < rpi;
-  f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-  if (act)
-    for (int r = r0 + rs; r < r1; r += rpi) sum += reinterpret_cast<const f32x4*>(P.x)[(size_t)r * C4 + c4];
-  red[tid] = sum;
-  __syncthreads();
-  f32x4 tot = {0.f, 0.f, 0.f, 0.f};
-  if (act)
-    for (int j = 0; j < rpi; ++j) tot += red[j * C4 + c4];  // fixed order
-  const float cnt = (float)(r1 - r0);
-  const f32x4 mean = tot / cnt;
-  __syncthreads();
-  f32x4 m2 = {0.f, 0.f, 0.f, 0.f};
-  if (act)
-    for (int r = r0 + rs; r < r1; r += rpi) {
-      const f32x4 d = reinterpret_cast<const f32x4*>(P.x)[(size_t)r * C4 + c4] - mean;
-      m2 += d * d;
-    }
-  red[tid] = m2;
-  __syncthreads();
-  if (rs == 0) {
-    f32x4 t2 = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < rpi; ++j) t2 += red[j * C4 + c4];
-    float* p = P.part + (size_t)blockIdx.x * 3 * P.C;
-    reinterpret_cast<f32x4*>(p)[c4] = f32x4{cnt, cnt, cnt, cnt};
-    reinterpret_cast<f32x4*>(p + P.C)[c4] = mean;
-    reinterpret_cast<f32x4*>(p + 2 * P.C)[c4] = t2;
-  }
-}
-
-struct InAgg {
-  float n;
-  f32x4 mu, m2;
-};
-__device__ __forceinline__ void in_agg_add(InAgg& a, float nb, const f32x4& mb, const f32x4& sb) {  // Chan et al.
-  if (nb <= 0.f) return;
-  const float nn = a.n + nb;
-  const f32x4 d = mb - a.mu;
-  a.mu += d * (nb / nn);
-  a.m2 += sb + d * d * (a.n * nb / nn);
-  a.n = nn;
+  rows_to_moments(row_lanes(P.C), P.x, P.C, r0, r1, P.part, red);
 }
 
 __global__ __launch_bounds__(256) void sp_in_apply_kernel(SpInParams P) {
@@ -127,26 +85,18 @@ __global__ __launch_bounds__(256) void sp_in_apply_kernel(SpInParams P) {
   if (!in_locate(P, P.rows_a, blockIdx.x, s, r0, r1)) return;  // (uniform)
   int p0, np;
   in_parts(P, s, p0, np);
-  const int C4 = P.C >> 2, tid = threadIdx.x, c4 = tid % C4, rs = tid / C4, rpi = 256 / C4;
+  const int tid = threadIdx.x;
+  const auto [C4, c4, rs, rpi] = row_lanes(P.C);
   const bool act = rs < rpi;
   // thread (c4, rs) merges the partials rs, rs + rpi, ... of the scene; thread (c4, 0) then merges the rpi aggregates in order
-  InAgg a{0.f, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  Moments a{0.f, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   if (act)
-    for (int j = rs; j < np; j += rpi) {
-      const float* p = P.part + (size_t)(p0 + j) * 3 * P.C;
-      in_agg_add(a, p[c4 * 4], reinterpret_cast<const f32x4*>(p + P.C)[c4], reinterpret_cast<const f32x4*>(p + 2 * P.C)[c4]);
-    }
-  float* o = agg[tid];
-  o[0] = a.n;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { o[1 + e] = a.mu[e]; o[5 + e] = a.m2[e]; }
+    for (int j = rs; j < np; j += rpi) moments_add_partial(a, P.part, p0 + j, P.C, c4);
+  moments_store_lds(agg[tid], a);
   __syncthreads();
   if (rs == 0) {
     const int lim = min(rpi, np);
-    for (int j = 1; j < lim; ++j) {
-      const float* q = agg[j * C4 + c4];
-      in_agg_add(a, q[0], f32x4{q[1], q[2], q[3], q[4]}, f32x4{q[5], q[6], q[7], q[8]});
-    }
+    for (int j = 1; j < lim; ++j) moments_add_lds(a, agg[j * C4 + c4]);
     const f32x4 var = a.m2 / a.n;
     f32x4 invstd;
 #pragma unroll
@@ -174,29 +124,8 @@ __global__ __launch_bounds__(256) void sp_in_bwd_stats_kernel(SpInParams P, SpIn
   __shared__ f32x4 red[2][256];
   int s, r0, r1;
   if (!in_locate(P, P.rows_s, blockIdx.x, s, r0, r1)) return;  // (uniform)
-  const int C4 = P.C >> 2, tid = threadIdx.x, c4 = tid % C4, rs = tid / C4, rpi = 256 / C4;
-  f32x4 sg = {0.f, 0.f, 0.f, 0.f}, sgx = {0.f, 0.f, 0.f, 0.f};
-  if (rs < rpi) {
-    const f32x4 mean = reinterpret_cast<const f32x4*>(P.save_mean + (size_t)s * P.C)[c4];
-    const f32x4 invstd = reinterpret_cast<const f32x4*>(P.save_invstd + (size_t)s * P.C)[c4];
-    for (int r = r0 + rs; r < r1; r += rpi) {
-      const size_t i = (size_t)r * C4 + c4;
-      const f32x4 g = reinterpret_cast<const f32x4*>(G.dy)[i];
-      const f32x4 xh = (reinterpret_cast<const f32x4*>(P.x)[i] - mean) * invstd;
-      sg += g;
-      sgx += g * xh;
-    }
-  }
-  red[0][tid] = sg;
-  red[1][tid] = sgx;
-  __syncthreads();
-  if (rs == 0) {
-    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < rpi; ++j) { a += red[0][j * C4 + c4]; b += red[1][j * C4 + c4]; }
-    float* p = P.part + (size_t)blockIdx.x * 2 * P.C;
-    reinterpret_cast<f32x4*>(p)[c4] = a;
-    reinterpret_cast<f32x4*>(p + P.C)[c4] = b;
-  }
+  const auto grad = [&](size_t i) { return reinterpret_cast<const f32x4*>(G.dy)[i]; };
+  rows_to_grad_sums(row_lanes(P.C), P.x, P.C, r0, r1, P.save_mean + (size_t)s * P.C, P.save_invstd + (size_t)s * P.C, grad, P.part, red);
 }
 
 __global__ __launch_bounds__(256) void sp_in_bwd_apply_kernel(SpInParams P, SpInGrads G) {
@@ -205,7 +134,8 @@ __global__ __launch_bounds__(256) void sp_in_bwd_apply_kernel(SpInParams P, SpIn
   if (!in_locate(P, P.rows_a, blockIdx.x, s, r0, r1)) return;  // (uniform)
   int p0, np;
   in_parts(P, s, p0, np);
-  const int C4 = P.C >> 2, tid = threadIdx.x, c4 = tid % C4, rs = tid / C4, rpi = 256 / C4;
+  const int tid = threadIdx.x;
+  const auto [C4, c4, rs, rpi] = row_lanes(P.C);
   const bool act = rs < rpi;
   f32x4 sg = {0.f, 0.f, 0.f, 0.f}, sgx = {0.f, 0.f, 0.f, 0.f};
   if (act)
@@ -239,28 +169,11 @@ __global__ __launch_bounds__(256) void sp_in_bwd_params_kernel(SpInParams P, SpI
   __shared__ f32x4 red[2][4];
   int p0, np;
   in_parts(P, P.nseg, p0, np);  // p0 = the number of partials of all scenes
-  const int c4 = blockIdx.x, tid = threadIdx.x;
-  f32x4 sg = {0.f, 0.f, 0.f, 0.f}, sgx = {0.f, 0.f, 0.f, 0.f};
-  for (int b = tid; b < p0; b += 256) {
-    const float* p = P.part + (size_t)b * 2 * P.C;
-    sg += reinterpret_cast<const f32x4*>(p)[c4];
-    sgx += reinterpret_cast<const f32x4*>(p + P.C)[c4];
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float a = __shfl_down(sg[e], off), b = __shfl_down(sgx[e], off);
-      if ((tid & 63) < off) { sg[e] += a; sgx[e] += b; }
-    }
-  }
-  if ((tid & 63) == 0) { red[0][tid >> 6] = sg; red[1][tid >> 6] = sgx; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w2 = 1; w2 < 4; ++w2) { sg += red[0][w2]; sgx += red[1][w2]; }
+  const int c4 = blockIdx.x;
+  partials_sum2(P.part, p0, P.C, c4, red, [&](const f32x4& sg, const f32x4& sgx) {
     if (G.dgamma) reinterpret_cast<f32x4*>(G.dgamma)[c4] = sgx;
     if (G.dbeta) reinterpret_cast<f32x4*>(G.dbeta)[c4] = sg;
-  }
+  });
 }
 
 static int in_fill(const vdetr_sp_inorm_desc* d, SpInParams* P, const char* op) {
