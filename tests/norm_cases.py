@@ -42,7 +42,7 @@ F32 = torch.float32
 
 # ---- dropout: the kernels' documented scale ----------------------------------------------------------------------------------
 def drop_threshold(p):
-    """t = round(p * 65536) clamped to [1, 65535] (ln_rng / bn_rng; p travels as a float32); 0 without dropout"""
+    """t = round(p * 65536) clamped to [1, 65535] (drop_stream.h: drop_rate; p travels as a float32); 0 without dropout"""
     if p <= 0.0:
         return 0
     t = int(float(np.float32(p)) * 65536.0 + 0.5)

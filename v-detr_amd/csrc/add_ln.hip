@@ -7,7 +7,7 @@
 // maps of the same normalised tensor).  In ATen this is dropout + add + 2 LayerNorm launches forward and ~6 backward per
 // block; the step pays ~4.5 us per launch whatever its size, and these tensors are 1 MB.
 // One wave per row (C <= 1024 channels, 4 per lane and pass); statistics through DPP all-reduces; the dropout mask is
-// the counter-based hash of attn_common.h keyed by (row, channel), so backward regenerates it.
+// the counter-based stream of drop_stream.h keyed by (row, channel / 4), so backward regenerates it and rowblock.hip draws it too.
 // Backward: per-workgroup partial dgamma / dbeta in registers -> LDS -> global partials, summed in a fixed order by a
 // second, tiny launch (no atomics, no pre-zeroed buffers: run-to-run deterministic).
 #include "attn_common.h"
@@ -20,48 +20,17 @@ constexpr int kLnThreadsBwd = 256;              // backward: 4 waves x 4 rows, a
 constexpr int kLnRowsPerWgBwd = 16;
 constexpr int kLnMaxC = 1024;
 
-struct LnRng {
-  unsigned seed_lo, seed_hi, off_lo, off_hi, thresh;
-  float scale;
-};
-__device__ __forceinline__ LnRng ln_rng(const vdetr_addln_desc& d) {
-  LnRng r;
-  unsigned long long s = d.seed, o = d.offset;
-  if (d.rng_state) { s ^= d.rng_state[0]; o += d.rng_state[1]; }
-  r.seed_lo = (unsigned)s; r.seed_hi = (unsigned)(s >> 32); r.off_lo = (unsigned)o; r.off_hi = (unsigned)(o >> 32);
-  r.thresh = 0; r.scale = 1.f;
-  if (d.dropout_p > 0.f && d.r) {
-    int t = (int)((double)d.dropout_p * 65536.0 + 0.5);
-    t = t < 1 ? 1 : (t > 65535 ? 65535 : t);
-    r.thresh = (unsigned)t;
-    r.scale = 65536.f / (float)(65536 - t);
-  }
-  return r;
-}
-// keep flags of channels 4*j .. 4*j+3 of `row` (one hash per 4 channels: 16-bit lanes of two chained mixes)
-__device__ __forceinline__ void ln_keep4(const LnRng& g, unsigned rowkey, int j, bool (&keep)[4]) {
-  if (!g.thresh) { keep[0] = keep[1] = keep[2] = keep[3] = true; return; }
-  const unsigned x = fmix32(rowkey ^ ((unsigned)j * 0x165667B1u));
-  const unsigned y = fmix32(x + 0x9E3779B9u);
-  keep[0] = (x & 0xFFFFu) >= g.thresh; keep[1] = (x >> 16) >= g.thresh;
-  keep[2] = (y & 0xFFFFu) >= g.thresh; keep[3] = (y >> 16) >= g.thresh;
-}
-__device__ __forceinline__ unsigned ln_rowkey(const LnRng& g, int row) {
-  const unsigned x = fmix32(((unsigned)row * 0x9E3779B1u + g.off_lo) ^ g.seed_lo);
-  return fmix32(x ^ (0x27D4EB2Fu + g.off_hi) ^ g.seed_hi);
-}
-
 template <int NPASS>  // 256 channels (64 lanes x 4) per pass
 __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(vdetr_addln_desc d) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   constexpr int C = NPASS * 256, npass = NPASS;
-  const LnRng g = ln_rng(d);
+  const DropStream g = drop_stream(d.r ? d.dropout_p : 0.f, d.seed, d.offset, d.rng_state);  // no residual: nothing to drop
   const float invC = 1.f / (float)C;
   for (int i = wv; i < kLnRowsPerWg; i += 4) {
     const int row = blockIdx.x * kLnRowsPerWg + i;
     if (row >= d.rows) return;
     const size_t base = (size_t)row * C;
-    const unsigned rowkey = ln_rowkey(g, row);
+    const unsigned rowkey = drop_prefix(g, row, 1);
     f32x4 y[NPASS];
     float s = 0.f;
 #pragma unroll
@@ -71,7 +40,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_kernel(vdetr_addln_desc
       if (d.r) {
         const f32x4 rr = reinterpret_cast<const f32x4*>(d.r + base)[j];
         bool keep[4];
-        ln_keep4(g, rowkey, j, keep);
+        drop_keep4(g, rowkey, j, keep);  // channels 4 j .. 4 j + 3
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] += keep[e] ? rr[e] * g.scale : 0.f;
         reinterpret_cast<f32x4*>(d.y + base)[j] = v;
@@ -114,7 +83,7 @@ __global__ __launch_bounds__(kLnThreadsBwd) void add_ln_bwd_kernel(vdetr_addln_d
   __shared__ float red[kWaves][NPASS * 256];  // per-wave partial of one of the four parameter gradients at a time
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   constexpr int C = NPASS * 256;
-  const LnRng rg = ln_rng(d);
+  const DropStream rg = drop_stream(d.r ? d.dropout_p : 0.f, d.seed, d.offset, d.rng_state);
   const float invC = 1.f / (float)C;
   const float* ysrc = d.r ? d.y : d.x;  // the tensor that was normalised
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -163,7 +132,7 @@ __global__ __launch_bounds__(kLnThreadsBwd) void add_ln_bwd_kernel(vdetr_addln_d
     const float m1 = wave_allsum_f32(s1) * invC, m2 = wave_allsum_f32(s2) * invC;
     if (!live) continue;
     const size_t base = (size_t)row * C;
-    const unsigned rowkey = ln_rowkey(rg, row);
+    const unsigned rowkey = drop_prefix(rg, row, 1);
 #pragma unroll
     for (int p = 0; p < NPASS; ++p) {
       const int j = p * 64 + lane;
@@ -173,7 +142,7 @@ __global__ __launch_bounds__(kLnThreadsBwd) void add_ln_bwd_kernel(vdetr_addln_d
       reinterpret_cast<f32x4*>(g.d_x + base)[j] = t;
       if (g.d_r) {
         bool keep[4];
-        ln_keep4(rg, rowkey, j, keep);
+        drop_keep4(rg, rowkey, j, keep);
 #pragma unroll
         for (int e = 0; e < 4; ++e) t[e] = keep[e] ? t[e] * rg.scale : 0.f;
         reinterpret_cast<f32x4*>(g.d_r + base)[j] = t;

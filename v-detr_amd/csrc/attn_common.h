@@ -1,6 +1,7 @@
 // attn_common.h — device helpers shared by the attention forward / backward kernels.
 #pragma once
 #include "common.h"
+#include "drop_stream.h"
 #include "wave.h"
 
 namespace vdetr {
@@ -65,40 +66,31 @@ struct AttnParams {
   int ds_given;        // table-gradient kernels: `dprob` already holds dS (attn_bwd_kv.hip wrote it); nothing else is read or stored
 };
 
-// ---- dropout random numbers: counter-based (stateless), so forward and backward regenerate the same keep-mask
-// from (seed, offset, b, head group, q, key).  A chain of murmur3 finalisers (fmix32: a bijection of 32 bits with
-// full avalanche) keyed by the counter words; the (seed, offset, b, q) prefix is lane-invariant in the kernels and
-// is hoisted out of the key loop, leaving two fmix32 (~16 VALU ops) per (query, key) pair for its 4 heads —
-// a Philox4x32-10 here cost ~100 ops, a seventh of the whole forward tile step.
-__device__ __forceinline__ unsigned fmix32(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  x ^= x >> 13;
-  x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return x;
+// ---- dropout: the stream of drop_stream.h, whose six words are fields of AttnParams.  The (seed, offset, b, head group, q) prefix
+// is lane-invariant in the kernels and is hoisted out of the key loop, leaving two fmix32 (~16 VALU ops) per (query, key) pair for
+// its 4 heads.
+__device__ __forceinline__ DropStream attn_stream(const AttnParams& P) {
+  return DropStream{P.seed_lo, P.seed_hi, P.off_lo, P.off_hi, P.drop_thresh, P.drop_scale};
 }
 // kernels call this first: fold the device-resident {seed, offset} pair into the by-value one
 __device__ __forceinline__ void attn_load_rng(AttnParams& P) {
   if (P.rng) {
-    // device state is COMBINED with the by-value pair: seed ^= state.seed, offset += state.offset, so that
-    // many attention modules can share one per-step device state and still draw independent masks
-    const unsigned long long s = P.rng[0] ^ (((unsigned long long)P.seed_hi << 32) | P.seed_lo);
-    const unsigned long long o = P.rng[1] + (((unsigned long long)P.off_hi << 32) | P.off_lo);
-    P.seed_lo = (unsigned)s; P.seed_hi = (unsigned)(s >> 32);
-    P.off_lo = (unsigned)o; P.off_hi = (unsigned)(o >> 32);
+    const DropStream g = drop_stream(0.f, ((unsigned long long)P.seed_hi << 32) | P.seed_lo, ((unsigned long long)P.off_hi << 32) | P.off_lo, P.rng);
+    P.seed_lo = g.seed_lo; P.seed_hi = g.seed_hi;
+    P.off_lo = g.off_lo; P.off_hi = g.off_hi;
   }
+}
+// the counter's prefix of query q for heads 4*hgroup .. 4*hgroup+3 of scene b
+__device__ __forceinline__ unsigned attn_prefix(const AttnParams& P, int b, int q, int hgroup) {
+  return drop_prefix(attn_stream(P), (unsigned)q, (unsigned)b * 64u + (unsigned)hgroup);
 }
 // Four 16-bit uniform values of attention element (b, q, key) for heads 4*hgroup .. 4*hgroup+3.
 __device__ __forceinline__ uint4 attn_rand4(const AttnParams& P, int b, int q, int key, int hgroup) {
-  unsigned x = fmix32(((unsigned)q * 0x9E3779B1u + P.off_lo) ^ P.seed_lo);
-  x = fmix32(x ^ (((unsigned)b * 64u + (unsigned)hgroup) * 0x27D4EB2Fu + P.off_hi) ^ P.seed_hi);
-  x = fmix32(x ^ ((unsigned)key * 0x165667B1u));
-  const unsigned y = fmix32(x + 0x9E3779B9u);
-  return make_uint4(x & 0xFFFFu, x >> 16, y & 0xFFFFu, y >> 16);
+  const unsigned x = drop_word(attn_prefix(P, b, q, hgroup), (unsigned)key), y = drop_next(x);
+  return make_uint4(drop_lo(x), drop_hi(x), drop_lo(y), drop_hi(y));
 }
 __device__ __forceinline__ unsigned pick4(const uint4& r, int i) {
-  return i == 0 ? r.x : (i == 1 ? r.y : (i == 2 ? r.z : r.w));
+  return drop_pick4(r.x, r.y, r.z, r.w, i);
 }
 
 // ---- element-wise softmax backward: P~ and dS for one head of one (query, key) pair (attn_bwd*.hip) ------------------

@@ -520,14 +520,8 @@ int attn_fill_params(const vdetr_attn_desc* d, AttnParams* P, const char* op) {
     P->rpe_nearest = d->rpe_interp == VDETR_RPE_NEAREST ? 1 : 0;
   }
   P->mask = d->mask; P->mask_kind = d->mask ? d->mask_kind : VDETR_MASK_NONE;
-  if (d->dropout_p > 0.f) {
-    int t = (int)((double)d->dropout_p * 65536.0 + 0.5);
-    t = t < 1 ? 1 : (t > 65535 ? 65535 : t);
-    P->drop_thresh = (unsigned)t;
-    P->drop_scale = 65536.f / (float)(65536 - t);
-  } else {
-    P->drop_thresh = 0; P->drop_scale = 1.f;
-  }
+  const DropRate rate = drop_rate(d->dropout_p);
+  P->drop_thresh = rate.thresh; P->drop_scale = rate.scale;
   P->seed_lo = (unsigned)d->seed; P->seed_hi = (unsigned)(d->seed >> 32);
   P->off_lo = (unsigned)d->offset; P->off_hi = (unsigned)(d->offset >> 32);
   P->rng = reinterpret_cast<const unsigned long long*>(d->rng_state);

@@ -96,13 +96,10 @@ __global__ __launch_bounds__(kSfWaves * kWave) __attribute__((amdgpu_waves_per_e
     }
   }
   // accumulator register r of lane (g, c): query q0 + 4 g + r, key (tile) + c
-  unsigned xq[4];  // the dropout counter's per-row prefix (attn_common.h: attn_rand4)
+  unsigned xq[4];  // the dropout counter's per-row prefix (attn_rand4's, hoisted)
   if (DROP) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      unsigned x = fmix32(((unsigned)(q0 + 4 * g + r) * 0x9E3779B1u + P.off_lo) ^ P.seed_lo);
-      xq[r] = fmix32(x ^ (((unsigned)b * 64u + (unsigned)(head >> 2)) * 0x27D4EB2Fu + P.off_hi) ^ P.seed_hi);
-    }
+    for (int r = 0; r < 4; ++r) xq[r] = attn_prefix(P, b, q0 + 4 * g + r, head >> 2);
   }
   const bool second = (head & 2) != 0;  // heads 2 / 3 of a group read the counter's second word
   const int shift = (head & 1) * 16;
@@ -174,13 +171,12 @@ __global__ __launch_bounds__(kSfWaves * kWave) __attribute__((amdgpu_waves_per_e
       for (int t = 0; t < 4; ++t) o[t][r] *= alpha[r];
     }
     if (DROP) {
-      const unsigned ka = (unsigned)key * 0x165667B1u, kb2 = (unsigned)(key + 64) * 0x165667B1u;
       unsigned xa[4], xb[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { xa[r] = fmix32(xq[r] ^ ka); xb[r] = fmix32(xq[r] ^ kb2); }
+      for (int r = 0; r < 4; ++r) { xa[r] = drop_word(xq[r], (unsigned)key); xb[r] = drop_word(xq[r], (unsigned)(key + 64)); }
       if (second) {  // (wave-uniform)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { xa[r] = fmix32(xa[r] + 0x9E3779B9u); xb[r] = fmix32(xb[r] + 0x9E3779B9u); }
+        for (int r = 0; r < 4; ++r) { xa[r] = drop_next(xa[r]); xb[r] = drop_next(xb[r]); }
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {

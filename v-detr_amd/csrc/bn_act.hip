@@ -60,14 +60,14 @@ __global__ __launch_bounds__(kBnThreads) void bn_act_fwd_kernel(vdetr_bnact_desc
   }
   const float ga = d.gamma ? d.gamma[c] : 1.f, be = d.beta ? d.beta[c] : 0.f;
   const float a = ga * invstd, sh = be - mean * a;
-  const BnRng rg = bn_rng(d);
-  const unsigned ck = bn_chankey(rg, c);
+  const DropStream rg = bn_rng(d);
+  const unsigned ck = drop_prefix(rg, c, 1);
   float* yc = d.y + (size_t)c * N;
   for (int b = 0; b < d.B; ++b)
     for (int i = lane; i < N; i += 64) {
       float v = xc[b * bstride + i] * a + sh;
       if (d.relu) v = fmaxf(v, 0.f);
-      if (rg.thresh) v = bn_keep(rg, ck, b * N + i) ? v * rg.scale : 0.f;
+      if (rg.thresh) v = drop_keep_pair(rg, ck, b * N + i) ? v * rg.scale : 0.f;
       yc[b * bstride + i] = v;
     }
 }
@@ -103,12 +103,12 @@ __device__ __forceinline__ void bn_act_bwd_body(const vdetr_bnact_desc& d, const
   const float* gc = g.dy + (size_t)c * N;
   const float mean = d.save_mean[c], invstd = d.save_invstd[c];
   const float ga = d.gamma ? d.gamma[c] : 1.f, be = d.beta ? d.beta[c] : 0.f;
-  const BnRng rg = bn_rng(d);
-  const unsigned ck = bn_chankey(rg, c);
+  const DropStream rg = bn_rng(d);
+  const unsigned ck = drop_prefix(rg, c, 1);
   const float a = ga * invstd, sh = be - mean * a;  // the forward's expression: identical relu decisions
   auto grad_at = [&](int b, int i, float xh) {
     float v = gc[b * bstride + i];
-    if (rg.thresh) v = bn_keep(rg, ck, b * N + i) ? v * rg.scale : 0.f;
+    if (rg.thresh) v = drop_keep_pair(rg, ck, b * N + i) ? v * rg.scale : 0.f;
     if (d.relu && !(xc[b * bstride + i] * a + sh > 0.f)) v = 0.f;
     return v;
   };
@@ -180,8 +180,8 @@ __global__ __launch_bounds__(kBnThreads) void bn_act_fwd_reg_kernel(vdetr_bnact_
     }
   }
   const float a = ga * invstd, sh = be - mean * a;
-  const BnRng rg = bn_rng(d);
-  const unsigned ck = bn_chankey(rg, c);
+  const DropStream rg = bn_rng(d);
+  const unsigned ck = drop_prefix(rg, c, 1);
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
     f32x4 v;
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_act_fwd_reg_kernel(vdetr_bnact_
     for (int e = 0; e < 4; ++e) {
       float t = xr[j][e] * a + sh;
       if (d.relu) t = fmaxf(t, 0.f);
-      if (rg.thresh) t = bn_keep(rg, ck, (j * 64 + lane) * 4 + e) ? t * rg.scale : 0.f;
+      if (rg.thresh) t = drop_keep_pair(rg, ck, (j * 64 + lane) * 4 + e) ? t * rg.scale : 0.f;
       v[e] = t;
     }
     *const_cast<f32x4*>(at(d.y, j * 64 + lane)) = v;
@@ -212,8 +212,8 @@ __device__ __forceinline__ void bn_act_bwd_reg_body(const vdetr_bnact_desc& d, c
   for (int j = 0; j < NCH; ++j) { xr[j] = *at(d.x, j * 64 + lane); gr[j] = *at(g.dy, j * 64 + lane); }
   const float mean = d.save_mean[c], invstd = d.save_invstd[c];
   const float ga = d.gamma ? d.gamma[c] : 1.f, be = d.beta ? d.beta[c] : 0.f;
-  const BnRng rg = bn_rng(d);
-  const unsigned ck = bn_chankey(rg, c);
+  const DropStream rg = bn_rng(d);
+  const unsigned ck = drop_prefix(rg, c, 1);
   const float a = ga * invstd, sh = be - mean * a;
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -221,7 +221,7 @@ __device__ __forceinline__ void bn_act_bwd_reg_body(const vdetr_bnact_desc& d, c
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float v = gr[j][e];
-      if (rg.thresh) v = bn_keep(rg, ck, (j * 64 + lane) * 4 + e) ? v * rg.scale : 0.f;
+      if (rg.thresh) v = drop_keep_pair(rg, ck, (j * 64 + lane) * 4 + e) ? v * rg.scale : 0.f;
       if (d.relu && !(xr[j][e] * a + sh > 0.f)) v = 0.f;
       const float xh = (xr[j][e] - mean) * invstd;
       gr[j][e] = v;
@@ -270,16 +270,15 @@ __global__ __launch_bounds__(kBnThreads) void bn_act_bwd_reg_batch_kernel(BnBwdB
 // (y > 0 <=> the element passed the relu AND was kept): dx = y > 0 ? dy * scale : 0.
 __global__ __launch_bounds__(256) void relu_dropout_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long n4,
                                                               vdetr_bnact_desc d) {
-  const BnRng rg = bn_rng(d);
+  const DropStream rg = bn_rng(d);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
     f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
     unsigned r0 = 0xFFFFFFFFu, r1 = 0xFFFFFFFFu;
     if (rg.thresh) {
-      r0 = fmix32(((unsigned)i * 0x9E3779B1u + rg.off_lo) ^ rg.seed_lo ^ ((unsigned)(i >> 32) * 0x27D4EB2Fu));
-      r0 = fmix32(r0 ^ rg.seed_hi ^ rg.off_hi);
-      r1 = fmix32(r0 + 0x9E3779B9u);
+      r0 = drop_flat(rg, i);
+      r1 = drop_next(r0);
     }
-    const unsigned k[4] = {r0 & 0xFFFFu, r0 >> 16, r1 & 0xFFFFu, r1 >> 16};
+    const unsigned k[4] = {drop_lo(r0), drop_hi(r0), drop_lo(r1), drop_hi(r1)};
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = (v[e] > 0.f && k[e] >= rg.thresh) ? v[e] * rg.scale : 0.f;
     reinterpret_cast<f32x4*>(y)[i] = v;
@@ -383,10 +382,9 @@ extern "C" int vdetr_relu_dropout_bwd_f32(const float* y, const float* dy, float
   VDETR_REQUIRE((((uintptr_t)y | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0, "relu_dropout_bwd: tensors must be 16-B aligned");
   vdetr_bnact_desc d = {};
   d.dropout_p = dropout_p;
-  const BnRng rg = [&] { BnRng r; r.thresh = 0; r.scale = 1.f; if (dropout_p > 0.f) { int t = (int)((double)dropout_p * 65536.0 + 0.5); t = t < 1 ? 1 : (t > 65535 ? 65535 : t); r.scale = 65536.f / (float)(65536 - t); } return r; }();
   const long n4 = n / 4;
   const int grid = (int)(n4 / 256 + 1 < 2048 ? n4 / 256 + 1 : 2048);
-  hipLaunchKernelGGL(relu_dropout_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, dy, dx, n4, rg.scale);
+  hipLaunchKernelGGL(relu_dropout_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, dy, dx, n4, drop_rate(dropout_p).scale);
   return check_launch("relu_dropout_bwd");
 }
 

@@ -166,7 +166,7 @@ struct HdBn {
   float *running_mean, *running_var, *save_mean, *save_invstd;
   int64_t* counter;
 };
-__device__ __forceinline__ void hd_bn_prepare(const HdBn& S, int P, int GC, int g, int tid, float eps, float momentum, const BnRng& rg,
+__device__ __forceinline__ void hd_bn_prepare(const HdBn& S, int P, int GC, int g, int tid, float eps, float momentum, const DropStream& rg,
                                               bool owner, float* ab, unsigned* ck, int merged) {
   const int ch = g * kHdC + tid;
   float mean, m2;
@@ -182,7 +182,7 @@ __device__ __forceinline__ void hd_bn_prepare(const HdBn& S, int P, int GC, int 
   const float a = S.gamma[ch] * invstd, sh = S.beta[ch] - mean * a;
   ab[2 * tid] = a;
   ab[2 * tid + 1] = sh;
-  ck[tid] = bn_chankey(rg, ch);
+  ck[tid] = drop_prefix(rg, ch, 1);
   if (owner) {
     S.save_mean[ch] = mean;
     S.save_invstd[ch] = invstd;
@@ -194,16 +194,16 @@ __device__ __forceinline__ void hd_bn_prepare(const HdBn& S, int P, int GC, int 
   }
 }
 // dropout(relu(v * a + sh)) for four consecutive elements e0 .. e0 + 3 of a channel (e0 even)
-__device__ __forceinline__ f32x4 hd_act4(const f32x4& v, float a, float sh, const BnRng& rg, unsigned key, int e0) {
+__device__ __forceinline__ f32x4 hd_act4(const f32x4& v, float a, float sh, const DropStream& rg, unsigned key, int e0) {
   f32x4 h;
 #pragma unroll
   for (int e = 0; e < 4; ++e) h[e] = fmaxf(v[e] * a + sh, 0.f);
   if (rg.thresh) {
-    const unsigned x0 = bn_draw2(key, e0 >> 1), x1 = bn_draw2(key, (e0 >> 1) + 1);
-    h[0] = (x0 & 0xFFFFu) >= rg.thresh ? h[0] * rg.scale : 0.f;
-    h[1] = (x0 >> 16) >= rg.thresh ? h[1] * rg.scale : 0.f;
-    h[2] = (x1 & 0xFFFFu) >= rg.thresh ? h[2] * rg.scale : 0.f;
-    h[3] = (x1 >> 16) >= rg.thresh ? h[3] * rg.scale : 0.f;
+    const unsigned x0 = drop_word(key, e0 >> 1), x1 = drop_word(key, (e0 >> 1) + 1);  // the pair words of e0, e0 + 1 and e0 + 2, e0 + 3
+    h[0] = drop_lo(x0) >= rg.thresh ? h[0] * rg.scale : 0.f;
+    h[1] = drop_hi(x0) >= rg.thresh ? h[1] * rg.scale : 0.f;
+    h[2] = drop_lo(x1) >= rg.thresh ? h[2] * rg.scale : 0.f;
+    h[3] = drop_hi(x1) >= rg.thresh ? h[3] * rg.scale : 0.f;
   }
   return h;
 }
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(kHdThreads) void heads_l2_kernel(HdArgs A, int merg
   f32x4 v[8];
 #pragma unroll
   for (int it = 0; it < 8; ++it) v[it] = hd_ld4(A.pre1 + base + (size_t)(64 * w + 8 * it + kk) * A.N);
-  const BnRng rg = bn_rng_of(A.p1, A.salt1, 0, A.rng_state);
+  const DropStream rg = drop_stream(A.p1, A.salt1, 0, A.rng_state);
   const HdBn S = {hd_part(A, 0), A.gamma1, A.beta1, A.running_mean1, A.running_var1, A.save_mean1, A.save_invstd1, A.counters1[g]};
   hd_bn_prepare(S, A.B * tps, GC, g, tid, A.eps, A.momentum, rg, blockIdx.x == 0, ab, ck, merged);
   __syncthreads();
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(kHdThreads) void heads_l3_kernel(HdArgs A, int merg
   f32x4 v[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it) v[it] = hd_ld4(A.pre2 + base + (size_t)(64 * w + 16 * it + kk) * A.N);
-  const BnRng rg = bn_rng_of(A.p2, A.salt2, 0, A.rng_state);
+  const DropStream rg = drop_stream(A.p2, A.salt2, 0, A.rng_state);
   const HdBn S = {hd_part(A, 1), A.gamma2, A.beta2, A.running_mean2, A.running_var2, A.save_mean2, A.save_invstd2, A.counters2[g]};
   hd_bn_prepare(S, A.B * (A.N / kHdTok), GC, g, tid, A.eps, A.momentum, rg, blockIdx.x == 0, ab, ck, merged);
   __syncthreads();

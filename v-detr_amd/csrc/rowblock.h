@@ -11,42 +11,14 @@ constexpr int kRbThreads = 256;
 constexpr int kRbDepth = 6;  // weight tiles in flight per wave (steps of 16 matrix instructions): one wave per SIMD, registers to spare
 constexpr int kRbStride = kRbC + 4;  // floats per LDS row: 16 rows x 1040 B land on 16 different 16-byte slots
 
-struct RbDrop {  // a dropout stream (add_ln.hip: LnRng / bn_act.hip: BnRng): keep iff 16-bit draw >= thresh
-  unsigned seed_lo, seed_hi, off_lo, off_hi, thresh;
-  float scale;
-};
-__device__ __forceinline__ RbDrop rb_drop(float p, unsigned long long seed, unsigned long long offset, const uint64_t* rng) {
-  RbDrop r;
-  unsigned long long s = seed, o = offset;
-  if (rng) { s ^= rng[0]; o += rng[1]; }
-  r.seed_lo = (unsigned)s; r.seed_hi = (unsigned)(s >> 32); r.off_lo = (unsigned)o; r.off_hi = (unsigned)(o >> 32);
-  r.thresh = 0; r.scale = 1.f;
-  if (p > 0.f) {
-    int t = (int)((double)p * 65536.0 + 0.5);
-    t = t < 1 ? 1 : (t > 65535 ? 65535 : t);
-    r.thresh = (unsigned)t;
-    r.scale = 65536.f / (float)(65536 - t);
-  }
-  return r;
+// The dropout streams (drop_stream.h) of the launches a row-block kernel replaces, from scratch per call: the residual blocks'
+// mask of add_ln.hip, channels 4 j .. 4 j + 3 of `row` ...
+__device__ __forceinline__ void rb_keep4_ln(const DropStream& g, int row, int j, bool (&keep)[4]) {
+  drop_keep4(g, drop_prefix(g, row, 1), j, keep);
 }
-// the residual blocks' mask (add_ln.hip: ln_rowkey / ln_keep4): channels 4 j .. 4 j + 3 of `row`
-__device__ __forceinline__ void rb_keep4_ln(const RbDrop& g, int row, int j, bool (&keep)[4]) {
-  if (!g.thresh) { keep[0] = keep[1] = keep[2] = keep[3] = true; return; }
-  unsigned k = fmix32(((unsigned)row * 0x9E3779B1u + g.off_lo) ^ g.seed_lo);
-  k = fmix32(k ^ (0x27D4EB2Fu + g.off_hi) ^ g.seed_hi);
-  const unsigned x = fmix32(k ^ ((unsigned)j * 0x165667B1u));
-  const unsigned y = fmix32(x + 0x9E3779B9u);
-  keep[0] = (x & 0xFFFFu) >= g.thresh; keep[1] = (x >> 16) >= g.thresh;
-  keep[2] = (y & 0xFFFFu) >= g.thresh; keep[3] = (y >> 16) >= g.thresh;
-}
-// the FFN activation's mask (bn_act.hip: relu_dropout_fwd_kernel): float4 number i of the flat tensor
-__device__ __forceinline__ void rb_keep4_act(const RbDrop& g, long i, bool (&keep)[4]) {
-  if (!g.thresh) { keep[0] = keep[1] = keep[2] = keep[3] = true; return; }
-  unsigned r0 = fmix32(((unsigned)i * 0x9E3779B1u + g.off_lo) ^ g.seed_lo ^ ((unsigned)(i >> 32) * 0x27D4EB2Fu));
-  r0 = fmix32(r0 ^ g.seed_hi ^ g.off_hi);
-  const unsigned r1 = fmix32(r0 + 0x9E3779B9u);
-  keep[0] = (r0 & 0xFFFFu) >= g.thresh; keep[1] = (r0 >> 16) >= g.thresh;
-  keep[2] = (r1 & 0xFFFFu) >= g.thresh; keep[3] = (r1 >> 16) >= g.thresh;
+// ... and the FFN activation's mask (bn_act.hip: relu_dropout_fwd_kernel): float4 number i of the flat tensor
+__device__ __forceinline__ void rb_keep4_act(const DropStream& g, long i, bool (&keep)[4]) {
+  drop_keep4(g, drop_flat(g, i), keep);
 }
 
 // ---- the 16 x 256 activation tile: global -> LDS (row-major, padded), LDS -> the 64 A-operand registers of a lane ----------

@@ -53,8 +53,8 @@ __global__ __launch_bounds__(kRbThreads) void rb_ffn_kernel(RbFfnArgs A, RbParts
   const int g = lane >> 4, c = lane & 15;
   const int row0 = blockIdx.x * kRbRows;
   const int col0 = 64 * w, colq = col0 + 4 * c;  // this lane's four columns
-  const RbDrop d2 = rb_drop(A.drop2.p, A.drop2.seed, 0, A.rng_state), da = rb_drop(A.drop_act.p, A.drop_act.seed, 0, A.rng_state),
-               d3 = rb_drop(A.drop3.p, A.drop3.seed, 0, A.rng_state);
+  const DropStream d2 = drop_stream(A.drop2.p, A.drop2.seed, 0, A.rng_state), da = drop_stream(A.drop_act.p, A.drop_act.seed, 0, A.rng_state),
+               d3 = drop_stream(A.drop3.p, A.drop3.seed, 0, A.rng_state);
   float a[64];
   f32x4 acc[4];
   f32x4 y[4];  // the residual stream of this lane's rows 4 g + r, columns colq ..
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(kRbThreads) void rb_proj_q_kernel(RbProjQArgs A) {
   const int g = lane >> 4, c = lane & 15;
   const int row0 = blockIdx.x * kRbRows;
   const int col0 = 64 * w, colq = col0 + 4 * c;
-  const RbDrop d1 = rb_drop(A.drop1.p, A.drop1.seed, 0, A.rng_state);
+  const DropStream d1 = drop_stream(A.drop1.p, A.drop1.seed, 0, A.rng_state);
   float a[64];
   f32x4 acc[4];
   f32x4 y[4];
@@ -361,8 +361,8 @@ __global__ __launch_bounds__(kRbThreads) void rb_ffn_bwd_kernel(vdetr_rb_ffn_des
   const int g = lane >> 4, c = lane & 15;
   const int row0 = blockIdx.x * kRbRows;
   const int col0 = 64 * w, colq = col0 + 4 * c;
-  const RbDrop d2 = rb_drop(A.drop2.p, A.drop2.seed, 0, A.rng_state), da = rb_drop(A.drop_act.p, A.drop_act.seed, 0, A.rng_state),
-               d3 = rb_drop(A.drop3.p, A.drop3.seed, 0, A.rng_state);
+  const DropStream d2 = drop_stream(A.drop2.p, A.drop2.seed, 0, A.rng_state), da = drop_stream(A.drop_act.p, A.drop_act.seed, 0, A.rng_state),
+               d3 = drop_stream(A.drop3.p, A.drop3.seed, 0, A.rng_state);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const bool two = G.d_o2 != nullptr;
   int rowc[4];
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(kRbThreads) void rb_proj_q_bwd_kernel(vdetr_rb_proj
   const int g = lane >> 4, c = lane & 15;
   const int row0 = blockIdx.x * kRbRows;
   const int col0 = 64 * w, colq = col0 + 4 * c;
-  const RbDrop d1 = rb_drop(A.drop1.p, A.drop1.seed, 0, A.rng_state);
+  const DropStream d1 = drop_stream(A.drop1.p, A.drop1.seed, 0, A.rng_state);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   int rowc[4];
   bool live[4];
