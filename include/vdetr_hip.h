@@ -1582,6 +1582,52 @@ int vdetr_sp_voxel_reduce_grad_f32(const vdetr_sp_voxel_reduce_desc* d, const fl
 int vdetr_sp_voxel_labels_i32(const int32_t* labels, const int32_t* order, const int32_t* seg, int M, int N, int ignore_label,
                               int32_t* out, vdetr_stream_t stream);
 
+/* Trilinear interpolation of a sparse tensor at float coordinates (MinkowskiInterpolation; DESIGN 6.16: this package's own
+ * definition, restated by tests/interp_restatement.py).
+ *
+ * Map, one launch.  keys [M] i64 ascending and unique (the keys of vdetr_sp_kernel_map_i32) of a tensor at integer stride
+ * s = `stride`, 1 <= s <= 32768; tfield [N, 4] f32 (batch, x, y, z) in units of the finest voxel, 16-byte aligned.  A site's
+ * feature sits AT its integer coordinate.  Per axis i = (int)floorf(x), lo = floor_div(i, s) * s (towards minus infinity),
+ * t = (x - (float)lo) / (float)s.  Corner k = 4 bx + 2 by + bz (bit 1 = the upper site lo + s):
+ *   nbr [N, 8] i32 = the row in keys of (batch, lo + b s), or -1;   w [N, 8] f32 = (fx fy) fz, f = b ? t : 1 - t, 0 where nbr = -1.
+ * A corner whose coordinate leaves -32768 .. 32767 is -1 (it never carries into the next field of the key).  A row with a
+ * non-finite coordinate, a floorf outside -32768 .. 32767 or a batch value that is not an integer in 0 .. 32767 gets eight -1;
+ * nothing is raised.  M == 0: every entry is -1 / 0 (keys may be NULL).  N == 0: no-op.  nbr and w 16-byte aligned.
+ * vdetr_sp_interp_tile() = the points per workgroup of this launch.  No atomics, no memset, no host read. */
+typedef struct vdetr_sp_interp_map_desc {
+  int32_t M, N, stride;
+  const int64_t* keys;
+  const float* tfield;
+  int32_t* nbr;
+  float* w;
+} vdetr_sp_interp_map_desc;
+int vdetr_sp_interp_tile(void);
+int vdetr_sp_interp_map_f32(const vdetr_sp_interp_map_desc* d, vdetr_stream_t stream);
+
+/* Forward, one launch: y [N, C] = sum over k = 0 .. 7 ascending, pairs with 0 <= nbr < M only, of w[n, k] * x[nbr[n, k], :];
+ * x = the feature table [M, C] f32, any C >= 1 (a float4 per lane where C % 4 == 0 and x, y are 16-byte aligned, a channel per
+ * lane otherwise).  float32, a multiply and an add per pair, from +0; a pair of weight 0 is still a pair.  M == 0 writes zeros
+ * (x may be NULL); N == 0: no-op.  order / seg are not read.
+ *
+ * Backward: sort the 8 N entries of nbr ascending with a STABLE sort (the -1 of absent pairs first) and hand the sorted values
+ * and the permutation to vdetr_sp_interp_seg_i32, one launch: seg [M + 1] i32 = the first sorted position of every site row
+ * (empty sites included; seg[M] = 8 N), order32 [8 N] = the permutation as i32.  N == 0 writes M + 1 zeros.  Then
+ * vdetr_sp_interp_bwd_f32, one launch, with x = dy [N, C] and y = dF [M, C]:
+ *   dF[m, :] = sum over p = order[seg[m] .. seg[m + 1]) of w[p] * dy[p / 8, :], in that order = ascending (n, k), from +0.
+ * A site with no pair gets an exact +0.  No atomics: two runs give the same bits.  M == 0: no-op.  nbr is not read. */
+typedef struct vdetr_sp_interp_desc {
+  int32_t M, N, C;
+  const float* x;
+  const int32_t* nbr;
+  const float* w;
+  const int32_t *order, *seg;
+  float* y;
+} vdetr_sp_interp_desc;
+int vdetr_sp_interp_fwd_f32(const vdetr_sp_interp_desc* d, vdetr_stream_t stream);
+int vdetr_sp_interp_seg_i32(const int32_t* sorted, const int64_t* order, int M, int N, int32_t* order32, int32_t* seg,
+                            vdetr_stream_t stream);
+int vdetr_sp_interp_bwd_f32(const vdetr_sp_interp_desc* d, vdetr_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Fixed coordinate embeddings — PositionEmbeddingCoordsSine (models/position_embedding.py:21-148); one launch each.
  *   xyz (b,n,3); range_min / range_max (b,3) = the scene extent for `normalize=True` (shift_scale_points,

@@ -474,6 +474,18 @@ class SpVoxelReduceDesc(ctypes.Structure):
 VDETR_VOXEL_SUM, VDETR_VOXEL_AVG, VDETR_VOXEL_MAX, VDETR_VOXEL_FIRST = 0, 1, 2, 3
 
 
+class SpInterpMapDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_interp_map_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("M", "N", "stride")] + [(n, c_void_p) for n in ("keys", "tfield", "nbr", "w")]
+
+
+class SpInterpDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_interp_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("M", "N", "C")] + [(n, c_void_p) for n in ("x", "nbr", "w", "order", "seg", "y")]
+
+
 class DetStore(ctypes.Structure):
     """Mirror of ``vdetr_det_store``."""
 
@@ -632,6 +644,11 @@ _SIGNATURES = {
     "vdetr_sp_voxel_reduce_f32": (c_int, [ctypes.POINTER(SpVoxelReduceDesc), c_void_p]),
     "vdetr_sp_voxel_reduce_grad_f32": (c_int, [ctypes.POINTER(SpVoxelReduceDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
     "vdetr_sp_voxel_labels_i32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vdetr_sp_interp_tile": (c_int, []),
+    "vdetr_sp_interp_map_f32": (c_int, [ctypes.POINTER(SpInterpMapDesc), c_void_p]),
+    "vdetr_sp_interp_fwd_f32": (c_int, [ctypes.POINTER(SpInterpDesc), c_void_p]),
+    "vdetr_sp_interp_seg_i32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vdetr_sp_interp_bwd_f32": (c_int, [ctypes.POINTER(SpInterpDesc), c_void_p]),
     "vdetr_rb_transpose_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vdetr_rb_qkv_f32": (c_int, [ctypes.POINTER(RbQkvDesc), c_void_p]),
     "vdetr_rb_proj_q_f32": (c_int, [ctypes.POINTER(RbProjQDesc), c_void_p]),

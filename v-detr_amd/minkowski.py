@@ -18,7 +18,10 @@ MinkowskiEngine is NOT under /root/reference (un-vendored): semantics follow its
     mask in order (DESIGN 6.11: this package's own statement);
   * duplicated input coordinates keep one feature row (here: the first in input order) under the default
     ``SparseTensorQuantizationMode.RANDOM_SUBSAMPLE``; UNWEIGHTED_AVERAGE / UNWEIGHTED_SUM / MAX_POOL fold the rows of a site in
-    ascending input order; sites are held in key order, which is also the row order of ``sparse_quantize``.
+    ascending input order (DESIGN 6.15); sites are held in key order, which is also the row order of ``sparse_quantize``;
+  * ``MinkowskiInterpolation`` / ``features_at_coordinates`` / ``SparseTensor.interpolate`` read a tensor of any stride at float
+    coordinates: trilinear over the 2^3 sites around a point, a site's feature AT its integer coordinate, absent sites as zero
+    without renormalisation (this package's own statement).
 The ORDER of the sites of a MinkowskiEngine tensor is an implementation detail of its hash map; here it is ascending
 (batch, x, y, z).  Parity against the MinkowskiEngine binary is unpinned; ``oracle/sparse_oracle.py`` pins the arithmetic
 against torch's dense convolutions.
@@ -523,9 +526,38 @@ class SparseTensor:
             raise ValueError("slice: the field must be the one whose sparse() built this tensor's coordinate manager")
         if self.tensor_stride != 1 or self.keys is not self.coordinate_manager.keys[1]:
             raise ValueError("slice: only a tensor on the field's own sites (tensor stride 1) can be sliced")
-        out = TensorField(S.voxel_slice(self.F.contiguous(), field._vmap), field.C, quantization_mode=field.quantization_mode)
-        out.coordinate_manager, out._vmap = field.coordinate_manager, field._vmap
-        return out
+        return field._like(S.voxel_slice(self.F.contiguous(), field._vmap))
+
+    def cat_slice(self, field):
+        """ME.SparseTensor.cat_slice: ``slice(field)`` with the field's own features behind it, F = cat((self.F[inverse], field.F),
+        1) — the site features first: that column order is this package's definition.  Preconditions and errors of ``slice``."""
+        sliced = self.slice(field)
+        return field._like(torch.cat((sliced.F, field.F), 1))
+
+    def _interp_map(self, tfield):
+        """the InterpMap of this tensor's keys at ``tfield`` [N, 4] fp32 (batch, x, y, z), cached in the coordinate manager per
+        (key set, stride, coordinate tensor and its version): it is geometry, built once by a geometry-only pass"""
+        cache = self.coordinate_manager.__dict__.setdefault("_interp_maps", {})
+        key = (self.keys.data_ptr(), self.tensor_stride, tfield.data_ptr(), tuple(tfield.shape), tfield._version)
+        if key not in cache:
+            if len(cache) >= 64:  # (query tensors made anew for every call: keep the record bounded)
+                cache.clear()
+            cache[key] = (S.interp_map(self.keys, self.tensor_stride, tfield), self.keys, tfield)  # the tensors are kept alive
+        return cache[key][0]
+
+    def features_at_coordinates(self, query_coordinates):
+        """ME.SparseTensor.features_at_coordinates: [N, C] = this tensor's features interpolated trilinearly at
+        ``query_coordinates`` [N, 4] fp32 (batch, x, y, z) in units of the finest voxel, at any tensor stride (a
+        site's feature sits at its integer coordinate; corners without a site count as zero, without renormalisation).
+        Gradients reach the features, not the coordinates."""
+        return MinkowskiInterpolation()(self, query_coordinates)
+
+    def interpolate(self, field):
+        """ME.SparseTensor.interpolate: ``features_at_coordinates`` at the float coordinates of ``field`` -> a TensorField on
+        them.  Only this tensor's keys are used: any tensor stride, the field's own coordinate manager or another."""
+        if not isinstance(field, TensorField):
+            raise ValueError(f"interpolate: a TensorField is expected, not {type(field).__name__}")
+        return field._like(self.features_at_coordinates(field.float_coordinates))
 
     def decomposed(self):
         """per batch element: (coordinates [n,3] int32, features [n,C]) — key order keeps the scenes contiguous"""
@@ -540,8 +572,10 @@ class SparseTensor:
 class TensorField:
     """ME.TensorField(features [N, C], coordinates [N, 4] = (batch, x, y, z)): features on POINTS, several of which may share a
     voxel.  ``sparse()`` quantises them into a SparseTensor (``quantization_mode``; ME's default for a field is the average) and
-    keeps the inverse map, so that ``SparseTensor.slice(field)`` brings site features back to the points.  Float coordinates are
-    floored.  ``cat_slice`` and the interpolating modes are not built."""
+    keeps the inverse map, so that ``SparseTensor.slice(field)`` / ``cat_slice(field)`` bring site features back to the points.
+    ``C`` holds float coordinates floored to int32; ``float_coordinates`` keeps them as given ([N, 4] fp32; integer coordinates
+    converted), and ``SparseTensor.interpolate(field)`` reads a tensor of any stride there trilinearly (``MinkowskiInterpolation``).
+    The SPLAT_LINEAR_INTERPOLATION and NO_QUANTIZATION modes and a gradient to the coordinates are not built."""
 
     def __init__(self, features, coordinates, quantization_mode=SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE):
         self.quantization_mode = _quantization_mode(quantization_mode)
@@ -549,10 +583,25 @@ class TensorField:
         S.L.require_gpu(coordinates, "coordinates")
         if coordinates.dim() != 2 or coordinates.shape[1] != 4 or coordinates.shape[0] != features.shape[0]:
             raise ValueError(f"TensorField: coordinates must be [{features.shape[0]}, 4] (batch, x, y, z), got {tuple(coordinates.shape)}")
+        self._given = coordinates
         if coordinates.is_floating_point():
             coordinates = torch.floor(coordinates).to(torch.int32)
         self.F, self.C = features, coordinates
-        self.coordinate_manager = self._vmap = None
+        self.coordinate_manager = self._vmap = self._float = None
+
+    @property
+    def float_coordinates(self):
+        """the coordinates as given, [N, 4] contiguous fp32 (integer coordinates interpolate at themselves); made on first use"""
+        if self._float is None:
+            self._float = self._given.detach().to(torch.float32).contiguous()
+        return self._float
+
+    def _like(self, features):
+        """a field of other features on this field's points: same coordinates (``C`` is shared), manager and voxel map"""
+        out = TensorField(features, self.C, quantization_mode=self.quantization_mode)
+        out._given, out._float = self._given, self._float
+        out.coordinate_manager, out._vmap = self.coordinate_manager, self._vmap
+        return out
 
     @property
     def inverse_mapping(self):
@@ -842,6 +891,45 @@ class MinkowskiPruning(nn.Module):
         kept, pos, keys = S.prune_map(mask.contiguous(), x.keys)
         return SparseTensor(S.take_rows(x.F.contiguous(), kept, back=pos), tensor_stride=x.tensor_stride,
                             coordinate_manager=x.coordinate_manager, keys=keys)
+
+
+class MinkowskiInterpolation(nn.Module):
+    """ME.MinkowskiInterpolation: ``forward(input, tfield)`` -> [N, C], the features of the SparseTensor ``input`` (any integer
+    tensor stride) interpolated trilinearly at ``tfield`` [N, 4] fp32 (batch, x, y, z) in units of the finest voxel.  A site's
+    feature sits at its integer coordinate; the 2^3 sites around a point weigh in by the usual products, the ones that do not
+    exist count as zero and the rest is NOT renormalised (this package's own statement).  With ``return_kernel_map``
+    / ``return_weights`` the result is the list [out, (in_map, out_map)?, weights?] of the pairs that exist in ascending (point,
+    corner) order: in_map = site rows, out_map = field rows (int32), weights fp32 — compacted with one host read; the plain
+    call reads nothing back.  Gradients reach the features only.  Under ``geometry_only`` the map is built and cached, the
+    table is uninitialised."""
+
+    def __init__(self, return_kernel_map=False, return_weights=False):
+        super().__init__()
+        self.return_kernel_map, self.return_weights = bool(return_kernel_map), bool(return_weights)
+
+    def forward(self, input, tfield):
+        if not isinstance(input, SparseTensor):
+            raise ValueError(f"MinkowskiInterpolation: a SparseTensor is expected, not {type(input).__name__}")
+        if not torch.is_tensor(tfield) or tfield.dim() != 2 or tfield.shape[1] != 4 or tfield.dtype != torch.float32:
+            raise ValueError("MinkowskiInterpolation: tfield must be a [N, 4] float32 tensor (batch, x, y, z), got "
+                             f"{tuple(tfield.shape) if torch.is_tensor(tfield) else type(tfield).__name__}"
+                             f"{' ' + str(tfield.dtype) if torch.is_tensor(tfield) else ''}")
+        if tfield.device != input.keys.device:
+            raise ValueError(f"MinkowskiInterpolation: tfield is on {tfield.device}, the tensor on {input.keys.device}")
+        imap = input._interp_map(tfield.detach().contiguous())
+        if _geometry_only():
+            out = input.F.new_empty((tfield.shape[0], input.F.shape[1]))
+        else:
+            out = S.interpolate(input.F.contiguous(), imap)
+        if not (self.return_kernel_map or self.return_weights):
+            return out
+        at = torch.nonzero(imap.nbr.view(-1) >= 0).view(-1)  # ascending n * 8 + k (the one host read: the pair count is data)
+        result = [out]
+        if self.return_kernel_map:
+            result.append((imap.nbr.view(-1)[at], (at >> 3).to(torch.int32)))
+        if self.return_weights:
+            result.append(imap.w.view(-1)[at])
+        return result
 
 
 class _Pointwise(nn.Module):

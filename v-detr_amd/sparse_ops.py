@@ -1209,6 +1209,116 @@ def voxel_labels(labels, vmap, ignore_label=-100):
     return out.to(labels.dtype)
 
 
+# ---- trilinear interpolation at float coordinates (csrc/sparse_interp.hip) -------------------------------------------
+def interp_tile():
+    """points per workgroup of the map launch (the tests place their edge cases on its multiples)"""
+    return int(L.lib().vdetr_sp_interp_tile())
+
+
+class InterpMap:
+    """The geometry of one interpolation, reusable for any feature table on the same keys: ``nbr`` [N, 8] int32 = the site row of
+    every corner (k = 4 bx + 2 by + bz, bit 1 = the upper site) or -1, ``w`` [N, 8] fp32 = its trilinear weight (0 where absent),
+    ``M`` sites, ``N`` points.  ``order`` [8 N] / ``seg`` [M + 1] int32, the pairs grouped by site in ascending (n, k) for the
+    backward, are built on first use: a stable library sort and one launch, no host read."""
+
+    def __init__(self, nbr, w, M):
+        self.nbr, self.w, self.M, self.N = nbr, w, int(M), nbr.shape[0]
+        self._fold = None
+
+    def _folded(self):
+        if self._fold is None:
+            dev = self.nbr.device
+            order32 = torch.empty(8 * self.N, dtype=torch.int32, device=dev)
+            seg = torch.empty(self.M + 1, dtype=torch.int32, device=dev)
+            # absent pairs (-1) sort first; the stable sort keeps every site's pairs in ascending (n, k)
+            rows, order = torch.sort(self.nbr.view(-1), stable=True) if self.N else (None, None)
+            L.check(L.lib().vdetr_sp_interp_seg_i32(L.ptr(rows), L.ptr(order), self.M, self.N, L.ptr(order32), L.ptr(seg), L.stream_ptr()),
+                    "sp_interp_seg")
+            self._fold = (order32, seg)
+        return self._fold
+
+    order = property(lambda self: self._folded()[0])
+    seg = property(lambda self: self._folded()[1])
+
+
+def interp_map(keys, tensor_stride, tfield):
+    """keys [M] sorted unique int64 (``pack_keys``) of a sparse tensor at integer ``tensor_stride`` s >= 1 and tfield [N, 4] fp32
+    (batch, x, y, z) in units of the finest voxel, both on the device -> ``InterpMap``.  A site's feature sits at its integer
+    coordinate; per axis lo = floor_div(floor(x), s) * s and t = (x - lo) / s, the corners are the sites (lo | lo + s) on every
+    axis.  A point outside every key (non-finite, outside the 16-bit range, a batch value that is no integer in [0, 32767]) has
+    eight absent corners; nothing is raised and nothing is read back.  One launch."""
+    # (the checks that do not need the tensors on a device come first)
+    if keys.dtype != torch.int64 or keys.dim() != 1:
+        raise RuntimeError(f"keys must be a one-dimensional int64 key tensor (it is {keys.dtype}, {tuple(keys.shape)})")
+    if not isinstance(tensor_stride, (int, np.integer)) or isinstance(tensor_stride, bool) or not 1 <= tensor_stride <= KEY_BIAS:
+        raise ValueError(f"interp_map: tensor_stride {tensor_stride!r} must be an integer in [1, {KEY_BIAS}]")
+    L.require_float(tfield, "tfield")
+    if tfield.dim() != 2 or tfield.shape[1] != 4:
+        raise RuntimeError(f"tfield must be [N, 4] (batch, x, y, z) (it is {tuple(tfield.shape)})")
+    _require_keys(keys, "keys")
+    L.require_gpu(tfield, "tfield")
+    L.require_contiguous(tfield, "tfield")
+    if tfield.device != keys.device:
+        raise RuntimeError(f"interp_map: keys on {keys.device}, tfield on {tfield.device}")
+    M, N, dev = keys.shape[0], tfield.shape[0], keys.device
+    if 8 * N >= 2 ** 31:
+        raise RuntimeError(f"interp_map: 8 x {N} pairs are more than 31 bits hold")
+    nbr = torch.empty((N, 8), dtype=torch.int32, device=dev)
+    w = torch.empty((N, 8), dtype=torch.float32, device=dev)
+    d = L.SpInterpMapDesc()
+    d.M, d.N, d.stride = M, N, int(tensor_stride)
+    d.keys, d.tfield, d.nbr, d.w = L.ptr(keys).value, L.ptr(tfield).value, L.ptr(nbr).value, L.ptr(w).value
+    L.check(L.lib().vdetr_sp_interp_map_f32(ctypes.byref(d), L.stream_ptr()), "sp_interp_map")
+    return InterpMap(nbr, w, M)
+
+
+class _InterpFn(Function):
+    """y [N, C] = sum_k w[n, k] * x[nbr[n, k]]; dx [M, C] = the same pairs folded per site in ascending (n, k) (no atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, imap):
+        ctx.imap = imap
+        M, C = x.shape
+        y = torch.empty((imap.N, C), dtype=torch.float32, device=x.device)
+        d = L.SpInterpDesc()
+        d.M, d.N, d.C = M, imap.N, C
+        d.x, d.nbr, d.w, d.y = L.ptr(x).value, L.ptr(imap.nbr).value, L.ptr(imap.w).value, L.ptr(y).value
+        L.check(L.lib().vdetr_sp_interp_fwd_f32(ctypes.byref(d), L.stream_ptr()), "sp_interp_fwd")
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        imap = ctx.imap
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        dy = dy.contiguous()
+        C = dy.shape[1]
+        dx = torch.empty((imap.M, C), dtype=torch.float32, device=dy.device)
+        d = L.SpInterpDesc()
+        d.M, d.N, d.C = imap.M, imap.N, C
+        d.x, d.w, d.order, d.seg, d.y = L.ptr(dy).value, L.ptr(imap.w).value, L.ptr(imap.order).value, L.ptr(imap.seg).value, L.ptr(dx).value
+        L.check(L.lib().vdetr_sp_interp_bwd_f32(ctypes.byref(d), L.stream_ptr()), "sp_interp_bwd")
+        return dx, None
+
+
+def interpolate(feats, imap):
+    """[N, C] = the trilinear interpolation of feats [M, C] (contiguous fp32 on the device, any C >= 1) at the points of an
+    ``InterpMap``: the weighted sum of the corners that exist, in ascending corner order, without renormalisation (a point with
+    no site around it reads zeros).  One launch forward; the backward is one launch (plus, once per map, a stable sort and the
+    segment launch) and folds every site's pairs in ascending (point, corner) order: no atomics, two runs agree bit for bit."""
+    if not isinstance(imap, InterpMap):
+        raise RuntimeError("imap must be the InterpMap of interp_map")
+    L.require_float(feats, "feats")
+    if feats.dim() != 2 or feats.shape[1] < 1:
+        raise RuntimeError(f"feats must be a feature table [M, C] with C >= 1 (it is {tuple(feats.shape)})")
+    if feats.shape[0] != imap.M:
+        raise RuntimeError(f"interpolate: feats has {feats.shape[0]} rows, the map {imap.M} sites")
+    _require_table(feats, "feats")
+    if feats.device != imap.nbr.device:
+        raise RuntimeError(f"interpolate: feats on {feats.device}, the map on {imap.nbr.device}")
+    return _InterpFn.apply(feats, imap)
+
+
 _MODE = os.environ.get("VDETR_SP_MODE", "pairs")  # pairs (fused kernels) | plan (batched library GEMMs) | im2col
 _IM2COL = _MODE == "im2col" or os.environ.get("VDETR_SP_IM2COL", "0") == "1"  # A/B switch: one dense im2col GEMM per layer instead of the plan
 
