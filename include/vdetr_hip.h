@@ -1628,6 +1628,74 @@ int vdetr_sp_interp_seg_i32(const int32_t* sorted, const int64_t* order, int M, 
                             vdetr_stream_t stream);
 int vdetr_sp_interp_bwd_f32(const vdetr_sp_interp_desc* d, vdetr_stream_t stream);
 
+/* A sparse tensor's table against ONE ROW PER SCENE (this package's own definitions, restated by
+ * tests/sparse_global_restatement.py): global pooling, broadcast, and the squeeze-excite gate of the inference form.
+ * Tables are point-major [N, C] f32, contiguous, C % 4 == 0, C <= 1024.  Scene s is the rows seg[s] .. seg[s+1]; seg [nseg+1] i32
+ * lives on the DEVICE, ascending, seg[0] = 0, seg[nseg] = N (its values are clamped to [0, N]).  No float atomics, no host read,
+ * every sum in a fixed order: two runs give the same bits.  N == 0 or nseg == 0: no-op.
+ * Chunks of the reducing launches hold vdetr_sp_global_chunk_rows(N) rows and are cut at scene boundaries: at most
+ * ceil(N / rows) + nseg of them; the *_workspace_bytes functions cover that many (and grow with N).
+ *
+ * Pooling forward, two launches (partials per chunk; one workgroup per scene folds them in ascending chunk order):
+ *   y [nseg, C]: sum; avg = the f32 sum times 1.0f / (float)n_s; max = np.max of the scene's slice per channel.  A scene without
+ *   rows gives 0 in every mode.  arg [nseg, C] i32 (max only; NULL otherwise) = the absolute row np.argmax finds: ties go to the
+ *   lowest row, a NaN in the column gives NaN at the lowest row holding one, a column of -inf gives the scene's first row; -1
+ *   for a scene without rows.
+ * Pooling backward, one launch, every element of dx [N, C] written (no memset): sum: dy[s]; avg: the f32 product
+ *   dy[s] * (1.0f / (float)n_s); max: dy[s, c] where arg[s, c] is this row, else +0.  Reads seg and arg, not x or the workspace. */
+#define VDETR_POOL_SUM 0 /* (the mode numbers of vdetr_sp_pool_desc) */
+#define VDETR_POOL_AVG 1
+#define VDETR_POOL_MAX 2
+typedef struct vdetr_sp_global_pool_desc {
+  int32_t N, C, nseg, mode; /* mode: VDETR_POOL_SUM / AVG / MAX */
+  const float* x;
+  const int32_t* seg;
+  float* y;
+  int32_t* arg;
+  void* workspace; /* vdetr_sp_global_pool_workspace_bytes(N, C, nseg); forward only */
+} vdetr_sp_global_pool_desc;
+int vdetr_sp_global_chunk_rows(int N);
+size_t vdetr_sp_global_pool_workspace_bytes(int N, int C, int nseg);
+int vdetr_sp_global_pool_fwd_f32(const vdetr_sp_global_pool_desc* d, vdetr_stream_t stream);
+int vdetr_sp_global_pool_bwd_f32(const vdetr_sp_global_pool_desc* d, const float* dy, float* dx, vdetr_stream_t stream);
+
+/* Broadcast of g [nseg, Cg] over x [N, Cx], one launch: ADD y = x + g[s], MUL y = x * g[s] (both need Cg == Cx), CAT
+ * y [N, Cx + Cg] = (x | g[s]).  Epilogue of the inference form (add / mul only): residual [N, Cx] or NULL is added after the op,
+ * then max(., 0) where relu != 0.
+ * Backward (residual / relu are not read): dx [N, Cx] = dy (add), dy * g[s] (mul), the first Cx columns of dy [N, Cx + Cg] (cat);
+ * dg [nseg, Cg] = per scene sum dy (add), sum dy * x (mul), the sum of the last Cg columns (cat), zero for a scene without rows.
+ * With dg, two launches: the sweep that writes dx leaves the chunk partials of dg, a fold per scene adds them in ascending
+ * chunk order.  dx == NULL or dg == NULL skips that half. */
+#define VDETR_BCAST_ADD 0
+#define VDETR_BCAST_MUL 1
+#define VDETR_BCAST_CAT 2
+typedef struct vdetr_sp_broadcast_desc {
+  int32_t N, Cx, Cg, nseg, mode, relu;
+  const float* x;
+  const float* g;
+  const int32_t* seg;
+  const float* residual;
+  float* y;
+  void* workspace; /* vdetr_sp_broadcast_workspace_bytes(N, Cg, nseg); backward with dg only */
+} vdetr_sp_broadcast_desc;
+size_t vdetr_sp_broadcast_workspace_bytes(int N, int Cg, int nseg);
+int vdetr_sp_broadcast_fwd_f32(const vdetr_sp_broadcast_desc* d, vdetr_stream_t stream);
+int vdetr_sp_broadcast_bwd_f32(const vdetr_sp_broadcast_desc* d, const float* dy, float* dx, float* dg, vdetr_stream_t stream);
+
+/* The gate of a squeeze-excite layer, inference only, two launches: the partials of an average pooling of x [N, C], then one
+ * workgroup per scene that folds them to p_s and goes on to  gate[s] = sigmoid(W2 relu(W1 p_s + b1) + b2)  [nseg, C].
+ * w1 [H, C], w2 [C, H] row-major (nn.Linear), 1 <= H <= 256; b1 [H] / b2 [C] may be NULL.  f32 fused multiply-adds in a fixed
+ * order.  A scene without rows: the formula at p = 0.  workspace: vdetr_sp_global_pool_workspace_bytes(N, C, nseg). */
+typedef struct vdetr_sp_se_gate_desc {
+  int32_t N, C, H, nseg;
+  const float* x;
+  const int32_t* seg;
+  const float *w1, *b1, *w2, *b2;
+  float* gate;
+  void* workspace;
+} vdetr_sp_se_gate_desc;
+int vdetr_sp_se_gate_f32(const vdetr_sp_se_gate_desc* d, vdetr_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Fixed coordinate embeddings — PositionEmbeddingCoordsSine (models/position_embedding.py:21-148); one launch each.
  *   xyz (b,n,3); range_min / range_max (b,3) = the scene extent for `normalize=True` (shift_scale_points,

@@ -486,6 +486,29 @@ class SpInterpDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("M", "N", "C")] + [(n, c_void_p) for n in ("x", "nbr", "w", "order", "seg", "y")]
 
 
+VDETR_BCAST_ADD, VDETR_BCAST_MUL, VDETR_BCAST_CAT = 0, 1, 2
+
+
+class SpGlobalPoolDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_global_pool_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("N", "C", "nseg", "mode")] + [(n, c_void_p) for n in ("x", "seg", "y", "arg", "workspace")]
+
+
+class SpBroadcastDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_broadcast_desc``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("N", "Cx", "Cg", "nseg", "mode", "relu")] +
+                [(n, c_void_p) for n in ("x", "g", "seg", "residual", "y", "workspace")])
+
+
+class SpSeGateDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_se_gate_desc``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("N", "C", "H", "nseg")] +
+                [(n, c_void_p) for n in ("x", "seg", "w1", "b1", "w2", "b2", "gate", "workspace")])
+
+
 class DetStore(ctypes.Structure):
     """Mirror of ``vdetr_det_store``."""
 
@@ -649,6 +672,14 @@ _SIGNATURES = {
     "vdetr_sp_interp_fwd_f32": (c_int, [ctypes.POINTER(SpInterpDesc), c_void_p]),
     "vdetr_sp_interp_seg_i32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vdetr_sp_interp_bwd_f32": (c_int, [ctypes.POINTER(SpInterpDesc), c_void_p]),
+    "vdetr_sp_global_chunk_rows": (c_int, [c_int]),
+    "vdetr_sp_global_pool_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vdetr_sp_global_pool_fwd_f32": (c_int, [ctypes.POINTER(SpGlobalPoolDesc), c_void_p]),
+    "vdetr_sp_global_pool_bwd_f32": (c_int, [ctypes.POINTER(SpGlobalPoolDesc), c_void_p, c_void_p, c_void_p]),
+    "vdetr_sp_broadcast_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vdetr_sp_broadcast_fwd_f32": (c_int, [ctypes.POINTER(SpBroadcastDesc), c_void_p]),
+    "vdetr_sp_broadcast_bwd_f32": (c_int, [ctypes.POINTER(SpBroadcastDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vdetr_sp_se_gate_f32": (c_int, [ctypes.POINTER(SpSeGateDesc), c_void_p]),
     "vdetr_rb_transpose_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "vdetr_rb_qkv_f32": (c_int, [ctypes.POINTER(RbQkvDesc), c_void_p]),
     "vdetr_rb_proj_q_f32": (c_int, [ctypes.POINTER(RbProjQDesc), c_void_p]),

@@ -21,7 +21,10 @@ MinkowskiEngine is NOT under /root/reference (un-vendored): semantics follow its
     ascending input order (DESIGN 6.15); sites are held in key order, which is also the row order of ``sparse_quantize``;
   * ``MinkowskiInterpolation`` / ``features_at_coordinates`` / ``SparseTensor.interpolate`` read a tensor of any stride at float
     coordinates: trilinear over the 2^3 sites around a point, a site's feature AT its integer coordinate, absent sites as zero
-    without renormalisation (this package's own statement).
+    without renormalisation (DESIGN 6.16: this package's own statement);
+  * ``MinkowskiGlobal*Pooling`` write one row per scene of the batch on the origin map (keys (b, 0, 0, 0), ``tensor_stride`` 0; a scene
+    without a site keeps a zero row), ``MinkowskiBroadcast*`` bring such rows back to the sites, ``MinkowskiLinear`` and the pointwise
+    layers take either kind of tensor (this package's own statement).
 The ORDER of the sites of a MinkowskiEngine tensor is an implementation detail of its hash map; here it is ascending
 (batch, x, y, z).  Parity against the MinkowskiEngine binary is unpinned; ``oracle/sparse_oracle.py`` pins the arithmetic
 against torch's dense convolutions.
@@ -357,6 +360,15 @@ class CoordinateManager:
             cache[key] = (S.scene_segments(keys, self.num_scenes), keys)
         return cache[key][0], self.num_scenes
 
+    def origin_keys(self):
+        """the keys of the origin map: one site (b, 0, 0, 0) per scene 0 .. num_scenes - 1, in order — where a global pooling
+        writes its rows (``tensor_stride`` 0 marks them).  Built on the device once the scene count is known."""
+        assert self.num_scenes is not None, "origin_keys: the scene count is not known yet (scene_segments reads it)"
+        if 0 not in self.keys:
+            centre = (S.KEY_BIAS << 32) | (S.KEY_BIAS << 16) | S.KEY_BIAS
+            self.keys[0] = (torch.arange(self.num_scenes, dtype=torch.int64, device=self.device) << 48) | centre
+        return self.keys[0]
+
     def scene_counts(self, keys):
         """sites per batch element of a key set, as a host list.  Cached per key set: it is geometry, and reading it back is a
         host synchronisation that must not sit between the backbone's forward launches and what follows them (measured: the
@@ -670,6 +682,14 @@ def sparse_quantize(coordinates, features=None, labels=None, ignore_label=-100, 
     return out[0] if len(out) == 1 else tuple(out)
 
 
+def _refuse_origin(module, x):
+    """a tensor on the origin map (``tensor_stride == 0``: one row per scene, the result of a global pooling) has no lattice for a
+    kernel to walk"""
+    if x.tensor_stride == 0:
+        raise ValueError(f"{type(module).__name__}: the input is an origin tensor (tensor_stride 0, one row per scene, "
+                         f"{x.keys.shape[0]} rows): convolutions and local poolings need a tensor on sites; use MinkowskiLinear")
+
+
 class MinkowskiConvolution(nn.Module):
     """ME.MinkowskiConvolution(in, out, kernel_size, stride=1, dilation=1, bias=False, kernel_generator=None, dimension=3).
     ``kernel_size`` / ``dilation``: an int or one value per axis; ``kernel_generator`` (KernelGenerator) replaces both and picks
@@ -712,6 +732,7 @@ class MinkowskiConvolution(nn.Module):
 
     def forward(self, x):
         cm, ts = x.coordinate_manager, x.tensor_stride
+        _refuse_origin(self, x)
         out_ts = self._out_stride(ts)
         w = self.kernel if self.kernel.dim() == 3 else self.kernel[None]
         if self.generative:
@@ -822,6 +843,7 @@ class _MinkowskiPooling(nn.Module):
 
     def forward(self, x):
         cm, ts = x.coordinate_manager, x.tensor_stride
+        _refuse_origin(self, x)
         out_ts, out_keys = self._sites(x)
         if _geometry_only():
             cm.kernel_map(x.keys, out_keys, ts, out_ts, self._offsets, self.transposed)
@@ -959,6 +981,103 @@ class MinkowskiELU(_Pointwise):
         self.fn = nn.ELU(alpha)
 
 
+class MinkowskiSigmoid(_Pointwise):
+    kind = "sigmoid"
+
+    def __init__(self):
+        super().__init__()
+        self.fn = nn.Sigmoid()
+
+
+class MinkowskiLinear(nn.Module):
+    """ME.MinkowskiLinear(in_features, out_features, bias=True): a linear map of the feature rows of any SparseTensor, the
+    origin one included; parameters under ``.linear`` (state-dict keys ``linear.weight`` / ``linear.bias``)."""
+
+    def __init__(self, in_features, out_features, bias=True):
+        super().__init__()
+        self.linear = nn.Linear(in_features, out_features, bias=bias)
+
+    def forward(self, x):
+        if _geometry_only():
+            return x._like(x.F.new_empty((x.F.shape[0], self.linear.out_features)))
+        return x._like(self.linear(x.F))
+
+
+class MinkowskiGlobalPooling(nn.Module):
+    """ME.MinkowskiGlobalPooling (the average, ME's default) and its sum / max forms: a SparseTensor of the same coordinate
+    manager on the ORIGIN map — one row per scene 0 .. ``cm.num_scenes - 1`` in order, keys (b, 0, 0, 0), ``tensor_stride`` 0 as
+    the marker.  A scene absent from the input's key set (a MinkowskiPruning took it) keeps its row: zeros, no gradient.  avg is
+    the float32 sum times 1 / n; max follows np.max / np.argmax.  These definitions are this package's own.  Two
+    launches forward, one backward, no host read.  Under ``geometry_only`` the segment table is built and cached and the output
+    table is uninitialised."""
+    mode = "avg"
+
+    def forward(self, x):
+        if not isinstance(x, SparseTensor):
+            raise ValueError(f"{type(self).__name__}: a SparseTensor is expected, not {type(x).__name__}")
+        if x.tensor_stride == 0:
+            raise ValueError(f"{type(self).__name__}: the input is already an origin tensor (tensor_stride 0)")
+        cm = x.coordinate_manager
+        seg, nseg = cm.scene_segments(x.keys)  # geometry: cached per key set, on the device
+        if _geometry_only():
+            f = x.F.new_empty((nseg, x.F.shape[1]))
+        else:
+            f = S.global_pool(x.F.contiguous(), seg, nseg, self.mode)
+        return SparseTensor(f, tensor_stride=0, coordinate_manager=cm, keys=cm.origin_keys())
+
+
+class MinkowskiGlobalSumPooling(MinkowskiGlobalPooling):
+    mode = "sum"
+
+
+class MinkowskiGlobalAvgPooling(MinkowskiGlobalPooling):
+    mode = "avg"
+
+
+class MinkowskiGlobalMaxPooling(MinkowskiGlobalPooling):
+    mode = "max"
+
+
+class MinkowskiBroadcast(nn.Module):
+    """ME.MinkowskiBroadcast*: ``forward(x, x_glob)`` combines every row of ``x`` with its scene's row of the origin tensor
+    ``x_glob`` (a global pooling's result, possibly through MinkowskiLinear / pointwise layers).  The result lives on x's keys and
+    stride.  One launch forward; the backward's sweep for dx leaves the partials of the origin tensor's gradient, a fold per scene
+    adds them.  Under ``geometry_only`` x passes through (concatenation: an uninitialised table of the right width)."""
+    mode = None
+
+    def forward(self, x, x_glob):
+        name = type(self).__name__
+        if self.mode is None:
+            raise NotImplementedError("MinkowskiBroadcast is the base: use MinkowskiBroadcastAddition / Multiplication / Concatenation")
+        if not isinstance(x, SparseTensor) or not isinstance(x_glob, SparseTensor):
+            raise ValueError(f"{name}: two SparseTensors are expected, not {type(x).__name__} and {type(x_glob).__name__}")
+        cm = x.coordinate_manager
+        if x_glob.coordinate_manager is not cm or x_glob.tensor_stride != 0:
+            raise ValueError(f"{name}: x_glob must be an origin tensor (tensor_stride 0) of x's coordinate manager; it has "
+                             f"tensor_stride {x_glob.tensor_stride} and manager {x_glob.coordinate_manager!r}, x has {cm!r}")
+        seg, nseg = cm.scene_segments(x.keys)
+        cx, (rows, cg) = x.F.shape[1], x_glob.F.shape
+        if rows != nseg:
+            raise ValueError(f"{name}: x_glob has {rows} rows, the coordinate manager {nseg} scenes")
+        if self.mode != "cat" and cg != cx:
+            raise ValueError(f"{name}: x has {cx} channels and x_glob {cg}")
+        if _geometry_only():
+            return x if self.mode != "cat" else x._like(x.F.new_empty((x.F.shape[0], cx + cg)))
+        return x._like(S.broadcast(x.F.contiguous(), x_glob.F.contiguous(), seg, nseg, self.mode))
+
+
+class MinkowskiBroadcastAddition(MinkowskiBroadcast):
+    mode = "add"
+
+
+class MinkowskiBroadcastMultiplication(MinkowskiBroadcast):
+    mode = "mul"
+
+
+class MinkowskiBroadcastConcatenation(MinkowskiBroadcast):
+    mode = "cat"
+
+
 class BasicBlock(nn.Module):
     """MinkowskiEngine.modules.resnet_block.BasicBlock (used by models/mink_resnet.py:5,22-23)."""
     expansion = 1
@@ -1010,7 +1129,7 @@ def fuse_activations(module):
         if isinstance(m, nn.Sequential):
             mods = list(m)
             for a, b in zip(mods, mods[1:]):
-                if isinstance(a, MinkowskiBatchNorm) and isinstance(b, _Pointwise) and (b.kind == "relu" or b.fn.alpha == 1.0):
+                if isinstance(a, MinkowskiBatchNorm) and isinstance(b, _Pointwise) and (b.kind == "relu" or (b.kind == "elu" and b.fn.alpha == 1.0)):
                     a.fused_act = b.kind
     return module
 

@@ -805,6 +805,186 @@ def instance_norm(x, seg, nseg, weight=None, bias=None, eps=1e-6):
     return _SpInstanceNormFn.apply(x, seg, int(nseg), weight, bias, eps)
 
 
+# ---- a table against one row per scene: global pooling, broadcast, the squeeze-excite gate (csrc/sparse_global.hip) ----
+BCAST_MODES = {"add": L.VDETR_BCAST_ADD, "mul": L.VDETR_BCAST_MUL, "cat": L.VDETR_BCAST_CAT}
+
+
+def global_chunk_rows(N):
+    """rows per chunk of the reducing launches of sparse_global.hip on a table of N rows"""
+    return int(L.lib().vdetr_sp_global_chunk_rows(int(N)))
+
+
+def _require_scene_table(op, x, seg, nseg, name="x"):
+    L.require_gpu(x, name)
+    L.require_float(x, name)
+    L.require_contiguous(x, name)
+    L.require_gpu(seg, "seg")
+    L.require_int(seg, "seg")
+    L.require_contiguous(seg, "seg")
+    if x.dim() != 2 or seg.numel() != nseg + 1:
+        raise RuntimeError(f"{op}: {name} must be [N, C] (it is {tuple(x.shape)}) and seg hold nseg + 1 = {nseg + 1} offsets "
+                           f"(it holds {seg.numel()})")
+
+
+def _require_scene_rows(op, g, nseg, name, C=None):
+    L.require_gpu(g, name)
+    L.require_float(g, name)
+    L.require_contiguous(g, name)
+    if g.dim() != 2 or g.shape[0] != nseg or (C is not None and g.shape[1] != C):
+        raise RuntimeError(f"{op}: {name} is {tuple(g.shape)}, expected {(nseg, 'C' if C is None else C)}")
+
+
+def _global_pool_desc(N, C, nseg, mode, seg, arg):
+    d = L.SpGlobalPoolDesc()
+    d.N, d.C, d.nseg, d.mode = N, C, nseg, mode
+    d.seg, d.arg = seg.data_ptr(), L.ptr(arg).value
+    return d
+
+
+class _GlobalPoolFn(Function):
+    """y [nseg, C] = sum / average / maximum of the rows seg[s] .. seg[s+1] of x (csrc/sparse_global.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, seg, nseg, mode):
+        N, C = x.shape
+        lib = L.lib()
+        new = torch.empty if N and nseg else torch.zeros  # (a table without rows launches nothing)
+        y = new((nseg, C), dtype=torch.float32, device=x.device)
+        arg = None
+        if mode == L.VDETR_POOL_MAX:
+            arg = torch.empty((nseg, C), dtype=torch.int32, device=x.device) if N and nseg else \
+                torch.full((nseg, C), -1, dtype=torch.int32, device=x.device)
+        ws = L.workspace(lib.vdetr_sp_global_pool_workspace_bytes(N, C, nseg), x.device)
+        d = _global_pool_desc(N, C, nseg, mode, seg, arg)
+        d.x, d.y, d.workspace = x.data_ptr(), y.data_ptr(), ws.data_ptr()
+        L.check(lib.vdetr_sp_global_pool_fwd_f32(ctypes.byref(d), L.stream_ptr()), "sp_global_pool_fwd")
+        ctx.save_for_backward(seg, arg)
+        ctx.cfg = (N, C, nseg, mode)
+        if arg is not None:
+            ctx.mark_non_differentiable(arg)
+        return y, arg
+
+    @staticmethod
+    def backward(ctx, dy, _darg):
+        seg, arg = ctx.saved_tensors
+        N, C, nseg, mode = ctx.cfg
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        dy = dy.contiguous()
+        dx = (torch.empty if N and nseg else torch.zeros)((N, C), dtype=torch.float32, device=dy.device)
+        d = _global_pool_desc(N, C, nseg, mode, seg, arg)
+        L.check(L.lib().vdetr_sp_global_pool_bwd_f32(ctypes.byref(d), L.ptr(dy), L.ptr(dx), L.stream_ptr()), "sp_global_pool_bwd")
+        return dx, None, None, None
+
+
+def global_pool(x, seg, nseg, mode, return_arg=False):
+    """Global pooling of a sparse tensor's table x [N, C] (contiguous fp32 on the device, C % 4 == 0, C <= 1024) over the scenes
+    ``seg`` [nseg + 1] int32 (``scene_segments``; device, seg[0] = 0, seg[nseg] = N): mode "sum" | "avg" | "max" -> y [nseg, C].
+    avg is the float32 sum times 1 / n; a scene without rows gives 0 in every mode and passes no gradient; max follows np.max /
+    np.argmax (ties: the lowest row; a NaN wins).  ``return_arg``: also arg [nseg, C] int32, the absolute row of every maximum
+    (-1: no row; None unless mode is "max").  Two launches forward, one backward; deterministic; no host read."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"global_pool: mode {mode!r} (sum, avg, max)")
+    _require_scene_table("global_pool", x, seg, nseg)
+    y, arg = _GlobalPoolFn.apply(x, seg, int(nseg), POOL_MODES[mode])
+    return (y, arg) if return_arg else y
+
+
+def _broadcast_desc(N, Cx, Cg, nseg, mode, seg):
+    d = L.SpBroadcastDesc()
+    d.N, d.Cx, d.Cg, d.nseg, d.mode, d.relu = N, Cx, Cg, nseg, mode, 0
+    d.seg = seg.data_ptr()
+    return d
+
+
+def _broadcast_forward(x, g, seg, nseg, mode, residual=None, relu=False):
+    (N, Cx), Cg = x.shape, g.shape[1]
+    y = torch.empty((N, Cx + Cg if mode == L.VDETR_BCAST_CAT else Cx), dtype=torch.float32, device=x.device)
+    d = _broadcast_desc(N, Cx, Cg, nseg, mode, seg)
+    d.relu = int(bool(relu))
+    d.x, d.g, d.residual, d.y = x.data_ptr(), g.data_ptr(), L.ptr(residual).value, y.data_ptr()
+    L.check(L.lib().vdetr_sp_broadcast_fwd_f32(ctypes.byref(d), L.stream_ptr()), "sp_broadcast_fwd")
+    return y
+
+
+class _BroadcastFn(Function):
+    """y = x + g[s] / x * g[s] / (x | g[s]) over the rows seg[s] .. seg[s+1] (csrc/sparse_global.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, g, seg, nseg, mode):
+        ctx.save_for_backward(x if mode == L.VDETR_BCAST_MUL else None, g if mode == L.VDETR_BCAST_MUL else None, seg)
+        ctx.cfg = (x.shape[0], x.shape[1], g.shape[1], nseg, mode)
+        return _broadcast_forward(x, g, seg, nseg, mode)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, g, seg = ctx.saved_tensors
+        N, Cx, Cg, nseg, mode = ctx.cfg
+        need_x, need_g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_g):
+            return None, None, None, None, None
+        dy = dy.contiguous()
+        lib = L.lib()
+        live = bool(N and nseg)
+        dx = dg = ws = None
+        if need_x:
+            if mode == L.VDETR_BCAST_ADD:
+                dx = dy  # (no launch: the gradient passes through)
+            else:
+                dx = (torch.empty if live else torch.zeros)((N, Cx), dtype=torch.float32, device=dy.device)
+        if need_g:
+            dg = (torch.empty if live else torch.zeros)((nseg, Cg), dtype=torch.float32, device=dy.device)
+            ws = L.workspace(lib.vdetr_sp_broadcast_workspace_bytes(N, Cg, nseg), dy.device)
+        launch_dx = dx if mode != L.VDETR_BCAST_ADD else None
+        if launch_dx is not None or dg is not None:
+            d = _broadcast_desc(N, Cx, Cg, nseg, mode, seg)
+            d.x, d.g, d.workspace = L.ptr(x).value, L.ptr(g).value, L.ptr(ws).value
+            L.check(lib.vdetr_sp_broadcast_bwd_f32(ctypes.byref(d), L.ptr(dy), L.ptr(launch_dx), L.ptr(dg), L.stream_ptr()),
+                    "sp_broadcast_bwd")
+        return dx, dg, None, None, None
+
+
+def broadcast(x, g, seg, nseg, mode):
+    """Broadcast of one row per scene over a sparse tensor's table: x [N, Cx], g [nseg, Cg] (contiguous fp32 on the device,
+    widths multiples of 4 and <= 1024), ``seg`` [nseg + 1] int32 as in ``global_pool``; mode "add" | "mul" (Cg == Cx) -> [N, Cx],
+    "cat" -> [N, Cx + Cg] = (x | g[s]).  One launch forward; backward: one sweep for dx that also leaves the partials of dg, and a
+    fold (nothing is launched for a half nobody needs; the dx of "add" is dy itself).  Deterministic; no host read."""
+    if mode not in BCAST_MODES:
+        raise ValueError(f"broadcast: mode {mode!r} (add, mul, cat)")
+    _require_scene_table("broadcast", x, seg, nseg)
+    _require_scene_rows("broadcast", g, nseg, "g", None if mode == "cat" else x.shape[1])
+    return _BroadcastFn.apply(x, g, seg, int(nseg), BCAST_MODES[mode])
+
+
+def se_scale(x, seg, nseg, w1, b1, w2, b2, residual=None, relu=False):
+    """The squeeze-excite layer of inference in three launches: x [N, C] * sigmoid(W2 relu(W1 avg_s(x) + b1) + b2)[s]
+    (+ residual [N, C]) (then ReLU).  w1 [H, C], w2 [C, H] as nn.Linear holds them, H <= 256; b1 [H] / b2 [C] or None.  Launches:
+    the pooling partials, the fold that goes on to the gate in the scene's workgroup, the broadcast multiply with its epilogue.
+    No autograd: gradients do not flow through it."""
+    _require_scene_table("se_scale", x, seg, nseg)
+    N, C = x.shape
+    if w1.dim() != 2 or w2.dim() != 2 or w1.shape[1] != C or tuple(w2.shape) != (C, w1.shape[0]):
+        raise RuntimeError(f"se_scale: w1 is {tuple(w1.shape)} and w2 {tuple(w2.shape)}, expected [H, {C}] and [{C}, H]")
+    H = w1.shape[0]
+    for name, t, n in (("w1", w1, H * C), ("b1", b1, H), ("w2", w2, C * H), ("b2", b2, C), ("residual", residual, N * C)):
+        if t is not None:
+            L.require_gpu(t, name)
+            L.require_float(t, name)
+            L.require_contiguous(t, name)
+            if t.numel() != n:
+                raise RuntimeError(f"se_scale: {name} has {t.numel()} elements, expected {n}")
+    lib = L.lib()
+    nseg = int(nseg)
+    gate = torch.empty((nseg, C), dtype=torch.float32, device=x.device)
+    ws = L.workspace(lib.vdetr_sp_global_pool_workspace_bytes(N, C, nseg), x.device)
+    d = L.SpSeGateDesc()
+    d.N, d.C, d.H, d.nseg = N, C, H, nseg
+    d.x, d.seg, d.gate, d.workspace = x.data_ptr(), seg.data_ptr(), gate.data_ptr(), ws.data_ptr()
+    d.w1, d.b1, d.w2, d.b2 = w1.data_ptr(), L.ptr(b1).value, w2.data_ptr(), L.ptr(b2).value
+    L.check(lib.vdetr_sp_se_gate_f32(ctypes.byref(d), L.stream_ptr()), "sp_se_gate")
+    return _broadcast_forward(x, gate, seg, nseg, L.VDETR_BCAST_MUL, residual, relu)
+
+
 # ---- sparse tensors on different key sets: union add / subtract and pruning (csrc/sparse_union.hip; DESIGN 6.11) ------------------
 def union_tile():
     """keys per workgroup of the two map builders (the tests place their edge cases on its multiples)"""
