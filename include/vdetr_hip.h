@@ -1430,6 +1430,34 @@ typedef struct vdetr_sp_pool_desc {
 int vdetr_sp_pool_fwd_f32(const vdetr_sp_pool_desc* d, vdetr_stream_t stream);
 int vdetr_sp_pool_bwd_f32(const vdetr_sp_pool_desc* d, const int32_t* inv, const float* dy, float* dx, vdetr_stream_t stream);
 
+/* Channelwise (depthwise) convolution of a sparse tensor over a kernel map nbr [K,nout]: ME.MinkowskiChannelwiseConvolution.
+ * One weight per (offset, channel), w [K,C], no mixing across channels.  With N(u) = {k : 0 <= nbr[k][u] < nin}:
+ *   forward  y[u][c]  = (sum over k in N(u) of w[k][c] * x[nbr[k][u]][c]) + bias[c]
+ *            the sum starts at +0 and takes one fmaf per term in ascending k; bias (may be NULL) is added last; an empty N(u)
+ *            gives bias[c], or exact +0 without one
+ *   dgrad    dx[i][c] = sum_k w[k][c] * dy[inv[k][i]][c]   through inv [K,nin] (vdetr_sp_inverse_map_i32 of nbr), ascending k;
+ *            every element of dx is written (no memset, no atomics); the same kernel as the forward, map and counts swapped
+ *   wgrad    dw[k][c] = sum over the u with k in N(u) of x[nbr[k][u]][c] * dy[u][c];   db[c] = sum_u dy[u][c]   (dw or db may be NULL)
+ *            two launches: one partial [K+1,C] per chunk of vdetr_sp_cwconv_chunk_rows(nout) output rows into workspace (row K is
+ *            the bias partial: one sweep over dy serves both), then a fold of the chunks in a fixed ascending order.
+ * All arithmetic fp32; tables point-major, contiguous; C % 4 == 0, 4 <= C <= 1024, 1 <= K <= 127.  No float atomics, no host read:
+ * two runs agree bit for bit.  nout == 0 (forward) / nin == 0 (dgrad): no-op.  wgrad over nout == 0 writes zeros into dw / db,
+ * dgrad over nout == 0 zeros into dx. */
+typedef struct vdetr_sp_cwconv_desc {
+  int32_t K, nout, nin, C;
+  const float* x;     /* [nin,C] (forward, wgrad) */
+  const int32_t* nbr; /* [K,nout] (forward, wgrad) */
+  const float* w;     /* [K,C] (forward, dgrad) */
+  const float* bias;  /* [C] or NULL (forward) */
+  float* y;           /* [nout,C] (forward) */
+  void* workspace;    /* vdetr_sp_cwconv_workspace_bytes(K, nout, C); wgrad only */
+} vdetr_sp_cwconv_desc;
+int vdetr_sp_cwconv_chunk_rows(int nout);
+size_t vdetr_sp_cwconv_workspace_bytes(int K, int nout, int C); /* 0 for arguments outside the ranges above */
+int vdetr_sp_cwconv_fwd_f32(const vdetr_sp_cwconv_desc* d, vdetr_stream_t stream);
+int vdetr_sp_cwconv_dgrad_f32(const vdetr_sp_cwconv_desc* d, const int32_t* inv, const float* dy, float* dx, vdetr_stream_t stream);
+int vdetr_sp_cwconv_wgrad_f32(const vdetr_sp_cwconv_desc* d, const float* dy, float* dw, float* db, vdetr_stream_t stream);
+
 /* InstanceNorm over the point-major table [N,C] of a sparse tensor (ME.MinkowskiInstanceNorm; models/mink_resnet.py with
  * stem_bn = False, models/modules/common.py:24-30): per scene s (rows seg[s] .. seg[s+1], key order keeps them contiguous) and
  * channel,  y = (x - mean_s) * rsqrt(var_s + eps) * gamma + beta  with the biased variance over the scene's rows.

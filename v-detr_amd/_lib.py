@@ -418,6 +418,13 @@ class SpPoolDesc(ctypes.Structure):
                 [(n, c_void_p) for n in ("x", "nbr", "y", "inv_count", "arg")])
 
 
+class SpCwConvDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_cwconv_desc``."""
+
+    _fields_ = ([(n, ctypes.c_int32) for n in ("K", "nout", "nin", "C")] +
+                [(n, c_void_p) for n in ("x", "nbr", "w", "bias", "y", "workspace")])
+
+
 class SpInormDesc(ctypes.Structure):
     """Mirror of ``vdetr_sp_inorm_desc``."""
 
@@ -650,6 +657,11 @@ _SIGNATURES = {
     "vdetr_sp_bn_act_bwd_f32": (c_int, [ctypes.POINTER(SpBnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vdetr_sp_pool_fwd_f32": (c_int, [ctypes.POINTER(SpPoolDesc), c_void_p]),
     "vdetr_sp_pool_bwd_f32": (c_int, [ctypes.POINTER(SpPoolDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vdetr_sp_cwconv_chunk_rows": (c_int, [c_int]),
+    "vdetr_sp_cwconv_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vdetr_sp_cwconv_fwd_f32": (c_int, [ctypes.POINTER(SpCwConvDesc), c_void_p]),
+    "vdetr_sp_cwconv_dgrad_f32": (c_int, [ctypes.POINTER(SpCwConvDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vdetr_sp_cwconv_wgrad_f32": (c_int, [ctypes.POINTER(SpCwConvDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
     "vdetr_sp_inorm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vdetr_sp_inorm_fwd_f32": (c_int, [ctypes.POINTER(SpInormDesc), c_void_p]),
     "vdetr_sp_inorm_bwd_f32": (c_int, [ctypes.POINTER(SpInormDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -765,6 +765,54 @@ class MinkowskiGenerativeConvolutionTranspose(MinkowskiConvolution):
     transposed, generative = True, True
 
 
+class MinkowskiChannelwiseConvolution(nn.Module):
+    """ME.MinkowskiChannelwiseConvolution(in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, kernel_generator=None,
+    dimension=3): the depthwise convolution.  ``kernel`` is [volume, in_channels] in the generator's offset order (one weight per
+    offset and channel, no mixing across channels), ``bias`` [1, in_channels]; y[u] = sum over the neighbours that exist of
+    kernel[k] * x[nbr[k][u]] (+ bias).  Output sites and map are those of a MinkowskiConvolution / pooling of the same generator and
+    stride: the coordinate manager's cached map, shared with them.  One HIP launch forward, one for the input gradient, two for the
+    kernel / bias gradients (``sparse_ops.channelwise_conv``).
+    Not built: a transposed channelwise convolution (MinkowskiEngine has none), dimension 4, double backward, and a fused
+    convolution -> BatchNorm -> activation inference form (a following MinkowskiBatchNorm runs its own launch)."""
+
+    def __init__(self, in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, kernel_generator=None, dimension=3):
+        super().__init__()
+        assert dimension == 3
+        if kernel_generator is None:
+            kernel_generator = KernelGenerator(kernel_size, stride, dilation, is_transpose=False, dimension=dimension)
+        else:
+            ks, dl = kernel_generator.kernel_size, kernel_generator.kernel_dilation
+            kernel_size = ks[0] if len(set(ks)) == 1 else ks  # (a cubic size stays an int)
+            dilation = dl[0] if len(set(dl)) == 1 else dl
+        if isinstance(stride, (tuple, list)):
+            if any(s != stride[0] for s in stride):
+                raise NotImplementedError(f"stride {stride}: one stride for all three axes only")
+            stride = int(stride[0])
+        if stride > 1 and max(kernel_generator.kernel_dilation) > 1:
+            raise ValueError(f"stride {stride} together with dilation {kernel_generator.kernel_dilation}")
+        self.in_channels, self.out_channels, self.kernel_size, self.stride = in_channels, in_channels, kernel_size, stride
+        self.dilation, self.kernel_generator = dilation, kernel_generator
+        self._offsets = _Offsets(kernel_generator.scaled_offsets())
+        kv = kernel_generator.kernel_volume
+        self.kernel = nn.Parameter(torch.empty(kv, in_channels))
+        self.bias = nn.Parameter(torch.zeros(1, in_channels)) if bias else None
+        stdv = 1.0 / math.sqrt(in_channels * kv)
+        with torch.no_grad():
+            self.kernel.uniform_(-stdv, stdv)
+
+    def forward(self, x):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        _refuse_origin(self, x)
+        out_ts = ts * self.stride
+        out_keys = x.keys if out_ts == ts else cm.strided(x.keys, ts, out_ts)
+        nbr, inv = cm.pool_map(x.keys, out_keys, ts, out_ts, self._offsets, False)
+        if _geometry_only():
+            return SparseTensor(x.F.new_empty((out_keys.shape[0], self.in_channels)), tensor_stride=out_ts, coordinate_manager=cm,
+                                keys=out_keys)
+        f = S.channelwise_conv(x.F.contiguous(), self.kernel, nbr, inv, self.bias)
+        return SparseTensor(f, tensor_stride=out_ts, coordinate_manager=cm, keys=out_keys)
+
+
 class MinkowskiBatchNorm(nn.Module):
     """BatchNorm1d over the feature rows of all sites of the batch (ME.MinkowskiBatchNorm: parameters under ``.bn``)."""
 

@@ -733,6 +733,98 @@ def sparse_pool(feats, nbr, inv, mode, return_aux=False):
     return (y, inv_count, arg) if return_aux else y
 
 
+def cwconv_chunk_rows(nout):
+    """output rows per chunk of the weight-gradient sweep of sparse_cwconv.hip on a table of nout rows"""
+    return int(L.lib().vdetr_sp_cwconv_chunk_rows(int(nout)))
+
+
+def _cwconv_desc(K, nout, nin, C):
+    d = L.SpCwConvDesc()
+    d.K, d.nout, d.nin, d.C = K, nout, nin, C
+    return d
+
+
+class _ChannelwiseConvFn(Function):
+    """y [Nout, C] = (sum_k weight[k] * feats[nbr[k, u]] over the neighbours that exist) + bias (csrc/sparse_cwconv.hip)."""
+
+    @staticmethod
+    def forward(ctx, feats, weight, bias, nbr, inv):
+        K, nout = nbr.shape
+        nin, C = feats.shape
+        b = bias.detach().reshape(-1) if bias is not None else None
+        y = torch.empty((nout, C), dtype=torch.float32, device=feats.device)
+        d = _cwconv_desc(K, nout, nin, C)
+        d.x, d.nbr, d.w, d.bias, d.y = feats.data_ptr(), nbr.data_ptr(), weight.data_ptr(), L.ptr(b).value, y.data_ptr()
+        L.check(L.lib().vdetr_sp_cwconv_fwd_f32(ctypes.byref(d), L.stream_ptr()), "sp_cwconv_fwd")
+        ctx.save_for_backward(feats, weight, nbr, inv)
+        ctx.bias_shape = None if bias is None else bias.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        feats, weight, nbr, inv = ctx.saved_tensors
+        K, nout = nbr.shape
+        nin, C = feats.shape
+        want_x, want_w, want_b = ctx.needs_input_grad[:3]
+        want_b = want_b and ctx.bias_shape is not None
+        lib, dev = L.lib(), dy.device
+        dy = dy.contiguous()
+        d = _cwconv_desc(K, nout, nin, C)
+        dx = dw = db = None
+        if want_x:
+            dx = torch.empty((nin, C), dtype=torch.float32, device=dev)
+            d.w = weight.data_ptr()
+            L.check(lib.vdetr_sp_cwconv_dgrad_f32(ctypes.byref(d), L.ptr(inv), L.ptr(dy), L.ptr(dx), L.stream_ptr()), "sp_cwconv_dgrad")
+        if want_w or want_b:
+            dw = torch.empty((K, C), dtype=torch.float32, device=dev) if want_w else None
+            db = torch.empty(C, dtype=torch.float32, device=dev) if want_b else None
+            ws = L.workspace(lib.vdetr_sp_cwconv_workspace_bytes(K, nout, C), dev)
+            d.x, d.nbr, d.workspace = feats.data_ptr(), nbr.data_ptr(), ws.data_ptr()
+            L.check(lib.vdetr_sp_cwconv_wgrad_f32(ctypes.byref(d), L.ptr(dy), L.ptr(dw), L.ptr(db), L.stream_ptr()), "sp_cwconv_wgrad")
+            if db is not None:
+                db = db.reshape(ctx.bias_shape)
+        return dx, dw, db, None, None
+
+
+def channelwise_conv(feats, weight, nbr, inv=None, bias=None):
+    """Channelwise (depthwise) convolution over a kernel map: feats [Nin, C] (contiguous fp32 on the device, C % 4 == 0,
+    4 <= C <= 1024), weight [K, C] (one weight per offset and channel), nbr [K, Nout] (``kernel_map``), inv [K, Nin]
+    (``inverse_map(nbr, Nin)``; None: built here when feats needs a gradient), bias [C] or [1, C] or None -> y [Nout, C] =
+    (sum_k weight[k] * feats[nbr[k, u]] over the neighbours that exist, one fmaf per term in ascending k) + bias.  A site without
+    a neighbour gives the bias (exact +0 without one).  One launch forward; backward one launch for the input gradient (a gather
+    through ``inv``) and two for the weight and bias gradients (chunk partials, then a fold), each only when asked for:
+    deterministic, no atomics, no host read."""
+    op = "channelwise_conv"
+    for name, t in (("feats", feats), ("weight", weight), ("bias", bias)):
+        if t is not None:
+            L.require_gpu(t, name)
+            L.require_float(t, name)
+            L.require_contiguous(t, name)
+    L.require_gpu(nbr, "nbr")
+    L.require_int(nbr, "nbr")
+    L.require_contiguous(nbr, "nbr")
+    if feats.dim() != 2 or nbr.dim() != 2:
+        raise RuntimeError(f"{op}: feats must be [Nin, C] (it is {tuple(feats.shape)}) and nbr [K, Nout] (it is {tuple(nbr.shape)})")
+    (nin, C), K = feats.shape, nbr.shape[0]
+    if C % 4 or not 4 <= C <= 1024:
+        raise RuntimeError(f"{op}: C={C} must be a multiple of 4 in 4 .. 1024 (float4 rows)")
+    if not 1 <= K <= 127:
+        raise RuntimeError(f"{op}: K={K} must be in 1 .. 127")
+    if tuple(weight.shape) != (K, C):
+        raise RuntimeError(f"{op}: weight is {tuple(weight.shape)}, expected {(K, C)}")
+    if bias is not None and tuple(bias.shape) not in ((C,), (1, C)):
+        raise RuntimeError(f"{op}: bias is {tuple(bias.shape)}, expected {(C,)} or {(1, C)}")
+    if inv is None and feats.requires_grad and torch.is_grad_enabled():
+        inv = inverse_map(nbr, nin)
+    if inv is not None:
+        L.require_gpu(inv, "inv")
+        L.require_int(inv, "inv")
+        L.require_contiguous(inv, "inv")
+        if tuple(inv.shape) != (K, nin):
+            raise RuntimeError(f"{op}: inv is {tuple(inv.shape)}, expected {(K, nin)}")
+    return _ChannelwiseConvFn.apply(feats, weight, bias, nbr, inv)
+
+
 class _SpInstanceNormFn(Function):
     """y = (x - mean_s) * rsqrt(var_s + eps) * gamma + beta per scene s = rows seg[s] .. seg[s+1] (csrc/sp_inorm.hip)."""
 
