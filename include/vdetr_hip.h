@@ -1565,6 +1565,21 @@ typedef struct vdetr_sp_voxel_keys_desc {
 int vdetr_sp_voxel_tile(void);
 int vdetr_sp_voxel_keys_f32(const vdetr_sp_voxel_keys_desc* d, vdetr_stream_t stream);
 
+/* The candidate keys of a kernel region (expand_coordinates), one launch.  keys [N] i64: sorted unique keys of
+ * vdetr_sp_kernel_map_i32; offsets [K, 3] i32: added to the site as they are (the host has scaled and signed them).
+ * cand [K * N] i64: cand[k * N + i] = the key of site i moved by offsets[k], or -1 where x, y or z leaves -32768 .. 32767 — the
+ * range flag of vdetr_sp_voxel_keys_f32, which vdetr_sp_voxel_sites_i64 reports after the sort.  The test is per field: a
+ * coordinate at the edge never carries into the field beside it or wraps.  A negative input key gives -1.  No atomics, no memset,
+ * no host read.  N == 0 or K == 0: no-op.  K * N >= 2^31, a negative count or a NULL pointer with K * N > 0: an error code, nothing
+ * launched. */
+typedef struct vdetr_sp_region_keys_desc {
+  int32_t N, K;
+  const int64_t* keys;
+  const int32_t* offsets;
+  int64_t* cand;
+} vdetr_sp_region_keys_desc;
+int vdetr_sp_region_keys_i64(const vdetr_sp_region_keys_desc* d, vdetr_stream_t stream);
+
 /* Sites: from the keys sorted ascending by a STABLE sort and that sort's permutation `order` [N] i64 to
  *   sites [M] i64 ascending and unique; inverse [N] i32 = the site row of every input row; first [M] i64 = the lowest input row of
  *   each site; order32 [N] = the permutation as i32; seg [M + 1] i32 = the run starts in sorted order (seg[M] = N);

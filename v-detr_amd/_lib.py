@@ -465,6 +465,12 @@ class SpVoxelKeysDesc(ctypes.Structure):
                 [(n, c_void_p) for n in ("points", "offsets", "coords", "keys")])
 
 
+class SpRegionKeysDesc(ctypes.Structure):
+    """Mirror of ``vdetr_sp_region_keys_desc``."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("N", "K")] + [(n, c_void_p) for n in ("keys", "offsets", "cand")]
+
+
 class SpVoxelSitesDesc(ctypes.Structure):
     """Mirror of ``vdetr_sp_voxel_sites_desc``."""
 
@@ -674,6 +680,7 @@ _SIGNATURES = {
     "vdetr_sp_take_rows_f32": (c_int, [ctypes.POINTER(SpTakeRowsDesc), c_void_p]),
     "vdetr_sp_voxel_tile": (c_int, []),
     "vdetr_sp_voxel_keys_f32": (c_int, [ctypes.POINTER(SpVoxelKeysDesc), c_void_p]),
+    "vdetr_sp_region_keys_i64": (c_int, [ctypes.POINTER(SpRegionKeysDesc), c_void_p]),
     "vdetr_sp_voxel_sites_workspace_bytes": (c_size_t, [c_int]),
     "vdetr_sp_voxel_sites_i64": (c_int, [ctypes.POINTER(SpVoxelSitesDesc), c_void_p]),
     "vdetr_sp_voxel_reduce_f32": (c_int, [ctypes.POINTER(SpVoxelReduceDesc), c_void_p]),

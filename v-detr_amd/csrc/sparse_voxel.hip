@@ -84,6 +84,32 @@ __global__ __launch_bounds__(256) void coord_keys_kernel(CoordKeysParams P) {
   P.keys[i] = pack_key(c.x, c.y, c.z, c.w);
 }
 
+// The candidate keys of a region (expand_coordinates): one thread per (offset k, site i) writes cand[k * N + i], the key
+// of site i moved by offsets[k] — offset-major, so that adjacent lanes read adjacent keys and write adjacent candidates.  Each
+// field is taken out of the key, moved in 64 bits and tested on its own: a coordinate that leaves -32768 .. 32767 makes the whole
+// candidate -1 (the range flag of the keys above) and never carries into the field beside it.  A negative input key stays -1.
+struct RegionKeysParams {
+  int N;
+  long long total;         // K * N < 2^31
+  const int64_t* keys;     // [N]
+  const int32_t* offsets;  // [K, 3]
+  int64_t* cand;           // [K * N]
+};
+
+__global__ __launch_bounds__(256) void region_keys_kernel(RegionKeysParams P) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= P.total) return;
+  const int k = (int)(t / P.N);
+  const int i = (int)(t - (long long)k * P.N);
+  const int64_t key = P.keys[i];
+  const int32_t* o = P.offsets + (size_t)k * 3;
+  const long long x = (long long)((key >> 32) & 0xFFFF) + o[0];  // biased: legal in 0 .. 65535
+  const long long y = (long long)((key >> 16) & 0xFFFF) + o[1];
+  const long long z = (long long)(key & 0xFFFF) + o[2];
+  const bool ok = key >= 0 && x >= 0 && x < 65536 && y >= 0 && y < 65536 && z >= 0 && z < 65536;
+  P.cand[t] = ok ? (int64_t)(((key >> 48) << 48) | (x << 32) | (y << 16) | z) : (int64_t)-1;
+}
+
 // ---- sites -------------------------------------------------------------------------------------------------------------------------
 struct VoxelSitesParams {
   int N, tiles;
@@ -286,6 +312,21 @@ extern "C" int vdetr_sp_voxel_keys_f32(const vdetr_sp_voxel_keys_desc* d, vdetr_
   VoxelKeysParams P{d->N, d->B, d->stride, inv, d->points, d->offsets, d->keys};
   hipLaunchKernelGGL(voxel_keys_kernel, dim3((unsigned)ceil_div(d->N, 256)), dim3(256), 0, (hipStream_t)stream, P);
   return check_launch("sp_voxel_keys");
+}
+
+extern "C" int vdetr_sp_region_keys_i64(const vdetr_sp_region_keys_desc* d, vdetr_stream_t stream) {
+  VDETR_REQUIRE(d, "sp_region_keys: null descriptor");
+  VDETR_REQUIRE(d->N >= 0, "sp_region_keys: N=%d is negative", d->N);
+  VDETR_REQUIRE(d->K >= 0, "sp_region_keys: K=%d is negative", d->K);
+  const long long total = (long long)d->K * d->N;
+  VDETR_REQUIRE(total < (1LL << 31), "sp_region_keys: K=%d x N=%d candidates are more than 31 bits hold", d->K, d->N);
+  if (total == 0) return VDETR_OK;
+  VDETR_REQUIRE(d->keys, "sp_region_keys: keys is NULL with N=%d", d->N);
+  VDETR_REQUIRE(d->offsets, "sp_region_keys: offsets is NULL with K=%d", d->K);
+  VDETR_REQUIRE(d->cand, "sp_region_keys: cand is NULL with K=%d x N=%d", d->K, d->N);
+  RegionKeysParams P{d->N, total, d->keys, d->offsets, d->cand};
+  hipLaunchKernelGGL(region_keys_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P);
+  return check_launch("sp_region_keys");
 }
 
 extern "C" size_t vdetr_sp_voxel_sites_workspace_bytes(int N) {

@@ -24,7 +24,11 @@ MinkowskiEngine is NOT under /root/reference (un-vendored): semantics follow its
     without renormalisation (DESIGN 6.16: this package's own statement);
   * ``MinkowskiGlobal*Pooling`` write one row per scene of the batch on the origin map (keys (b, 0, 0, 0), ``tensor_stride`` 0; a scene
     without a site keeps a zero row), ``MinkowskiBroadcast*`` bring such rows back to the sites, ``MinkowskiLinear`` and the pointwise
-    layers take either kind of tensor (this package's own statement).
+    layers take either kind of tensor (DESIGN 6.17: this package's own statement);
+  * ``expand_coordinates=True`` in a convolution's or pooling's constructor writes every site the kernel reaches from an input site
+    (exactly the sites whose row of the kernel map is not empty); ``forward(x, coordinates)`` writes the sites the caller gives, a
+    SparseTensor's, a key tensor's or an integer [M, 4] list's, in key order with ``inverse_mapping`` back to the list (DESIGN 6.19:
+    this package's own statement).
 The ORDER of the sites of a MinkowskiEngine tensor is an implementation detail of its hash map; here it is ascending
 (batch, x, y, z).  Parity against the MinkowskiEngine binary is unpinned; ``oracle/sparse_oracle.py`` pins the arithmetic
 against torch's dense convolutions.
@@ -308,6 +312,32 @@ class CoordinateManager:
             child[:, :, 1:] += off[None]
             cache[key] = (torch.unique(S.pack_keys(child.reshape(-1, 4))), keys)  # the parent key tensor is kept alive
         return cache[key][0]
+
+    def expanded(self, keys, ts, out_ts, kernel_size, transposed):
+        """the sites of an expanding layer (``expand_coordinates=True``): every site u of the output lattice whose row of
+        the kernel map is not empty.  Not transposed (stride 1): u = v - offset * ts over the input sites v — the MINUS of the map's
+        u + offset * ts = v; transposed: u = v + offset * out_ts, the children of ``generated``.  One candidates launch, the sort and
+        the sites pass of ``sparse_ops.region_keys``, one host read.  A NEW, non-canonical key set, never written into ``self.keys``;
+        cached per (key set, strides, offsets, transposed) like the generated ones."""
+        region = _kernel_offsets(kernel_size)
+        cache = self.__dict__.setdefault("_expanded", {})
+        key = (keys.data_ptr(), ts, out_ts, region, transposed)
+        if key not in cache:
+            reg = torch.tensor(region, dtype=torch.int32)
+            offsets = (reg * out_ts if transposed else -reg * ts).to(keys.device)
+            cache[key] = (S.region_keys(keys, offsets), keys)  # the parent key tensor is kept alive
+        return cache[key][0]
+
+    def targets(self, coordinates):
+        """(keys, inverse) of ``sparse_ops.target_keys`` for caller-chosen output sites [M, 4] (``forward(x, coordinates)``), cached
+        per coordinate tensor and its version, bounded like the interpolation maps: it is geometry, and its size is read back once"""
+        cache = self.__dict__.setdefault("_targets", {})
+        key = (coordinates.data_ptr(), tuple(coordinates.shape), coordinates.dtype, coordinates._version)
+        if key not in cache:
+            if len(cache) >= 64:  # (coordinate tensors made anew for every call: keep the record bounded)
+                cache.clear()
+            cache[key] = S.target_keys(coordinates) + (coordinates,)  # the tensor is kept alive
+        return cache[key][:2]
 
     def union_map(self, a_keys, b_keys):
         """(u, row_a, row_b, src_a, src_b) of ``sparse_ops.union_map`` for two key sets of one stride: the sites of
@@ -690,18 +720,75 @@ def _refuse_origin(module, x):
                          f"{x.keys.shape[0]} rows): convolutions and local poolings need a tensor on sites; use MinkowskiLinear")
 
 
+def _expanding(module, expand_coordinates, stride):
+    """the ``expand_coordinates`` keyword of a layer's constructor -> bool.  The expansion of a strided, non-transposed layer is
+    not built: its candidates v - offset * ts mostly lie off the output lattice and need a filter."""
+    if expand_coordinates and not module.transposed and stride > 1:
+        raise NotImplementedError(f"{type(module).__name__}: expand_coordinates=True with stride {stride} is not built (the "
+                                  "expansion of a non-transposed layer exists at stride 1 only; the transposed layers expand at "
+                                  "any stride)")
+    return bool(expand_coordinates)
+
+
+def _given_sites(module, x, out_ts, coordinates):
+    """``forward(x, coordinates)``: the output sites the caller chose -> (keys, inverse).  A SparseTensor of the same coordinate
+    manager at the layer's output stride: its keys as they are.  A 1-D int64 tensor on the device: sorted unique keys, unchecked.
+    An integer [M, 4] tensor on the device: (batch, x, y, z) through ``cm.targets`` — rows in key order, duplicates merged,
+    ``inverse`` [M] int32 the row of every given coordinate (it becomes ``out.inverse_mapping``); the coordinates are taken as given,
+    nothing ties them to the output lattice.  Everything else is a ValueError that names what was given."""
+    name, cm = type(module).__name__, x.coordinate_manager
+    if module.expand_coordinates:
+        raise ValueError(f"{name}: coordinates together with expand_coordinates=True (the layer chooses its sites or the caller does)")
+    if isinstance(coordinates, SparseTensor):
+        if coordinates.coordinate_manager is not cm:
+            raise ValueError(f"{name}: coordinates is a SparseTensor of a different coordinate manager ({coordinates.coordinate_manager!r}, "
+                             f"the input's is {cm!r})")
+        if coordinates.tensor_stride != out_ts:
+            raise ValueError(f"{name}: coordinates has tensor stride {coordinates.tensor_stride}, the layer's output stride is {out_ts}")
+        return coordinates.keys, None
+    if not torch.is_tensor(coordinates):
+        raise ValueError(f"{name}: coordinates must be a SparseTensor, a key tensor or an integer [M, 4] tensor, not "
+                         f"{type(coordinates).__name__}")
+    given = f"{tuple(coordinates.shape)} {coordinates.dtype} on {coordinates.device}"
+    if not coordinates.is_cuda or coordinates.device != x.keys.device:
+        raise ValueError(f"{name}: coordinates must be on the input's device {x.keys.device} (it is {given})")
+    if coordinates.dtype == torch.int64 and coordinates.dim() == 1:
+        return coordinates, None
+    integer = coordinates.dtype in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8)
+    if not integer or coordinates.dim() != 2 or coordinates.shape[1] != 4:
+        raise ValueError(f"{name}: coordinates must be integer [M, 4] (batch, x, y, z) or int64 keys [M] (it is {given})")
+    return cm.targets(coordinates)
+
+
+def _site_tensor(features, out_ts, cm, keys, inverse):
+    """the output of a layer; ``inverse`` (coordinates given as a list): the row of every given coordinate, ``out.F[out.inverse_mapping
+    .long()]`` is in the caller's order"""
+    out = features if isinstance(features, SparseTensor) else SparseTensor(features, tensor_stride=out_ts, coordinate_manager=cm, keys=keys)
+    out.inverse_mapping = inverse
+    return out
+
+
 class MinkowskiConvolution(nn.Module):
-    """ME.MinkowskiConvolution(in, out, kernel_size, stride=1, dilation=1, bias=False, kernel_generator=None, dimension=3).
+    """ME.MinkowskiConvolution(in, out, kernel_size, stride=1, dilation=1, bias=False, kernel_generator=None,
+    expand_coordinates=False, dimension=3).
     ``kernel_size`` / ``dilation``: an int or one value per axis; ``kernel_generator`` (KernelGenerator) replaces both and picks
-    the region (cube, cross, custom).  ``kernel`` is [volume, in, out] in the generator's offset order."""
+    the region (cube, cross, custom).  ``kernel`` is [volume, in, out] in the generator's offset order.
+    Output sites: the input's at stride 1, ``cm.strided`` above it; the transposed form lands on the canonical sites of its output
+    stride.  ``expand_coordinates=True`` writes every site the kernel reaches from an input site instead — exactly the sites whose
+    row of the kernel map is not empty: u = v - offset * ts at stride 1 (the minus matters for even cubes and custom regions),
+    u = v + offset * out_ts transposed (the sites and, with the same kernel, the bits of MinkowskiGenerativeConvolutionTranspose).
+    Not built: the expansion of a non-transposed layer above stride 1 (NotImplementedError at construction).
+    ``forward(x, coordinates)`` writes the sites the caller gives (``_given_sites``: a SparseTensor, keys, or integer [M, 4]
+    coordinates); a target that no input reaches is a zero row (plus bias)."""
     transposed, generative = False, False
 
     def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False, kernel_generator=None,
-                 dimension=3):
+                 expand_coordinates=False, dimension=3):
         super().__init__()
         assert dimension == 3
         if kernel_generator is None:
-            kernel_generator = KernelGenerator(kernel_size, stride, dilation, is_transpose=self.transposed, dimension=dimension)
+            kernel_generator = KernelGenerator(kernel_size, stride, dilation, is_transpose=self.transposed,
+                                               expand_coordinates=bool(expand_coordinates), dimension=dimension)
         else:
             ks, dl = kernel_generator.kernel_size, kernel_generator.kernel_dilation
             kernel_size = ks[0] if len(set(ks)) == 1 else ks  # (a cubic size stays an int)
@@ -714,6 +801,7 @@ class MinkowskiConvolution(nn.Module):
             raise ValueError(f"stride {stride} together with dilation {kernel_generator.kernel_dilation}")
         self.in_channels, self.out_channels, self.kernel_size, self.stride = in_channels, out_channels, kernel_size, stride
         self.dilation, self.kernel_generator = dilation, kernel_generator
+        self.expand_coordinates = _expanding(self, expand_coordinates, stride)
         self._offsets = _Offsets(kernel_generator.scaled_offsets())
         kv = kernel_generator.kernel_volume
         # MinkowskiEngine keeps a plain [in, out] matrix only for the 1x1x1 stride-1 case
@@ -730,13 +818,18 @@ class MinkowskiConvolution(nn.Module):
         assert ts % self.stride == 0, "transposed convolution below tensor stride 1"
         return ts // self.stride
 
-    def forward(self, x):
+    def forward(self, x, coordinates=None):
         cm, ts = x.coordinate_manager, x.tensor_stride
         _refuse_origin(self, x)
         out_ts = self._out_stride(ts)
         w = self.kernel if self.kernel.dim() == 3 else self.kernel[None]
-        if self.generative:
+        inverse = None
+        if coordinates is not None:
+            out_keys, inverse = _given_sites(self, x, out_ts, coordinates)
+        elif self.generative:
             out_keys = cm.generated(x.keys, out_ts, self._offsets)
+        elif self.expand_coordinates:
+            out_keys = cm.expanded(x.keys, ts, out_ts, self._offsets, self.transposed)
         elif self.transposed:
             assert out_ts in cm.keys, "MinkowskiConvolutionTranspose needs existing sites at the output stride"
             out_keys = cm.keys[out_ts]
@@ -746,22 +839,26 @@ class MinkowskiConvolution(nn.Module):
         if _geometry_only():
             if hasattr(plan, "request_wgrad"):  # the weight-gradient chunk table of this layer's width: built with the geometry
                 plan.request_wgrad(w.shape[1], w.shape[2])
-            return SparseTensor(x.F.new_empty((out_keys.shape[0], self.out_channels)), tensor_stride=out_ts,
-                                coordinate_manager=cm, keys=out_keys)
+            return _site_tensor(x.F.new_empty((out_keys.shape[0], self.out_channels)), out_ts, cm, out_keys, inverse)
         if _conv_bn_fusable(self, x.F, plan=plan, cout=self.out_channels):
-            return SparseTensor.pending(_PendingConv(S.pair_products(x.F, w, plan), plan.slot, self.out_channels, self.bias),
-                                        out_ts, cm, out_keys)
+            return _site_tensor(SparseTensor.pending(_PendingConv(S.pair_products(x.F, w, plan), plan.slot, self.out_channels, self.bias),
+                                                     out_ts, cm, out_keys), out_ts, cm, out_keys, inverse)
         f = S.sparse_conv(x.F, w, nbr, inv, plan)
         if self.bias is not None:
             f = f + self.bias
-        return SparseTensor(f, tensor_stride=out_ts, coordinate_manager=cm, keys=out_keys)
+        return _site_tensor(f, out_ts, cm, out_keys, inverse)
 
 
 class MinkowskiConvolutionTranspose(MinkowskiConvolution):
+    """ME.MinkowskiConvolutionTranspose: onto the canonical sites of the output stride; with ``expand_coordinates=True`` onto the
+    children u = v + offset * out_ts of every input site (any stride the class accepts), the key set and bits of
+    MinkowskiGenerativeConvolutionTranspose; ``forward(x, coordinates)`` onto given sites, e.g. a pruned tensor's."""
     transposed = True
 
 
 class MinkowskiGenerativeConvolutionTranspose(MinkowskiConvolution):
+    """ME.MinkowskiGenerativeConvolutionTranspose: every child site, through ``CoordinateManager.generated`` (an ATen composition;
+    profiles/expand_bench.txt holds both sides for the day it moves onto ``expanded``)."""
     transposed, generative = True, True
 
 
@@ -773,13 +870,18 @@ class MinkowskiChannelwiseConvolution(nn.Module):
     stride: the coordinate manager's cached map, shared with them.  One HIP launch forward, one for the input gradient, two for the
     kernel / bias gradients (``sparse_ops.channelwise_conv``).
     Not built: a transposed channelwise convolution (MinkowskiEngine has none), dimension 4, double backward, and a fused
-    convolution -> BatchNorm -> activation inference form (a following MinkowskiBatchNorm runs its own launch)."""
+    convolution -> BatchNorm -> activation inference form (a following MinkowskiBatchNorm runs its own launch).
+    ``expand_coordinates=True`` (stride 1 only: NotImplementedError above it) and ``forward(x, coordinates)`` choose the output sites
+    as in MinkowskiConvolution."""
+    transposed = False
 
-    def __init__(self, in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, kernel_generator=None, dimension=3):
+    def __init__(self, in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, kernel_generator=None,
+                 expand_coordinates=False, dimension=3):
         super().__init__()
         assert dimension == 3
         if kernel_generator is None:
-            kernel_generator = KernelGenerator(kernel_size, stride, dilation, is_transpose=False, dimension=dimension)
+            kernel_generator = KernelGenerator(kernel_size, stride, dilation, is_transpose=False,
+                                               expand_coordinates=bool(expand_coordinates), dimension=dimension)
         else:
             ks, dl = kernel_generator.kernel_size, kernel_generator.kernel_dilation
             kernel_size = ks[0] if len(set(ks)) == 1 else ks  # (a cubic size stays an int)
@@ -792,6 +894,7 @@ class MinkowskiChannelwiseConvolution(nn.Module):
             raise ValueError(f"stride {stride} together with dilation {kernel_generator.kernel_dilation}")
         self.in_channels, self.out_channels, self.kernel_size, self.stride = in_channels, in_channels, kernel_size, stride
         self.dilation, self.kernel_generator = dilation, kernel_generator
+        self.expand_coordinates = _expanding(self, expand_coordinates, stride)
         self._offsets = _Offsets(kernel_generator.scaled_offsets())
         kv = kernel_generator.kernel_volume
         self.kernel = nn.Parameter(torch.empty(kv, in_channels))
@@ -800,17 +903,22 @@ class MinkowskiChannelwiseConvolution(nn.Module):
         with torch.no_grad():
             self.kernel.uniform_(-stdv, stdv)
 
-    def forward(self, x):
+    def forward(self, x, coordinates=None):
         cm, ts = x.coordinate_manager, x.tensor_stride
         _refuse_origin(self, x)
         out_ts = ts * self.stride
-        out_keys = x.keys if out_ts == ts else cm.strided(x.keys, ts, out_ts)
+        inverse = None
+        if coordinates is not None:
+            out_keys, inverse = _given_sites(self, x, out_ts, coordinates)
+        elif self.expand_coordinates:
+            out_keys = cm.expanded(x.keys, ts, out_ts, self._offsets, False)
+        else:
+            out_keys = x.keys if out_ts == ts else cm.strided(x.keys, ts, out_ts)
         nbr, inv = cm.pool_map(x.keys, out_keys, ts, out_ts, self._offsets, False)
         if _geometry_only():
-            return SparseTensor(x.F.new_empty((out_keys.shape[0], self.in_channels)), tensor_stride=out_ts, coordinate_manager=cm,
-                                keys=out_keys)
+            return _site_tensor(x.F.new_empty((out_keys.shape[0], self.in_channels)), out_ts, cm, out_keys, inverse)
         f = S.channelwise_conv(x.F.contiguous(), self.kernel, nbr, inv, self.bias)
-        return SparseTensor(f, tensor_stride=out_ts, coordinate_manager=cm, keys=out_keys)
+        return _site_tensor(f, out_ts, cm, out_keys, inverse)
 
 
 class MinkowskiBatchNorm(nn.Module):
@@ -862,14 +970,18 @@ class MinkowskiInstanceNorm(nn.Module):
 
 class _MinkowskiPooling(nn.Module):
     """Pooling over a kernel region: the output sites are those of a convolution of the same kernel and stride (the same sites
-    at stride 1, ``cm.strided`` above it), the map is the coordinate manager's, shared with such a convolution."""
+    at stride 1, ``cm.strided`` above it), the map is the coordinate manager's, shared with such a convolution.
+    ``expand_coordinates=True``: every site the kernel reaches from an input site (non-transposed at stride 1 only, NotImplementedError
+    above it; the transposed poolings at any stride); ``forward(x, coordinates)``: the sites the caller gives, a target without a
+    neighbour holding what ``sparse_pool`` writes for an empty row (0 for sum and avg).  Both as in MinkowskiConvolution; DESIGN 6.19."""
     mode, transposed = None, False
 
-    def __init__(self, kernel_size, stride=1, dilation=1, kernel_generator=None, dimension=3):
+    def __init__(self, kernel_size, stride=1, dilation=1, kernel_generator=None, expand_coordinates=False, dimension=3):
         super().__init__()
         assert dimension == 3
         if kernel_generator is None:
-            kernel_generator = KernelGenerator(kernel_size, stride, dilation, is_transpose=self.transposed, dimension=dimension)
+            kernel_generator = KernelGenerator(kernel_size, stride, dilation, is_transpose=self.transposed,
+                                               expand_coordinates=bool(expand_coordinates), dimension=dimension)
         if isinstance(stride, (tuple, list)):
             if any(s != stride[0] for s in stride):
                 raise NotImplementedError(f"stride {stride}: one stride for all three axes only")
@@ -877,29 +989,35 @@ class _MinkowskiPooling(nn.Module):
         if stride > 1 and max(kernel_generator.kernel_dilation) > 1:
             raise ValueError(f"stride {stride} together with dilation {kernel_generator.kernel_dilation}")
         self.kernel_size, self.stride, self.dilation, self.kernel_generator = kernel_size, stride, dilation, kernel_generator
+        self.expand_coordinates = _expanding(self, expand_coordinates, stride)
         self._offsets = _Offsets(kernel_generator.scaled_offsets())
 
-    def _sites(self, x):
+    def _sites(self, x, coordinates=None):
+        """(output stride, output keys, the inverse map of coordinates given as a list or None)"""
         cm, ts = x.coordinate_manager, x.tensor_stride
         if not self.transposed:
             out_ts = ts * self.stride
-            return out_ts, (x.keys if out_ts == ts else cm.strided(x.keys, ts, out_ts))
-        assert ts % self.stride == 0, "transposed pooling below tensor stride 1"
-        out_ts = ts // self.stride
+        else:
+            assert ts % self.stride == 0, "transposed pooling below tensor stride 1"
+            out_ts = ts // self.stride
+        if coordinates is not None:
+            return (out_ts,) + tuple(_given_sites(self, x, out_ts, coordinates))
+        if self.expand_coordinates:
+            return out_ts, cm.expanded(x.keys, ts, out_ts, self._offsets, self.transposed), None
+        if not self.transposed:
+            return out_ts, (x.keys if out_ts == ts else cm.strided(x.keys, ts, out_ts)), None
         assert out_ts in cm.keys, f"{type(self).__name__} needs existing sites at the output stride"
-        return out_ts, cm.keys[out_ts]
+        return out_ts, cm.keys[out_ts], None
 
-    def forward(self, x):
+    def forward(self, x, coordinates=None):
         cm, ts = x.coordinate_manager, x.tensor_stride
         _refuse_origin(self, x)
-        out_ts, out_keys = self._sites(x)
+        out_ts, out_keys, inverse = self._sites(x, coordinates)
         if _geometry_only():
             cm.kernel_map(x.keys, out_keys, ts, out_ts, self._offsets, self.transposed)
-            return SparseTensor(x.F.new_empty((out_keys.shape[0], x.F.shape[1])), tensor_stride=out_ts, coordinate_manager=cm,
-                                keys=out_keys)
+            return _site_tensor(x.F.new_empty((out_keys.shape[0], x.F.shape[1])), out_ts, cm, out_keys, inverse)
         nbr, inv = cm.pool_map(x.keys, out_keys, ts, out_ts, self._offsets, self.transposed)
-        return SparseTensor(S.sparse_pool(x.F.contiguous(), nbr, inv, self.mode), tensor_stride=out_ts, coordinate_manager=cm,
-                            keys=out_keys)
+        return _site_tensor(S.sparse_pool(x.F.contiguous(), nbr, inv, self.mode), out_ts, cm, out_keys, inverse)
 
 
 class MinkowskiSumPooling(_MinkowskiPooling):

@@ -1363,6 +1363,38 @@ def voxel_map_coords(coords):
     return _voxel_sites(keys, None)
 
 
+def region_keys(keys, offsets):
+    """The sites a kernel region reaches from a key set: sorted unique ``keys`` [N] int64 and ``offsets`` [K, 3]
+    int32, both on the device, the offsets already scaled and signed -> the sorted unique int64 keys of every ``site + offset``.
+    One candidates launch (csrc/sparse_voxel.hip: no atomics, no memset), the stable library sort, the two sites launches of
+    ``voxel_map`` and their ONE host read of eight bytes (the site count and the range flag).  A candidate outside the 16-bit
+    fields raises the ValueError of ``voxel_map``."""
+    L.require_gpu(keys, "keys")
+    L.require_gpu(offsets, "offsets")
+    if keys.dtype != torch.int64 or keys.dim() != 1:
+        raise RuntimeError(f"keys must be a 1-D int64 tensor (it is {tuple(keys.shape)} {keys.dtype})")
+    if offsets.dtype != torch.int32 or offsets.dim() != 2 or offsets.shape[1] != 3:
+        raise RuntimeError(f"offsets must be a [K, 3] int32 tensor (it is {tuple(offsets.shape)} {offsets.dtype})")
+    keys, offsets = keys.contiguous(), offsets.contiguous()
+    N, K = keys.shape[0], offsets.shape[0]
+    if K * N >= 2 ** 31:
+        raise RuntimeError(f"region_keys: {K} offsets x {N} sites are more candidates than 31 bits hold")
+    cand = torch.empty(K * N, dtype=torch.int64, device=keys.device)
+    if K * N:
+        d = L.SpRegionKeysDesc()
+        d.N, d.K, d.keys, d.offsets, d.cand = N, K, keys.data_ptr(), offsets.data_ptr(), cand.data_ptr()
+        L.check(L.lib().vdetr_sp_region_keys_i64(ctypes.byref(d), L.stream_ptr()), "sp_region_keys")
+    return _voxel_sites(cand, None).sites.clone()  # (the sites pass writes into a buffer of K * N: keep the M that are sites)
+
+
+def target_keys(coordinates):
+    """Caller-chosen output sites: integer coordinates [M, 4] (batch, x, y, z) on the device -> (keys sorted and unique, inverse
+    [M] int32 = the key row of every given coordinate).  ``voxel_map_coords`` under the name of its use here: one keys launch,
+    the sort, the sites pass, one host read."""
+    vm = voxel_map_coords(coordinates)
+    return vm.sites, vm.inverse
+
+
 def _require_vmap(vmap, n=None):
     if not isinstance(vmap, tuple) or len(vmap) != 5:
         raise RuntimeError("vmap must be the (sites, inverse, first, seg, order) of voxel_map / voxel_map_coords")
