@@ -459,11 +459,11 @@ typedef struct vdetr_addln_grads {
   float* d_x;                  /* [rows, C] total gradient of y = gradient of x */
   float* d_r;                  /* [rows, C] gradient of r (d_x through the dropout mask), or NULL */
   float *d_gamma, *d_beta, *d_gamma2, *d_beta2; /* [C]; the *2 pair only with d_out2 */
-  float* partials;             /* vdetr_add_ln_bwd_workspace_bytes() of scratch */
+  float* partials;             /* vdetr_add_ln_bwd_workspace_bytes() of scratch, 16-B aligned */
 } vdetr_addln_grads;
 
 int vdetr_add_ln_fwd_f32(const vdetr_addln_desc* d, vdetr_stream_t stream);
-size_t vdetr_add_ln_bwd_workspace_bytes(const vdetr_addln_desc* d);
+size_t vdetr_add_ln_bwd_workspace_bytes(const vdetr_addln_desc* d); /* 0 for NULL, rows <= 0 or C <= 0 */
 int vdetr_add_ln_bwd_f32(const vdetr_addln_desc* d, const vdetr_addln_grads* g, vdetr_stream_t stream);
 /* With d_gamma == d_beta == NULL vdetr_add_ln_bwd_f32 only leaves the per-workgroup partial sums in `partials`
  * (nparts = workspace bytes / (4 * C * 4) rows of [4][C]); this call then reduces the partials of SEVERAL backward passes
@@ -666,8 +666,9 @@ typedef struct vdetr_pack_entry {
 int vdetr_colsum_f32(const float* x, float* out, int rows, int cols, long row_stride, vdetr_stream_t stream);
 /* out[i][c] = sum_r x[i * item_stride + r * row_stride + c] for n matrices: one launch, or two for tall matrices with few columns
  * (partial sums of row ranges into `workspace`, vdetr_colsum_workspace_bytes(n, rows, cols) bytes, then their sum; without a workspace:
- * one launch, unsplit).  Fixed summation order: bit-reproducible. */
-size_t vdetr_colsum_workspace_bytes(int n, int rows, int cols);
+ * one launch, unsplit; a workspace that is too small or not 16-B aligned is not used: the same one launch).  Fixed summation
+ * order: bit-reproducible. */
+size_t vdetr_colsum_workspace_bytes(int n, int rows, int cols); /* 0: no split (also for any argument <= 0) */
 int vdetr_colsum_batched_f32(const float* x, float* out, int n, int rows, int cols, long row_stride, long item_stride,
                              void* workspace, size_t workspace_bytes, vdetr_stream_t stream);
 /* the same for n separately allocated matrices: `items` is a DEVICE array of n pointers (16-byte aligned; cols, row_stride % 4 == 0) */
@@ -1362,9 +1363,9 @@ int vdetr_sp_wgrad_reduce_f32(const float* partials, const int32_t* seg, int K, 
  *   nbr [K][nout] (vdetr_sp_kernel_map_i32)  ->  pin, pout [capacity K*nout; the first P entries are written]
  *                                                slot [K][nout], islot [K][nin]  (pair index or -1)
  *                                                counts [K+1] (device): pairs per offset, counts[K] = P
- * workspace: vdetr_sp_pair_plan_workspace_ints(K, nout) ints.  No host synchronisation: the caller copies `counts` back
+ * workspace: vdetr_sp_pair_plan_workspace_ints(K, nout) ints, 4-B aligned.  No host synchronisation: the caller copies `counts` back
  * when it needs the sizes (v-detr_amd/sparse_ops.py:PairPlan).  Deterministic (ranks, no atomics). */
-int vdetr_sp_pair_plan_workspace_ints(int K, int nout);
+int vdetr_sp_pair_plan_workspace_ints(int K, int nout); /* K <= 0 gives 0, nout <= 0 counts as one row */
 int vdetr_sp_pair_plan_i32(const int32_t* nbr, int K, int nout, int nin, int32_t* pin, int32_t* pout, int32_t* slot,
                            int32_t* islot, int32_t* counts, int32_t* workspace, vdetr_stream_t stream);
 
@@ -1382,9 +1383,9 @@ typedef struct vdetr_spbn_desc {
   float *running_mean, *running_var;        /* may be NULL in training mode */
   int64_t* num_batches_tracked;             /* optional */
   float *y, *save_mean, *save_invstd;
-  void* workspace;
+  void* workspace; /* vdetr_sp_bn_workspace_bytes(N, C), 16-B aligned */
 } vdetr_spbn_desc;
-size_t vdetr_sp_bn_workspace_bytes(int N, int C);
+size_t vdetr_sp_bn_workspace_bytes(int N, int C); /* grows with N; N <= 0 counts as one row, C <= 0 gives 0 */
 int vdetr_sp_bn_act_fwd_f32(const vdetr_spbn_desc* d, vdetr_stream_t stream);
 /* dx [N,C] (or NULL), dresidual [N,C] (or NULL: = dy * act'), dgamma / dbeta [C] (or NULL) from dy [N,C], the forward's x, y,
  * save_mean, save_invstd */
@@ -1450,7 +1451,7 @@ typedef struct vdetr_sp_cwconv_desc {
   const float* w;     /* [K,C] (forward, dgrad) */
   const float* bias;  /* [C] or NULL (forward) */
   float* y;           /* [nout,C] (forward) */
-  void* workspace;    /* vdetr_sp_cwconv_workspace_bytes(K, nout, C); wgrad only */
+  void* workspace;    /* vdetr_sp_cwconv_workspace_bytes(K, nout, C), 16-B aligned; wgrad only */
 } vdetr_sp_cwconv_desc;
 int vdetr_sp_cwconv_chunk_rows(int nout);
 size_t vdetr_sp_cwconv_workspace_bytes(int K, int nout, int C); /* 0 for arguments outside the ranges above */
@@ -1474,9 +1475,9 @@ typedef struct vdetr_sp_inorm_desc {
   const int32_t* seg;
   const float *gamma, *beta;
   float *y, *save_mean, *save_invstd;
-  void* workspace;
+  void* workspace; /* vdetr_sp_inorm_workspace_bytes(N, C, nseg), 16-B aligned */
 } vdetr_sp_inorm_desc;
-size_t vdetr_sp_inorm_workspace_bytes(int N, int C, int nseg);
+size_t vdetr_sp_inorm_workspace_bytes(int N, int C, int nseg); /* grows with N and nseg; negative arguments count as 0 */
 int vdetr_sp_inorm_fwd_f32(const vdetr_sp_inorm_desc* d, vdetr_stream_t stream);
 /* dx [N,C] (or NULL), dgamma / dbeta [C] (or NULL) from dy [N,C], the forward's x, save_mean, save_invstd (y is not read) */
 int vdetr_sp_inorm_bwd_f32(const vdetr_sp_inorm_desc* d, const float* dy, float* dx, float* dgamma, float* dbeta,
@@ -1695,7 +1696,7 @@ typedef struct vdetr_sp_global_pool_desc {
   const int32_t* seg;
   float* y;
   int32_t* arg;
-  void* workspace; /* vdetr_sp_global_pool_workspace_bytes(N, C, nseg); forward only */
+  void* workspace; /* vdetr_sp_global_pool_workspace_bytes(N, C, nseg), 16-B aligned; forward only */
 } vdetr_sp_global_pool_desc;
 int vdetr_sp_global_chunk_rows(int N);
 size_t vdetr_sp_global_pool_workspace_bytes(int N, int C, int nseg);
@@ -1719,7 +1720,7 @@ typedef struct vdetr_sp_broadcast_desc {
   const int32_t* seg;
   const float* residual;
   float* y;
-  void* workspace; /* vdetr_sp_broadcast_workspace_bytes(N, Cg, nseg); backward with dg only */
+  void* workspace; /* vdetr_sp_broadcast_workspace_bytes(N, Cg, nseg), 16-B aligned; backward with dg only */
 } vdetr_sp_broadcast_desc;
 size_t vdetr_sp_broadcast_workspace_bytes(int N, int Cg, int nseg);
 int vdetr_sp_broadcast_fwd_f32(const vdetr_sp_broadcast_desc* d, vdetr_stream_t stream);
@@ -1735,7 +1736,7 @@ typedef struct vdetr_sp_se_gate_desc {
   const int32_t* seg;
   const float *w1, *b1, *w2, *b2;
   float* gate;
-  void* workspace;
+  void* workspace; /* vdetr_sp_global_pool_workspace_bytes(N, C, nseg), 16-B aligned */
 } vdetr_sp_se_gate_desc;
 int vdetr_sp_se_gate_f32(const vdetr_sp_se_gate_desc* d, vdetr_stream_t stream);
 
@@ -1783,9 +1784,9 @@ typedef struct vdetr_heads_desc {
   float *pre1, *h1, *pre2, *h2;                                 /* [B, G*256, N] */
   float *save_mean1, *save_invstd1, *save_mean2, *save_invstd2; /* [G*256] */
   float* y;                /* [B, G, rows, N] */
-  void* workspace;
+  void* workspace;         /* vdetr_heads_workspace_bytes(B, N, G), 16-B aligned */
 } vdetr_heads_desc;
-size_t vdetr_heads_workspace_bytes(int B, int N, int G);
+size_t vdetr_heads_workspace_bytes(int B, int N, int G); /* 0 unless B, N and G are positive */
 int vdetr_heads_fwd_f32(const vdetr_heads_desc* d, vdetr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------

@@ -259,6 +259,7 @@ extern "C" int vdetr_add_ln_fwd_f32(const vdetr_addln_desc* d, vdetr_stream_t st
 extern "C" int vdetr_add_ln_bwd_f32(const vdetr_addln_desc* d, const vdetr_addln_grads* g, vdetr_stream_t stream) {
   if (int e = addln_check(d, "add_ln_bwd")) return e;
   VDETR_REQUIRE(g && g->d_x && g->partials && (g->d_gamma == nullptr) == (g->d_beta == nullptr), "add_ln_bwd: null pointer");
+  VDETR_REQUIRE_WORKSPACE_ALIGNED("add_ln_bwd", "partials", g->partials, 16);
   VDETR_REQUIRE(g->d_out || g->d_out2 || g->d_y, "add_ln_bwd: no incoming gradient");
   VDETR_REQUIRE(!g->d_out2 || (d->gamma2 && (g->d_gamma == nullptr || (g->d_gamma2 && g->d_beta2))),
                 "add_ln_bwd: d_out2 needs gamma2 and its gradient buffers");

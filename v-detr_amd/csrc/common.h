@@ -32,6 +32,12 @@ inline int check_launch(const char* what) {
     }                                 \
   } while (0)
 
+// a workspace that comes as a bare pointer (no byte count) and is read as float4 / int4 (`align` 16) or int (4); NULL passes:
+// whether it is needed at all is the launch's own check
+inline bool workspace_aligned(const void* p, unsigned align) { return (((uintptr_t)p) & (uintptr_t)(align - 1)) == 0; }
+#define VDETR_REQUIRE_WORKSPACE_ALIGNED(op, field, p, align) \
+  VDETR_REQUIRE(vdetr::workspace_aligned((p), (align)), "%s: %s must be %u-B aligned", (op), (field), (unsigned)(align))
+
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 int device_cu_count();  // core.hip

@@ -18,6 +18,14 @@ namespace vdetr {
 
 constexpr int kBnRowsMin = 16, kBnRowsMax = 128;  // rows per workgroup: chosen so that a table gives >= ~1000 workgroups
 static inline int bn_rows(int N) { int r = N / 1024; r = r < kBnRowsMin ? kBnRowsMin : r > kBnRowsMax ? kBnRowsMax : r; return (r + 15) / 16 * 16; }
+// an upper bound of ceil(N / bn_rows(N)) that grows with N (the count itself drops where the rows step up: 1088 workgroups at
+// N = 17407, 544 at 17408).  Rows of 16: ceil(N / 16) <= 1088; rows of 32 .. 112: N < (rows + 1) * 1024, so at most
+// 1024 + ceil(1023 / rows) <= 1056 workgroups; rows of 128: ceil(N / 128).
+static inline size_t bn_block_bound(int N) {
+  const long by16 = ((long)N + 15) / 16, by128 = ((long)N + 127) / 128;
+  const long low = by16 < 1088 ? by16 : 1088;
+  return (size_t)(low > by128 ? low : by128);
+}
 
 // d act / d pre-activation from the OUTPUT y
 __device__ __forceinline__ f32x4 bn_act_grad(f32x4 dy, f32x4 y, int act) {
@@ -169,6 +177,7 @@ static int fill(const vdetr_spbn_desc* d, SpBnParams* P, const char* op) {
   VDETR_REQUIRE(d && d->N >= 0 && d->C > 0, "%s: bad descriptor", op);
   VDETR_REQUIRE(d->C % 4 == 0 && d->C <= 1024, "%s: C=%d must be a multiple of 4 and <= 1024", op, d->C);
   VDETR_REQUIRE(d->act >= 0 && d->act <= 2, "%s: act %d", op, d->act);
+  VDETR_REQUIRE_WORKSPACE_ALIGNED(op, "workspace", d->workspace, 16);
   P->N = d->N; P->C = d->C; P->act = d->act; P->training = d->training; P->rows = bn_rows(d->N); P->nblk = ceil_div(d->N, P->rows);
   P->eps = d->eps; P->momentum = d->momentum;
   P->x = d->x; P->gamma = d->gamma; P->beta = d->beta; P->residual = d->residual;
@@ -184,7 +193,8 @@ static int fill(const vdetr_spbn_desc* d, SpBnParams* P, const char* op) {
 using namespace vdetr;
 
 extern "C" size_t vdetr_sp_bn_workspace_bytes(int N, int C) {
-  return ((size_t)ceil_div(N > 0 ? N : 1, bn_rows(N)) * 3 + 2) * C * sizeof(float);  // partials + the backward's two sums
+  if (C <= 0) return 0;
+  return (bn_block_bound(N > 0 ? N : 1) * 3 + 2) * (size_t)C * sizeof(float);  // partials + the backward's two sums
 }
 
 extern "C" int vdetr_sp_bn_act_fwd_f32(const vdetr_spbn_desc* d, vdetr_stream_t stream) {

@@ -21,6 +21,12 @@ namespace vdetr {
 
 static inline int inorm_round16(int r) { return (r + 15) / 16 * 16; }
 static inline int inorm_stat_rows(int N) { const int r = (N + 63) / 64; return inorm_round16(r < 16 ? 16 : r); }
+// an upper bound of ceil(N / inorm_stat_rows(N)) that grows with N (the count itself drops where the rows step up: 64 chunks at
+// N = 1024, 33 at 1025): the rows are at least 16 and at least N / 64
+static inline size_t inorm_chunk_bound(int N) {
+  const long by16 = ((long)N + 15) / 16;
+  return (size_t)(by16 < 64 ? by16 : 64);
+}
 static inline int inorm_apply_rows(int N) { int r = N / 1024; r = r < 16 ? 16 : r > 128 ? 128 : r; return inorm_round16(r); }
 
 struct SpInParams {
@@ -181,6 +187,7 @@ static int in_fill(const vdetr_sp_inorm_desc* d, SpInParams* P, const char* op) 
   VDETR_REQUIRE(d->C > 0 && d->C % 4 == 0 && d->C <= 1024, "%s: C=%d must be a positive multiple of 4 and <= 1024", op, d->C);
   VDETR_REQUIRE(d->N >= 0, "%s: N=%d is negative", op, d->N);
   VDETR_REQUIRE(d->nseg >= 0, "%s: nseg=%d is negative", op, d->nseg);
+  VDETR_REQUIRE_WORKSPACE_ALIGNED(op, "workspace", d->workspace, 16);
   P->N = d->N; P->C = d->C; P->nseg = d->nseg; P->eps = d->eps;
   P->rows_s = inorm_stat_rows(d->N); P->rows_a = inorm_apply_rows(d->N);
   P->x = d->x; P->seg = d->seg; P->gamma = d->gamma; P->beta = d->beta;
@@ -196,7 +203,7 @@ extern "C" size_t vdetr_sp_inorm_workspace_bytes(int N, int C, int nseg) {
   if (N < 0) N = 0;
   if (nseg < 0) nseg = 0;
   if (C < 0) C = 0;
-  return ((size_t)ceil_div(N, inorm_stat_rows(N)) + (size_t)nseg + 1) * 3 * (size_t)C * sizeof(float);
+  return (inorm_chunk_bound(N) + (size_t)nseg + 1) * 3 * (size_t)C * sizeof(float);
 }
 
 extern "C" int vdetr_sp_inorm_fwd_f32(const vdetr_sp_inorm_desc* d, vdetr_stream_t stream) {

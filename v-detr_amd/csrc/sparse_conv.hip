@@ -855,7 +855,7 @@ extern "C" int vdetr_sp_wgrad_reduce_f32(const float* partials, const int32_t* s
   return check_launch("sp_wgrad_reduce");
 }
 
-extern "C" int vdetr_sp_pair_plan_workspace_ints(int K, int nout) { return K * ceil_div(nout > 0 ? nout : 1, 256); }
+extern "C" int vdetr_sp_pair_plan_workspace_ints(int K, int nout) { return K > 0 ? K * ceil_div(nout > 0 ? nout : 1, 256) : 0; }
 
 extern "C" int vdetr_sp_pair_plan_i32(const int32_t* nbr, int K, int nout, int nin, int32_t* pin, int32_t* pout, int32_t* slot,
                                       int32_t* islot, int32_t* counts, int32_t* workspace, vdetr_stream_t stream) {
@@ -864,6 +864,7 @@ extern "C" int vdetr_sp_pair_plan_i32(const int32_t* nbr, int K, int nout, int n
   hipStream_t st = (hipStream_t)stream;
   if (nout == 0) return hipMemsetAsync(counts, 0, sizeof(int32_t) * (K + 1), st) == hipSuccess ? VDETR_OK : VDETR_ERR_LAUNCH;
   VDETR_REQUIRE(nbr && pin && pout && slot && (islot || nin == 0) && workspace, "sp_pair_plan: null pointer");
+  VDETR_REQUIRE_WORKSPACE_ALIGNED("sp_pair_plan", "workspace", workspace, 4);
   const int nb = ceil_div(nout, 256);
   if (nin > 0 && hipMemsetAsync(islot, 0xFF, sizeof(int32_t) * (size_t)K * nin, st) != hipSuccess) return VDETR_ERR_LAUNCH;
   hipLaunchKernelGGL(sp_plan_count_kernel, dim3(nb, K), dim3(256), 0, st, nbr, nout, nb, workspace);

@@ -247,6 +247,7 @@ extern "C" int vdetr_sp_cwconv_wgrad_f32(const vdetr_sp_cwconv_desc* d, const fl
   const char* op = "sp_cwconv_wgrad";
   if (int e = cw_check(d, op)) return e;
   VDETR_REQUIRE(dw || db, "%s: dw is NULL and db is NULL (one of them is wanted)", op);
+  VDETR_REQUIRE_WORKSPACE_ALIGNED(op, "workspace", d->workspace, 16);
   const int C4 = d->C / 4;
   const int rows = cw_chunk_rows(d->nout);
   const int chunks = ceil_div(d->nout, rows);

@@ -437,6 +437,7 @@ extern "C" int vdetr_sp_global_pool_fwd_f32(const vdetr_sp_global_pool_desc* d, 
   VDETR_REQUIRE(d->y, "%s: y is NULL with nseg=%d", op, d->nseg);
   VDETR_REQUIRE(d->mode != VDETR_POOL_MAX || d->arg, "%s: arg is NULL with mode=VDETR_POOL_MAX", op);
   VDETR_REQUIRE(d->workspace, "%s: workspace is NULL (vdetr_sp_global_pool_workspace_bytes)", op);
+  VDETR_REQUIRE_WORKSPACE_ALIGNED(op, "workspace", d->workspace, 16);
   const int grid = ceil_div(d->N, P.rows_p) + d->nseg;
   if (d->mode == VDETR_POOL_MAX) {
     hipLaunchKernelGGL(sg_pool_max_part_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, P);
@@ -490,6 +491,7 @@ extern "C" int vdetr_sp_broadcast_bwd_f32(const vdetr_sp_broadcast_desc* d, cons
   VDETR_REQUIRE(d->mode != VDETR_BCAST_MUL || !dx || d->g, "%s: g is NULL (dx of mode=VDETR_BCAST_MUL reads it)", op);
   VDETR_REQUIRE(d->mode != VDETR_BCAST_MUL || !dg || d->x, "%s: x is NULL (dg of mode=VDETR_BCAST_MUL reads it)", op);
   VDETR_REQUIRE(!dg || d->workspace, "%s: workspace is NULL (vdetr_sp_broadcast_workspace_bytes)", op);
+  if (dg) VDETR_REQUIRE_WORKSPACE_ALIGNED(op, "workspace", d->workspace, 16);
   if (dg) P.rows = sg_chunk_rows(d->N);  // the sweep leaves partials: the large chunks of the fold
   const int grid = ceil_div(d->N, P.rows) + d->nseg;
   hipLaunchKernelGGL(sg_bcast_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, P, dy, dx, dg ? 1 : 0);
@@ -514,6 +516,7 @@ extern "C" int vdetr_sp_se_gate_f32(const vdetr_sp_se_gate_desc* d, vdetr_stream
   VDETR_REQUIRE(d->w1 && d->w2, "%s: %s is NULL", op, d->w1 ? "w2" : "w1");
   VDETR_REQUIRE(d->gate, "%s: gate is NULL with nseg=%d", op, d->nseg);
   VDETR_REQUIRE(d->workspace, "%s: workspace is NULL (vdetr_sp_global_pool_workspace_bytes)", op);
+  VDETR_REQUIRE_WORKSPACE_ALIGNED(op, "workspace", d->workspace, 16);
   SgPoolParams P{};
   P.S = SgSeg{d->N, d->nseg, d->seg};
   P.C = d->C; P.mode = VDETR_POOL_AVG; P.rows_p = sg_chunk_rows(d->N); P.rows_s = sg_stream_rows(d->N);

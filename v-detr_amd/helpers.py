@@ -22,7 +22,7 @@ def colsum_batched(x3d):
     n, rows, cols = x3d.shape
     lib = L.lib()
     need = lib.vdetr_colsum_workspace_bytes(n, rows, cols)
-    ws = torch.empty(need, dtype=torch.uint8, device=x3d.device) if need else None  # (tall, few columns: partial sums of row ranges)
+    ws = L.workspace(need, x3d.device) if need else None  # (tall, few columns: partial sums of row ranges)
     out = torch.empty((n, cols), dtype=x3d.dtype, device=x3d.device)
     L.check(lib.vdetr_colsum_batched_f32(L.ptr(x3d), L.ptr(out), n, rows, cols, ctypes.c_long(x3d.stride(1)), ctypes.c_long(x3d.stride(0)),
                                          L.ptr(ws), need, L.stream_ptr()), "colsum_batched")
@@ -77,7 +77,7 @@ def _wgrad_ptrs(group, need_w, need_b):
         lib = L.lib()
         dB = torch.empty((n, out_f), dtype=torch.float32, device=dev)
         need = lib.vdetr_colsum_workspace_bytes(n, rows, out_f)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        ws = L.workspace(need, dev) if need else None
         L.check(lib.vdetr_colsum_ptrs_f32(ctypes.c_void_p(base + 8 * n), L.ptr(dB), n, rows, out_f, ctypes.c_long(g0.stride(0)), L.ptr(ws), need,
                                           L.stream_ptr()), "colsum_ptrs")
     if dW is not None:

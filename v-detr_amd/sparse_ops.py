@@ -322,7 +322,7 @@ class PairPlan:
         self.slot = torch.empty((K, nout), dtype=torch.int32, device=dev)
         self.islot = torch.empty((K, nin), dtype=torch.int32, device=dev)
         counts_dev = torch.empty(K + 1, dtype=torch.int32, device=dev)
-        ws = torch.empty(max(lib.vdetr_sp_pair_plan_workspace_ints(K, nout), 1), dtype=torch.int32, device=dev)
+        ws = L.workspace(4 * max(lib.vdetr_sp_pair_plan_workspace_ints(K, nout), 1), dev).view(torch.int32)
         L.check(lib.vdetr_sp_pair_plan_i32(L.ptr(nbr), K, nout, nin, L.ptr(self._pin_buf), L.ptr(self._pout_buf), L.ptr(self.slot),
                                            L.ptr(self.islot) if nin else None, L.ptr(counts_dev), L.ptr(ws), L.stream_ptr()),
                 "sp_pair_plan")
