@@ -542,3 +542,42 @@ def test_kernel_map_full_size_symmetry():
     assert torch.equal(plan.slot[kidx, plan.pout.long()].long(), p)              # slot finds the pair back from its output row
     assert torch.equal(plan.islot[kidx, plan.pin.long()].long(), p)              # islot from its input row
     assert int((plan.slot >= 0).sum()) == plan.P and int((plan.islot >= 0).sum()) == plan.P
+
+
+def test_kernel_map_with_offsets_beyond_the_fields():
+    """Offsets that no 16-bit field and no 32-bit sum holds: sites at the corners of the key range, moved by +-1, +-65535 (which
+    reaches the opposite corner), 65536 and the ends of int32.  The oracle moves every field in int64; a moved field that leaves
+    its range is -1 and never carries into its neighbour.  The same sites and offsets through the region-keys launch."""
+    import ctypes
+
+    import expand_restatement as E
+    from vdetr_amd import _lib as L
+    from vdetr_amd import sparse_ops as S
+    sites = np.array([[0, -32768, -32768, -32768], [0, -32768, -32768, 32767], [0, -32768, 32767, 32767],
+                      [1, 0, 0, 0], [1, 1, 0, 0], [1, 32767, 32767, -32768]], dtype=np.int64)
+    big, small = 2 ** 31 - 1, -2 ** 31
+    offsets = np.array([(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 0, 65535), (0, -65535, 0), (65536, 0, 0), (big, 0, 0), (0, small, 0),
+                        (big, big, small)], dtype=np.int64)
+    keys = torch.from_numpy(O.pack_keys_np(sites))
+    assert bool((keys[1:] > keys[:-1]).all())
+    off = torch.from_numpy(offsets).to(torch.int32)
+    assert np.array_equal(off.numpy().astype(np.int64), offsets)
+    ref = O.kernel_map(keys, keys, off)
+    # every site finds itself; the interior pair finds each other; the +-65535 moves land on the occupied opposite corner
+    assert ref[0].tolist() == list(range(6)) and ref[1].tolist() == [-1, -1, -1, 4, -1, -1] and ref[2].tolist() == [-1, -1, -1, -1, 3, -1]
+    assert ref[3].tolist() == [1, -1, -1, -1, -1, -1] and ref[4].tolist() == [-1, -1, 1, -1, -1, -1]
+    assert int((ref >= 0).sum()) == 10 and int((ref[5:] >= 0).sum()) == 0
+    got = S.kernel_map(keys.to(DEV), keys.to(DEV), off.to(DEV))
+    assert torch.equal(got.cpu(), ref)
+
+    # the region-keys launch itself (sparse_ops.region_keys refuses a region that leaves the range): candidate [k][i], -1 outside
+    c = E.candidates(sites, offsets, 1, 1, True).reshape(len(sites), len(offsets), 4)  # site + offset, in int64
+    inside = ((c[:, :, 1:] >= -32768) & (c[:, :, 1:] <= 32767)).all(2)
+    want = np.where(inside, O.pack_keys_np(c.reshape(-1, 4)).reshape(inside.shape), -1).T
+    assert inside.sum(0).tolist() == [6, 5, 3, 2, 2, 0, 0, 0, 0]  # candidates inside the range, per offset
+    dkeys, doff = keys.to(DEV), off.to(DEV)
+    cand = torch.full((want.size,), -7, dtype=torch.int64, device=DEV)
+    d = L.SpRegionKeysDesc()
+    d.N, d.K, d.keys, d.offsets, d.cand = len(sites), len(offsets), dkeys.data_ptr(), doff.data_ptr(), cand.data_ptr()
+    L.check(L.lib().vdetr_sp_region_keys_i64(ctypes.byref(d), L.stream_ptr()), "sp_region_keys")
+    assert np.array_equal(cand.cpu().numpy().reshape(want.shape), want)

@@ -7,10 +7,7 @@
 // Parity is unpinned against the MinkowskiEngine binary; the oracle (oracle/sparse_oracle.py) pins these kernels against
 // torch's dense conv3d / conv_transpose3d on densified grids.
 //
-// Layout: a sparse tensor = sorted int64 voxel KEYS [N] + a point-major feature table [N, C] (exactly what the hot path's
-// FPS / row gathers consume downstream).  A key packs (batch, x, y, z) as 16-bit biased fields, so ascending key order =
-// lexicographic (batch, x, y, z) order and a neighbour lookup is a binary search in an L2-resident array (40 k keys =
-// 320 KB) instead of a hash table: no atomics, no collisions, and the resulting maps are deterministic.
+// Layout: a sparse tensor = sorted int64 voxel KEYS [N] (sparse_key.h) + a point-major feature table [N, C].
 //   vdetr_sp_kernel_map_i32   nbr[k][u]  = row of the input site at out_key[u] + offset[k], or -1         (geometry only:
 //   vdetr_sp_inverse_map_i32  inv[k][i]  = the output u that reads input i through offset k, or -1         once per scene)
 //   vdetr_sp_gather_cols_f32  col[u][k][:] = in[nbr[k][u]][:] or 0     (the im2col operand of ONE library GEMM per layer)
@@ -26,39 +23,19 @@
 #include <mutex>
 #include "block_scan.h"
 #include "bn_common.h"
+#include "sparse_key.h"
 
 namespace vdetr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr long long kKeyBias = 32768;
-
-__device__ __forceinline__ long long sp_key_add(long long key, int dx, int dy, int dz, bool& ok) {
-  const int b = (int)((unsigned long long)key >> 48);
-  const int x = (int)((key >> 32) & 0xFFFF) + dx, y = (int)((key >> 16) & 0xFFFF) + dy, z = (int)(key & 0xFFFF) + dz;
-  ok = ((unsigned)x | (unsigned)y | (unsigned)z) < 65536u;  // a neighbour outside the 16-bit box cannot be occupied
-  return ((long long)b << 48) | ((long long)x << 32) | ((long long)y << 16) | (long long)z;
-}
-
-// lower bound in a sorted array; -1 if `key` is absent
-__device__ __forceinline__ int sp_find(const long long* __restrict__ keys, int n, long long key) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (keys[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < n && keys[lo] == key) ? lo : -1;
-}
 
 __global__ __launch_bounds__(256) void sp_kernel_map_kernel(const long long* __restrict__ in_keys, int nin,
                                                            const long long* __restrict__ out_keys, int nout,
                                                            const int* __restrict__ offsets, int K, int* __restrict__ nbr) {
   const int u = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
   if (u >= nout) return;
-  bool ok;
-  const long long q = sp_key_add(out_keys[u], offsets[k * 3], offsets[k * 3 + 1], offsets[k * 3 + 2], ok);
-  nbr[(size_t)k * nout + u] = ok ? sp_find(in_keys, nin, q) : -1;
+  const long long q = key_shift(out_keys[u], offsets[k * 3], offsets[k * 3 + 1], offsets[k * 3 + 2]);
+  nbr[(size_t)k * nout + u] = q < 0 ? -1 : key_find(in_keys, nin, q);
 }
 
 __global__ __launch_bounds__(256) void sp_inverse_map_kernel(const int* __restrict__ nbr, int K, int nout, int nin,

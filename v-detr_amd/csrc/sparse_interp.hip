@@ -14,7 +14,7 @@
 //   two roundings of the real quotient, and may round to exactly 1: the lower corner's weight is then an exact 0 and the upper
 //   one's 1, which is the nearest float32 statement of the same point.
 // Corner k = 4 bx + 2 by + bz, bit 1 = the upper site lo + s; w = (fx * fy) * fz with f = b ? t : 1 - t.  A corner whose
-// coordinate leaves the 16-bit field of the key is absent (-1): it is tested on the coordinate BEFORE the key is packed, so
+// coordinate leaves its field of the key (sparse_key.h) is absent (-1): it is tested on the coordinate BEFORE the key is packed, so
 // nothing carries into the neighbouring field.  w = 0 wherever nbr = -1.  A row with a non-finite coordinate, a floorf outside
 // -32768 .. 32767 or a batch value that is not an integer in 0 .. 32767 gets eight -1.
 // The eight corners are four z-adjacent pairs: ONE lower bound per pair (four interleaved binary searches over the sorted keys,
@@ -35,11 +35,11 @@
 // One lane per (site, float4 of channels | channel), four pairs' loads in flight per lane, the adds in order.  No atomics: two
 // runs give the same bits.  A site with L pairs is L dependent adds on its lanes: every point in one cell is eight serial walks.
 #include "common.h"
+#include "sparse_key.h"
 
 namespace vdetr {
 
 constexpr int kInterpTile = 256;  // points per workgroup of the map launch (vdetr_sp_interp_tile)
-constexpr int kInterpBias = 32768;
 
 struct InterpMapParams {
   int M, N, s, steps;      // steps: binary-search steps that empty any range of M keys
@@ -60,8 +60,6 @@ __device__ __forceinline__ bool interp_axis(float x, int s, int& lo, float& t) {
   return true;
 }
 
-__device__ __forceinline__ bool interp_in_field(int c) { return (unsigned)(c + kInterpBias) < 65536u; }
-
 __global__ __launch_bounds__(kInterpTile) void interp_map_kernel(InterpMapParams P) {
   const int n = (int)blockIdx.x * kInterpTile + (int)threadIdx.x;
   if (n >= P.N) return;
@@ -77,18 +75,18 @@ __global__ __launch_bounds__(kInterpTile) void interp_map_kernel(InterpMapParams
 #pragma unroll
   for (int k = 0; k < 8; ++k) { nb[k] = -1; wt[k] = 0.f; }
   if (row && P.M > 0) {
-    const int64_t b = (int64_t)(int)p.x << 48;
-    const bool zlo_in = interp_in_field(lo[2]), zhi_in = interp_in_field(lo[2] + P.s);
+    const bool zlo_in = key_in_field(lo[2]), zhi_in = key_in_field(lo[2] + P.s);
     // the key of the lower-z corner of pair j = 2 bx + by (z clamped into the field: an absent lower z still places the search)
     int64_t key[4];
     bool in[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int x = lo[0] + (j >> 1) * P.s, y = lo[1] + (j & 1) * P.s;
-      in[j] = interp_in_field(x) && interp_in_field(y) && (zlo_in || zhi_in);
+      in[j] = key_in_field(x) && key_in_field(y) && (zlo_in || zhi_in);
       const int z = zlo_in ? lo[2] : lo[2] + P.s;
-      key[j] = b | ((int64_t)(x + kInterpBias) << 32) | ((int64_t)(y + kInterpBias) << 16) | (int64_t)(z + kInterpBias);
+      key[j] = key_pack_fields((int)p.x, x, y, z);  // (tested above: a pair that is not `in` never reads its key's row)
     }
+    // four lower bounds interleaved, four loads in flight per step: deliberately not four calls of key_lower_bound
     int a[4] = {0, 0, 0, 0}, e[4] = {P.M, P.M, P.M, P.M};  // lower bounds: keys[< a] < key <= keys[>= e]
     for (int step = 0; step < P.steps; ++step) {
 #pragma unroll
@@ -109,13 +107,7 @@ __global__ __launch_bounds__(kInterpTile) void interp_map_kernel(InterpMapParams
         key[j] += P.s;  // (z + s is inside the field: no carry)
       }
       // the upper z: the next sorted key on a lattice of s; a key in between (off the lattice) asks for a search of its own
-      if (at < P.M && P.keys[at] < key[j]) {
-        int hi = P.M;
-        while (at < hi) {
-          const int mid = (int)(((unsigned)at + (unsigned)hi) >> 1);
-          if (P.keys[mid] < key[j]) at = mid + 1; else hi = mid;
-        }
-      }
+      if (at < P.M && P.keys[at] < key[j]) at += key_lower_bound(P.keys + at, P.M - at, key[j]);
       if (at < P.M && P.keys[at] == key[j]) nb[2 * j + 1] = at;
     }
 #pragma unroll
@@ -192,12 +184,7 @@ __global__ __launch_bounds__(256) void interp_seg_kernel(InterpSegParams P) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i < P.P) P.order32[i] = (int32_t)P.order[i];
   if (i <= P.M) {  // seg[m] = the first sorted position whose site row is >= m; seg[M] = P (rows are below M)
-    int lo = 0, hi = P.P;
-    while (lo < hi) {
-      const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-      if (P.sorted[mid] < (int)i) lo = mid + 1; else hi = mid;
-    }
-    P.seg[i] = lo;
+    P.seg[i] = key_lower_bound(P.sorted, P.P, (int32_t)i);
   }
 }
 

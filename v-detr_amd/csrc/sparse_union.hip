@@ -9,7 +9,7 @@
 // Geometry.  Both maps are the two-launch compaction of block_scan.h over tiles of kUnionTile keys.
 // The outputs are allocated at their bound (na + nb, N) and the total is the ONE 4-byte word the host reads, after launch 2.
 //
-// Union of A [na] and B [nb] (sorted, unique), symmetric in the two sides.  With q(i) = |{j : B[j] < A[i]}| (a binary search) and
+// Union of A [na] and B [nb] (sorted, unique), symmetric in the two sides.  With q(i) = |{j : B[j] < A[i]}| (sparse_key.h's lower bound) and
 // m(i) = |{i' < i : A[i'] in B}| (a prefix over A's OWN flags, which is what makes the scan local to a side):
 //   row_a[i] = i + q(i) - m(i)        (the keys of B below A[i] that A does not hold come before it)
 // and the same with the sides exchanged.  Launch 1 keeps q and the flag of every key in the workspace, launch 2 only scans.
@@ -19,6 +19,7 @@
 // Features.  Whole-row gathers as in sparse_pool.hip: a thread owns one row's channel quad (16 bytes).  A missing operand is
 // SELECTED as zero, not multiplied away: an infinity on a row the other side lacks stays an infinity.
 #include "block_scan.h"
+#include "sparse_key.h"
 #include "workspace.h"
 
 namespace vdetr {
@@ -28,15 +29,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kUnionThreads = 256;
 constexpr int kUnionItems = 4;                             // consecutive keys per thread
 constexpr int kUnionTile = kUnionThreads * kUnionItems;    // keys per workgroup (vdetr_sp_union_tile)
-
-__device__ __forceinline__ int lower_bound_i64(const int64_t* keys, int n, int64_t key) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 struct UnionParams {
   int na, nb, ta, tb;  // keys and tiles per side; tile t < ta belongs to A
@@ -62,7 +54,7 @@ __global__ __launch_bounds__(kUnionThreads) void union_search_kernel(UnionParams
     const int i = first + e;
     if (i >= n) break;
     const int64_t key = x[i];
-    const int p = lower_bound_i64(y, m, key);
+    const int p = key_lower_bound(y, m, key);
     const bool found = p < m && y[p] == key;
     out[i] = (unsigned)p | (found ? 0x80000000u : 0u);
     matches += found ? 1 : 0;

@@ -9,9 +9,8 @@
 // no host loop), the voxel index is floorf(p * inv) with inv = (float)(1.0 / voxel_size), taken in double and rounded ONCE on the
 // host — the arithmetic of ATen's `tensor / python_float` on the device, which multiplies by a reciprocal instead of dividing, as
 // measured against the device expression itself.  A
-// point that no key can hold (an index outside the 16-bit fields, a non-finite coordinate, a batch index outside 0 .. 32767) gets
-// the key -1: legal keys are non-negative, so after the sort ONE comparison of the first sorted key is the range flag.  No memset,
-// no atomics, every thread writes only its own key.
+// point that no key can hold (sparse_key.h; a non-finite coordinate as well) gets the key -1, which sorts first: after the sort
+// ONE comparison of the first sorted key is the range flag.  No memset, no atomics, every thread writes only its own key.
 //
 // Sites.  The two-launch compaction of block_scan.h over tiles of kVoxelTile SORTED keys and the sort's permutation.  What is
 // counted are the run heads (key[i] != key[i - 1]).  Launch 2 writes, per sorted position i of site row r: inverse[order[i]] = r,
@@ -25,6 +24,7 @@
 // loads on its lanes while the other lanes of the wave idle: L = N (every point in one voxel) is one workgroup's serial walk of
 // the whole table.  Real clouds at 1-5 cm voxels have runs of 1-8.  The gradients are gathers through `inverse`.
 #include "block_scan.h"
+#include "sparse_key.h"
 #include "workspace.h"
 
 namespace vdetr {
@@ -32,16 +32,8 @@ namespace vdetr {
 constexpr int kVoxelThreads = 256;
 constexpr int kVoxelItems = 4;                             // consecutive sorted keys per thread
 constexpr int kVoxelTile = kVoxelThreads * kVoxelItems;    // sorted keys per workgroup (vdetr_sp_voxel_tile)
-constexpr int kKeyBias = 32768;
 
 // ---- keys --------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t pack_key(int b, int x, int y, int z) {
-  const bool ok = (unsigned)b < 32768u && (unsigned)(x + kKeyBias) < 65536u && (unsigned)(y + kKeyBias) < 65536u &&
-                  (unsigned)(z + kKeyBias) < 65536u;
-  if (!ok) return -1;
-  return ((int64_t)b << 48) | ((int64_t)(x + kKeyBias) << 32) | ((int64_t)(y + kKeyBias) << 16) | (int64_t)(z + kKeyBias);
-}
-
 // the voxel index of one coordinate, or an index no key holds (1 << 20) where the coordinate or its product has none
 __device__ __forceinline__ int voxel_index(float p, float inv) {
   const float f = floorf(p * inv);
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(256) void voxel_keys_kernel(VoxelKeysParams P) {
   const bool inside = P.offsets[lo] <= i && i < P.offsets[lo + 1];
   const float* p = P.points + (size_t)i * P.stride;
   const int x = voxel_index(p[0], P.inv), y = voxel_index(p[1], P.inv), z = voxel_index(p[2], P.inv);
-  P.keys[i] = pack_key(inside ? lo : -1, x, y, z);
+  P.keys[i] = key_pack(inside ? lo : -1, x, y, z);
 }
 
 struct CoordKeysParams {
@@ -81,13 +73,12 @@ __global__ __launch_bounds__(256) void coord_keys_kernel(CoordKeysParams P) {
   const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
   if (i >= P.N) return;
   const int4 c = reinterpret_cast<const int4*>(P.coords)[i];
-  P.keys[i] = pack_key(c.x, c.y, c.z, c.w);
+  P.keys[i] = key_pack(c.x, c.y, c.z, c.w);
 }
 
 // The candidate keys of a region (expand_coordinates): one thread per (offset k, site i) writes cand[k * N + i], the key
-// of site i moved by offsets[k] — offset-major, so that adjacent lanes read adjacent keys and write adjacent candidates.  Each
-// field is taken out of the key, moved in 64 bits and tested on its own: a coordinate that leaves -32768 .. 32767 makes the whole
-// candidate -1 (the range flag of the keys above) and never carries into the field beside it.  A negative input key stays -1.
+// of site i moved by offsets[k] (key_shift) — offset-major, so that adjacent lanes read adjacent keys and write adjacent
+// candidates.  A coordinate that leaves its field makes the whole candidate -1, the range flag of the keys above.
 struct RegionKeysParams {
   int N;
   long long total;         // K * N < 2^31
@@ -101,13 +92,8 @@ __global__ __launch_bounds__(256) void region_keys_kernel(RegionKeysParams P) {
   if (t >= P.total) return;
   const int k = (int)(t / P.N);
   const int i = (int)(t - (long long)k * P.N);
-  const int64_t key = P.keys[i];
   const int32_t* o = P.offsets + (size_t)k * 3;
-  const long long x = (long long)((key >> 32) & 0xFFFF) + o[0];  // biased: legal in 0 .. 65535
-  const long long y = (long long)((key >> 16) & 0xFFFF) + o[1];
-  const long long z = (long long)(key & 0xFFFF) + o[2];
-  const bool ok = key >= 0 && x >= 0 && x < 65536 && y >= 0 && y < 65536 && z >= 0 && z < 65536;
-  P.cand[t] = ok ? (int64_t)(((key >> 48) << 48) | (x << 32) | (y << 16) | z) : (int64_t)-1;
+  P.cand[t] = key_shift(P.keys[i], o[0], o[1], o[2]);
 }
 
 // ---- sites -------------------------------------------------------------------------------------------------------------------------
@@ -172,7 +158,7 @@ __global__ __launch_bounds__(kVoxelThreads) void voxel_fill_kernel(VoxelSitesPar
     P.seg[M] = P.N;
     P.count[0] = M;
     // the key of a point out of range sorts first; otherwise the last key holds the highest batch index
-    P.count[1] = P.sorted[0] < 0 ? -1 : (int)(P.sorted[P.N - 1] >> 48) + 1;
+    P.count[1] = P.sorted[0] < 0 ? -1 : key_batch(P.sorted[P.N - 1]) + 1;
   }
 }
 

@@ -386,7 +386,7 @@ class CoordinateManager:
         key = keys.data_ptr()
         if key not in cache:
             if self.num_scenes is None:
-                self.num_scenes = int(keys[-1] >> 48) + 1 if keys.numel() else 0
+                self.num_scenes = int(S.key_batch(keys[-1])) + 1 if keys.numel() else 0
             cache[key] = (S.scene_segments(keys, self.num_scenes), keys)
         return cache[key][0], self.num_scenes
 
@@ -395,8 +395,7 @@ class CoordinateManager:
         writes its rows (``tensor_stride`` 0 marks them).  Built on the device once the scene count is known."""
         assert self.num_scenes is not None, "origin_keys: the scene count is not known yet (scene_segments reads it)"
         if 0 not in self.keys:
-            centre = (S.KEY_BIAS << 32) | (S.KEY_BIAS << 16) | S.KEY_BIAS
-            self.keys[0] = (torch.arange(self.num_scenes, dtype=torch.int64, device=self.device) << 48) | centre
+            self.keys[0] = S.origin_keys(self.num_scenes, self.device)
         return self.keys[0]
 
     def scene_counts(self, keys):
@@ -406,7 +405,7 @@ class CoordinateManager:
         cache = self.__dict__.setdefault("_scene_counts", {})
         key = keys.data_ptr()
         if key not in cache:
-            b = keys >> 48
+            b = S.key_batch(keys)
             nb = int(b.max()) + 1 if b.numel() else 0
             # (a key set from which MinkowskiPruning took a whole scene still has one entry per scene of the batch)
             nb = max(nb, self.num_scenes or 0)

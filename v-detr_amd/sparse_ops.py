@@ -39,6 +39,23 @@ def unpack_keys(keys):
     return torch.stack((b, x, y, z), dim=1).to(torch.int32)
 
 
+def key_batch(keys):
+    """int64 keys -> their batch index (int64)."""
+    return keys >> 48
+
+
+def scene_floor_keys(nseg, device):
+    """[nseg + 1] int64: the smallest key of each scene 0 .. nseg; scene s of a sorted key vector lies between the lower bounds
+    of entries s and s + 1."""
+    return torch.arange(nseg + 1, dtype=torch.int64, device=device) << 48
+
+
+def origin_keys(num_scenes, device):
+    """[num_scenes] int64: the key of the site (b, 0, 0, 0) of every scene, in order."""
+    centre = (KEY_BIAS << 32) | (KEY_BIAS << 16) | KEY_BIAS
+    return (torch.arange(num_scenes, dtype=torch.int64, device=device) << 48) | centre
+
+
 def kernel_map(in_keys, out_keys, offsets):
     """nbr [K, Nout] int32: row of the (sorted) input site at out_keys[u] + offsets[k], -1 where unoccupied."""
     L.require_gpu(in_keys, "in_keys")
@@ -872,8 +889,7 @@ class _SpInstanceNormFn(Function):
 
 def scene_segments(keys, nseg):
     """seg [nseg + 1] int32 on the device: scene s of a sorted key vector is the rows seg[s] .. seg[s+1].  No host read."""
-    bounds = torch.arange(nseg + 1, dtype=torch.int64, device=keys.device) << 48
-    return torch.searchsorted(keys, bounds).to(torch.int32)
+    return torch.searchsorted(keys, scene_floor_keys(nseg, keys.device)).to(torch.int32)
 
 
 def instance_norm(x, seg, nseg, weight=None, bias=None, eps=1e-6):
