@@ -3,8 +3,10 @@ answers by tests/test_drop_stream.py): bit for bit, per stream and dispatch arm,
 
 The step's device state {seed, offset} is read back after reset_rng() and begin_step(); the by-value seed of a launch is its
 `salt`, the by-value offset 0.  Masks are read out of the kernels as tests/test_gpu_norm_parity.py does (LayerNorm: x = 0, r = 1;
-BatchNorm: gamma = 1 on x = 0; relu_dropout: ones) and through attention.dropout_keep_mask.  The row-block and heads kernels draw
-the same streams and are held to these launches by test_gpu_rowblock.py and test_gpu_heads.py.
+BatchNorm: gamma = 1 on x = 0; relu_dropout: ones) and through attention.dropout_keep_mask.  The row-block kernels draw the same
+streams: test_gpu_rowblock_parity.py reads their four masks (and ffn0's two) out of the launches and holds them to the same host
+restatement, bit for bit, at a tail block and at three scenes; test_gpu_rowblock.py still holds them to these launches through a
+whole layer.  The heads kernels are held to these launches by test_gpu_heads.py.
 
 Not reached at test size: the `(i >> 32)` term of the flat form (a tensor of 2^34 floats); tests/drop_stream_check.cpp covers it
 on the host."""
